@@ -17,7 +17,12 @@ Workloads, weak scaling, one rank per GPU, no collective on the d
 `python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself, before
 anything touches a GPU, and forwards rank 0's line; under torchrun it runs as one of the ranks.
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: it generates the clips, parses them once into resident descriptors, warms up,
+times `--steps` steps and prints the line (`roofline` is derived from the timed steps and the committed profiles).
+`--dump-outputs DIR` then also writes what the last timed step left for its caller (rank 0's resident pictures) as float32 .npy
+files.  `--full` adds everything else below: the oracle parity check, the free-running replay, the CPU baseline and the side legs.
+
+Extra objects on the JSON line (`--full` only, except `roofline`):
   roofline      algorithmic bytes (1.5 B/px written + 1.5 B/px read for P/B) of a step / HIP-event
                 time of the step on the launch stream (= bytes per launch / average launch duration: the step is its 7
                 launches), vs 8 TB/s; `traffic` = HBM bytes per launch from the committed rocprofv3 PMC passes
@@ -68,6 +73,10 @@ def parse_args(argv=None):
     ap.add_argument("--mv-bits", default="0,1,2", help="vector residual-bit choices of the synthetic P/B pictures (reach = 16 << bits samples)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes that generate the synthetic clips (0 = cores / ranks)")
     ap.add_argument("--clip-cache", default="", help="directory that keeps generated clips between runs (profiling passes of one workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity check against the CPU oracle, the free-running replay, the CPU baseline and the side legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write rank 0's resident pictures (what the last step computed) to DIR/*.npy as float32")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal, no GPU: start the ranks, rendezvous, bind cores (sysfs tree from HVQM4_AMD_SYSFS), deal the "
                          "clips / streams to the ranks, reduce -- and print what every rank would decode")
@@ -239,6 +248,7 @@ def main():
     from hvqm4_amd.synth import SynthConfig
 
     mv_bits = tuple(int(x) for x in args.mv_bits.split(","))
+    full = args.full                    # everything beside the headline (module docstring)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     copy_threads, my_cores, my_node, pin_how = pin_rank(local_rank % max(1, local_world), local_world)
     workers = args.gen_workers or usable_cores()                # after pin_rank: the cores of this rank's slice, capped by the cgroup quota
@@ -264,7 +274,7 @@ def main():
     # (spawn) from a GPU-initialised parent -- under rocprofv3 every child gets the tool injected (round 4's evidence logs ended
     # in eight "Aborted" blocks from exactly that) -- and this pool is touchy about it
     c4_share_clips = single_clips = None
-    if rank == 0 and world == 1 and not args.no_sdk:
+    if full and rank == 0 and world == 1 and not args.no_sdk:
         c4_share_clips = gen_clips(c4_share_configs(), workers, args.clip_cache)
         single_clips = gen_clips([SynthConfig(width=320, height=240, version="1.5", gop="I", n_gops=64, seed=2, preset=args.preset),
                                   SynthConfig(width=640, height=480, version="1.5", gop=GOP16, seed=1000, preset=args.preset)],
@@ -274,7 +284,7 @@ def main():
 
     # CPU baseline first: the host is otherwise idle, and its worker processes start before this process touches the GPU
     cpu_base = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         c3 = clips[0] if (args.workload == "c5" and (args.width, args.height, args.gop) == (640, 480, GOP16)) else None
         cpu_base = cpu_baseline(args.cpu_seconds, c3, args.preset)
     _GPU_OPEN = True                    # from here on gen_clips refuses to start a process pool
@@ -306,7 +316,7 @@ def main():
     # ... and once more in steady state (a context of its own, second pass: the pinned arenas and the workers' buffers are sized by then --
     # the first pass above pays for a few hundred MB of pinned allocation)
     e2e_steady = None
-    if rank == 0 and world == 1 and not args.no_sdk:
+    if full and rank == 0 and world == 1 and not args.no_sdk:
         ctxh = batch.Context(device)
         sidh = [ctxh.open_stream(clips[ci].width, clips[ci].height, 2, 2, clips[ci].version == "1.5", args.nslots) for ci in stream_clip]
         a_sidh = [sidh[s] for s in a_stream]
@@ -326,7 +336,7 @@ def main():
     # ---- parity check against the CPU oracle on what is still resident ----
     # every stream keeps its last min(nslots, pictures) pictures; the first `distinct` streams (c4: every 4th clip) are checked
     verified = expected = None
-    if not args.no_verify:
+    if full and not args.no_verify:
         from oracle import bridge
         verified = expected = 0
         check = list(range(min(args.distinct, len(sids)))) if args.workload == "c5" else list(range(0, len(sids), 4))
@@ -364,16 +374,18 @@ def main():
     gpu_ms = ctx.replay_stage(args.steps, 1)  # K steps, timed by HIP events on the launch stream
     barrier()
     wall = grp.max(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, sids, [len(pics[ci]) for ci in stream_clip], args.dump_outputs)
     # beside the headline: the same launches with the launch queues running free over all steps (forked once, joined once: rounds
     # 1-5's timed region -- a queue that is ahead runs into the next step)
-    recon_ms = ctx.replay(args.steps)
+    recon_ms = ctx.replay(args.steps) if full else None
     st = ctx.stats()
 
     # ---- end to end with the entropy parse ON THE GPU, on EVERY rank at once: raw bitstreams in
     # host memory -> H2D -> parse kernel -> reconstruction launches; host copy threads, pinned arenas and PCIe of all
     # ranks contend as they would in production.  Second pass of a fresh context = steady state (buffers sized).
     gpu_e2e = None
-    if not args.no_gpu_parse:
+    if full and not args.no_gpu_parse:
         ctx2 = batch.Context(device)
         sids2 = [ctx2.open_stream(clips[ci].width, clips[ci].height, 2, 2, clips[ci].version == "1.5", args.nslots)
                  for ci in stream_clip]
@@ -649,8 +661,6 @@ def main():
     # per-kernel average from the committed kernel trace of this same command (profiles/*_kernel_stats.csv).
     stage_s = gpu_ms * 1e-3 / args.steps
     avg_launch_s = stage_s / (launches / queues)
-    free_s = recon_ms * 1e-3 / args.steps
-    free_achieved = st.algorithmic_bytes / free_s / 1e9
     achieved = st.algorithmic_bytes / stage_s / 1e9
     traffic = pmc_traffic(args)
     trace = kernel_trace_avg(args)
@@ -694,10 +704,6 @@ def main():
             "traffic_what": "HBM bytes per launch of the dominant kernel (hvq_recon_inline_kernel), PMC passes",
             "valu": pmc_valu(args),
             "kernel": "hvq_recon_inline_kernel", "algorithmic_bytes_per_launch": int(st.algorithmic_bytes // launches),
-            "free_running": {"achieved": round(free_achieved, 1), "frac": round(free_achieved / HBM_PEAK_GBS, 4),
-                             "us_per_step": round(free_s * 1e6, 2),
-                             "what": "the same launches with the launch queues forked once and joined once around all timed steps (hvq_replay; "
-                                     "the timed region of rounds 1-5): a queue that is ahead runs into the next step.  Never the headline"},
             "avg_launch_us": round(avg_launch_s * 1e6, 2),
             "avg_launch_us_what": "derived: joined step time / (launches / queues) -- a queue's launches run back to back",
             "avg_launch_us_measured": trace["avg_us"] if trace else None,
@@ -711,7 +717,7 @@ def main():
             "descriptor_bytes_what": "blobs (maps, vectors, payload pools, nests) per reconstruction launch; not credited",
         },
         "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4),
-        "gpu_event_ms_per_step_free_running": round(recon_ms / args.steps, 4),
+        "full": full,
         "end_to_end_gpu_parse": gpu_e2e,
         "end_to_end": {"value": round(px_step / t_e2e / 1e6, 1), "unit": "Mpixels/s", "parse_threads": threads,
                        "parse_only_mpix_s": round(px_step / t_parse / 1e6, 1),
@@ -723,31 +729,39 @@ def main():
         "verified_pictures": verified, "verified_pictures_expected": expected,
         "flags_or": int(st.flags_or),
     }
+    if recon_ms is not None:
+        free_s = recon_ms * 1e-3 / args.steps
+        free_achieved = st.algorithmic_bytes / free_s / 1e9
+        out["roofline"]["free_running"] = {
+            "achieved": round(free_achieved, 1), "frac": round(free_achieved / HBM_PEAK_GBS, 4), "us_per_step": round(free_s * 1e6, 2),
+            "what": "the same launches with the launch queues forked once and joined once around all timed steps (hvq_replay; "
+                    "the timed region of rounds 1-5): a queue that is ahead runs into the next step.  Never the headline"}
+        out["gpu_event_ms_per_step_free_running"] = round(recon_ms / args.steps, 4)
 
     # display epilogue: YUV420 -> RGB24 of the newest picture of every stream, one launch
-    try:
-        ctx.rgb_bench(2)
-        rms, rbytes, rpics = ctx.rgb_bench(50)
-        out["rgb_epilogue"] = {"kernel": "hvq_yuv420_rgb_kernel", "pictures_per_launch": rpics,
-                               "bytes_per_launch": rbytes, "avg_launch_us": round(rms * 1e3 / 50, 2),
-                               "achieved_GBs": round(rbytes * 50 / (rms * 1e-3) / 1e9, 1),
-                               "frac_of_8TBs": round(rbytes * 50 / (rms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-    except Exception as e:      # never let the optional epilogue measurement break the headline number
-        out["rgb_epilogue"] = {"error": str(e)}
+    if full:
+        try:
+            ctx.rgb_bench(2)
+            rms, rbytes, rpics = ctx.rgb_bench(50)
+            out["rgb_epilogue"] = {"kernel": "hvq_yuv420_rgb_kernel", "pictures_per_launch": rpics,
+                                   "bytes_per_launch": rbytes, "avg_launch_us": round(rms * 1e3 / 50, 2),
+                                   "achieved_GBs": round(rbytes * 50 / (rms * 1e-3) / 1e9, 1),
+                                   "frac_of_8TBs": round(rbytes * 50 / (rms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+        except Exception as e:      # never let the optional epilogue measurement break the headline number
+            out["rgb_epilogue"] = {"error": str(e)}
 
     # the SDK boundary itself (PCIe-inclusive, never `value`): one stream, one synchronous call per picture -- upload
     # of the caller's reference pictures, host parse, launch, download of the decoded picture
-    if rank == 0 and world == 1 and not args.no_sdk:
+    if full and rank == 0 and world == 1 and not args.no_sdk:
         out["sdk_path"] = sdk_leg(clips[0], pics[0])
 
     if cpu_base is not None:
         out["cpu_baseline"] = cpu_base
-    last_single = [ctx.read_picture(sids[s], len(pics[stream_clip[s]]) - 1) for s in range(min(4, len(sids)))]
     ctx.close()
     # the same 2048 pictures per step with the GOP phase of the streams STAGGERED (stream s is s mod 16 pictures into its GOP when
     # the batch starts): every launch then holds I, P and B pictures in the stream's own proportion instead of one kind per
     # dependency level.  An extra line; the headline stays lock-step (every stream at the same picture, as a batch of players is).
-    if rank == 0 and world == 1 and not args.no_sdk and args.workload == "c5" and all(len(p) == 16 for p in pics):
+    if full and rank == 0 and world == 1 and not args.no_sdk and args.workload == "c5" and all(len(p) == 16 for p in pics):
         try:
             from oracle import bridge as _bridge
             ctxs = batch.Context(device)
@@ -801,7 +815,7 @@ def main():
 
     # BASELINE config 4 at the shape one GPU of eight sees it: clips 0, 8, ..., 56 of the 64 (4 x 320x240 + 4 x 640x480, HVQM4 1.3
     # and 1.5 alternating), every picture checked against the SHA-256 the REFERENCE decoder produced (tests/golden/manifest.json)
-    if rank == 0 and world == 1 and not args.no_sdk:
+    if full and rank == 0 and world == 1 and not args.no_sdk:
         out["c4_share"] = c4_share_leg(device, args.steps, args.warmup or 1, threads, c4_share_clips)
         # BASELINE configs 2 and 3: ONE clip on one GPU (latency-bound by construction: a 16-picture GOP is seven dependent launches)
         out["single_clip"] = {"C2": single_clip_leg(device, single_clips[0], args.steps, args.warmup or 1, not args.no_verify),
@@ -810,6 +824,42 @@ def main():
     if rank == 0:
         grp.emit(json.dumps(out))
     grp.close()
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ctx, sids, n_pics, out_dir):
+    """--dump-outputs: what the last timed step left in the streams' slots, i.e. what a caller reads back (Y|U|V, uint8), as float32:
+      picture_sNNN.npy    the newest picture of each of the first (up to 8) streams, whole
+      resident_sample.npy one row per resident picture of every stream (stream-major, ordinals ascending), the same seeded positions
+                          (fractions of the picture size) in every row
+    The inputs are seeded, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    from hvqm4_amd._lib import HVQ_E_STATE, HvqError
+    os.makedirs(out_dir, exist_ok=True)
+    used = 0
+    for s in range(min(8, len(sids))):
+        pic = ctx.read_picture(sids[s], n_pics[s] - 1).astype(np.float32)
+        if used + pic.nbytes > DUMP_BYTES // 2:
+            break
+        np.save(os.path.join(out_dir, f"picture_s{s:03d}.npy"), pic)
+        used += pic.nbytes
+    # positions per row sized for every ordinal (the resident ones are fewer), so that the sample fits whatever the ring keeps
+    k = max(1, min(8192, (DUMP_BYTES - used) // (4 * max(1, sum(n_pics)))))
+    frac = np.sort(np.random.default_rng(DUMP_SEED).random(k))
+    rows = []
+    for s, sid in enumerate(sids):
+        for o in range(n_pics[s]):
+            try:
+                p = ctx.read_picture(sid, o)
+            except HvqError as e:
+                if e.code != HVQ_E_STATE:
+                    raise
+                continue                    # slot reused by a later picture
+            rows.append(p[(frac * p.size).astype(np.int64)])
+    np.save(os.path.join(out_dir, "resident_sample.npy"), np.stack(rows).astype(np.float32))
 
 
 def dry_run(args, grp):

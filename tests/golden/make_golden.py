@@ -6,6 +6,7 @@ clip of tests/clips.py it stores the expected output of the reference (Tilka/hvq
 h4m_audio_decode.c, compiled by oracle/Makefile):
   - small clips: the .h4m bytes (synthetic, produced by hvqm4_amd/synth.py) + SHA-256 per picture
   - medium clips: SHA-256 of the clip bytes (guards against generator drift) + SHA-256 per picture
+  - small clips: where the reference's 20 bit-buffer cursors stop after every picture (ref_cursors.json)
 The fixtures are data (inputs and expected outputs), not reference source.
 """
 import hashlib
@@ -26,6 +27,8 @@ def main():
         raise SystemExit("oracle/_ref/libh4mref.so missing: run `make -C oracle ref` where /root/reference exists")
     manifest = {"generator": "tests/golden/make_golden.py", "reference": "Tilka/hvqm4 h4m_audio_decode.c (gcc -O2, -DNATIVE=1)",
                 "clips": {}}
+    cursors = {"generator": "tests/golden/make_golden.py", "what": "probe of ref_decode_clip: per picture, the byte offset at which "
+               "each of the reference's 20 bit-buffer cursors stops (-1: empty section)", "clips": {}}
     for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE:
         clip = clips.get((name, cfg))
         pics, probe = bridge.ref_decode(clip.data, clip.n_pictures, probe=True)
@@ -42,6 +45,7 @@ def main():
             with open(os.path.join(HERE, name + ".h4m"), "wb") as f:
                 f.write(clip.data)
             entry["file"] = name + ".h4m"
+            cursors["clips"][name] = probe.tolist()
         manifest["clips"][name] = entry
         print(name, len(clip.data), "bytes", clip.n_pictures, "pictures")
     # known-answer vectors of the pixel primitives, from the reference's own functions
@@ -81,6 +85,8 @@ def main():
                             "64x48": int(lib.ref_buffsize(64, 48, 2, 2))}
     with open(os.path.join(HERE, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)
+    with open(os.path.join(HERE, "ref_cursors.json"), "w") as f:
+        json.dump(cursors, f, separators=(",", ":"))
     print("wrote manifest.json")
 
 

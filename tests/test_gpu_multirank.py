@@ -21,7 +21,7 @@ def _bench(*extra, env=None):
     e.update(env or {})
     e.pop("WORLD_SIZE", None); e.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--streams", "8", "--distinct", "2", "--width", "320",
-           "--height", "240", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-sdk"] + list(extra)
+           "--height", "240", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-sdk", "--full"] + list(extra)
     p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads(p.stdout.strip().splitlines()[-1])

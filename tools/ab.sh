@@ -3,7 +3,7 @@
 # usage: tools/ab.sh <tag> "<presets>" <reps> name[:ENV=v[,ENV=v...]] ...        (ENV may include HVQM4_AMD_LIB=path)
 T=$1; P=$2; R=$3; shift 3
 O=gpurun_out/$T; mkdir -p $O
-C="--clip-cache /tmp/hvq_clip_cache --no-sdk --no-gpu-parse --cpu-seconds 0"
+C="--full --clip-cache /tmp/hvq_clip_cache --no-sdk --no-gpu-parse --cpu-seconds 0"
 for p in $P; do
   for rep in $(seq 1 $R); do
     for v in "$@"; do

@@ -6,7 +6,7 @@ tag=${1:-sab}; reps=${2:-2}; shift 2 || true
 out=gpurun_out/$tag; mkdir -p $out
 for r in $(seq 1 $reps); do
   for ps in 1; do
-    timeout -k 10 400 python bench.py --no-sdk --cpu-seconds 0 --clip-cache /tmp/hvq_clip_cache "$@" > $out/ps${ps}_$r.json 2> $out/ps${ps}_$r.err || { tail -5 $out/ps${ps}_$r.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --no-sdk --cpu-seconds 0 --clip-cache /tmp/hvq_clip_cache "$@" > $out/ps${ps}_$r.json 2> $out/ps${ps}_$r.err || { tail -5 $out/ps${ps}_$r.err; exit 1; }
     python - $out/ps${ps}_$r.json "rep $r" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
