@@ -7,12 +7,13 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import HvqStats, check, lib
+from ._lib import HVQ_E_ARG, HvqError, HvqStats, check, lib
 
 
 class Context:
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
+        self._geom = {}                                    # stream id -> (width, height), for export()
         check(lib().hvq_context_create(device, C.byref(self._h)))
 
     def set_launch_queues(self, n: int) -> None:
@@ -21,10 +22,13 @@ class Context:
 
     def open_stream(self, width: int, height: int, h_samp: int = 2, v_samp: int = 2, is15: bool = True,
                     nslots: int = 4) -> int:
-        return check(lib().hvq_stream_open(self._h, width, height, h_samp, v_samp, int(is15), nslots))
+        sid = check(lib().hvq_stream_open(self._h, width, height, h_samp, v_samp, int(is15), nslots))
+        self._geom[sid] = (width, height)
+        return sid
 
     def close_stream(self, sid: int) -> None:
         check(lib().hvq_stream_close(self._h, sid))
+        self._geom.pop(sid, None)
 
     def set_parse_threads(self, sid: int, threads: int) -> int:
         """host threads that share the parse of ONE picture of this stream (hvq_stream_set_parse_threads); returns the count in effect"""
@@ -161,6 +165,31 @@ class Context:
         ptr = C.c_void_p()
         check(lib().hvq_picture_device_ptr(self._h, sid, ordinal, C.byref(ptr)))
         return int(ptr.value or 0)
+
+    def export(self, sids, ordinals, out, fmt: str = "rgb") -> None:
+        """hvq_export_pictures: resident pictures into uint8 CUDA tensors, in one launch on torch's current stream of `out`'s
+        device, without a host synchronisation.  fmt "rgb" -> [H, W, 3], "rgbp" (RGB planar) and "yuv444p" -> [3, H, W]; `out` is
+        one tensor [N, ...] (pictures of one geometry) or a list of N tensors; views with larger row / plane strides are fine.
+        Work queued on that stream afterwards sees the pictures; the library keeps their slots from being rewritten before the
+        export has read them."""
+        import torch
+        from .export import FORMATS, HvqExportDst, check_one_hip_runtime, destinations
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        geoms = [self._geom[s] for s in sids]
+        dsts = destinations(out, geoms, fmt)
+        check_one_hip_runtime()
+        dev = out.device if isinstance(out, torch.Tensor) else (out[0].device if n else torch.device("cuda"))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_d = (HvqExportDst * n)(*[HvqExportDst(p, r, pl) for p, r, pl in dsts])
+        check(lib().hvq_export_pictures(self._h, n, a_s, a_o, FORMATS[fmt], C.cast(a_d, C.c_void_p),
+                                           C.c_void_p(stream)))
 
     def rgb_bench(self, reps: int):
         """-> (gpu_ms, bytes_per_rep, pictures): batched display epilogue over the newest picture of every stream"""

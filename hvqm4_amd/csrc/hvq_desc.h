@@ -180,5 +180,16 @@ typedef struct HvqTileRef {
     uint32_t tile;                 /* tiles of the picture */
 } HvqTileRef;
 
+/* one picture of the display epilogue / export (hvq_yuv_rgb_kernel): source planes of a slot, destination and its layout.
+ * Output formats (HVQ_FMT_* of hvqm4_amd.h): 0 RGB24 interleaved rows of w*3 bytes, 1 RGB planar, 2 YUV 4:4:4 planar; planar
+ * formats put three planes of h rows `plane_pitch` apart.  dst, row_pitch and plane_pitch are multiples of 4. */
+typedef struct HvqRgbJob {
+    const uint8_t *y, *u, *v;
+    uint8_t *dst;
+    int64_t row_pitch, plane_pitch;    /* bytes */
+    int32_t w, h;
+    int32_t wshift, hshift;            /* chroma subsampling: (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 */
+} HvqRgbJob;
+
 
 #endif

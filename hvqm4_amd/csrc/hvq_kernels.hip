@@ -14,7 +14,7 @@
  *                      the tile is assembled in LDS and leaves as 16-byte row segments (every store instruction of a wave
  *                      writes four complete 256-byte runs, every output line reaches HBM once and whole)
  *   hvq_selfref_kernel P pictures with future-referencing macroblocks: the reference's raster-order walk
- *   hvq_yuv420_rgb_kernel, hvq_gather_kernel   display epilogue, bulk readback
+ *   hvq_yuv_rgb_kernel, hvq_gather_kernel      display epilogue and picture export, bulk readback
  *   - sample arithmetic is SIMD-within-register: v_lerp_u8 for the 2-tap and 4-tap half-sample filters, 16-bit packed math for
  *     the weighted-DC predictor, v_sad_u8 for block sums; the AOT products in the reference's own uint32 wrap arithmetic
  *     (v_mul_lo_u32); the reference's divTable / mcdivTable lookups are one v_rcp_f32 and a biased multiply (udiv_table, no fix-up);
@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "hvq_desc.h"
+#include "../../include/hvqm4_amd.h"
 
 typedef uint32_t u32;
 typedef int32_t i32;
@@ -1194,10 +1195,13 @@ extern "C" hipError_t hvq_launch_recon_inline(const HvqJob *jobs_dev, uint32_t n
 }
 
 /* ------------------------------------------------------------------------------------------------------
- * Display epilogue: YUV 4:2:0 -> RGB24 exactly as the reference player's dumpRGB
- * (h4m:897-926): single-precision, one rounding per operation (the intrinsics below are never contracted
- * into FMAs), clamp, truncate.  Pure streaming kernel: 1.5 B/px read, 3 B/px written; one lane = 4 samples
- * of a row = one dword of Y in, three dwords of RGB out (a wave stores 768 contiguous bytes).
+ * Display epilogue and picture export (hvq_export_pictures): YUV -> RGB exactly as the reference player's dumpRGB
+ * (h4m:897-926): single-precision, one rounding per operation (the intrinsics below are never contracted into FMAs), clamp,
+ * truncate.  Output sample (i, j) reads chroma sample [(i >> hshift) * (w >> wshift) + (j >> wshift)] of each chroma plane: at 4:2:0
+ * that is dumpRGB's i/2 * w/2 + j/2.  The reference converts 4:2:0 only ("HACK: assumes 4:2:0"); 4:2:2 and 4:4:4 take the same
+ * rule with their shifts, the natural extension of dumpRGB.  YUV444P copies Y and replicates U and V by the same index rule.
+ * Pure streaming kernel: one lane = 4 samples of a row = one dword of Y in, three dwords out (a wave stores 768 contiguous bytes
+ * of RGB24); planar formats store one dword per plane.
  */
 /* clamp to [0, 255] and truncate (h4m:897-900), packed into byte `sel` of `acc`: v_floor_f32 + v_cvt_pk_u8_f32.  The pack
  * instruction saturates at both ends but rounds to nearest, the floor in front makes it exact (tools/ubench/cvt_probe.hip on
@@ -1208,113 +1212,192 @@ __device__ __forceinline__ u32 rgb_put(float f, u32 sel, u32 acc)
     return __builtin_amdgcn_cvt_pk_u8_f32(__builtin_floorf(f), sel, acc);
 }
 
-struct HvqRgbJob { const uint8_t *yuv; uint8_t *rgb; int w, h; };
-
-/* four samples: one dword of Y, two bytes each of U and V -> three dwords of RGB */
-__device__ __forceinline__ void rgb4(u32 y4, u32 u2, u32 v2, u32 out[3])
+/* four samples: one dword of Y and their chroma (the low two bytes of `uc` / `vc` at WS = 1, four bytes at WS = 0) -> three dwords,
+ * interleaved RGB (byte 3k + c) or one dword per plane (byte k of dword c) */
+template <int WS, bool PLANAR>
+__device__ __forceinline__ void rgb4(u32 y4, u32 uc, u32 vc, u32 out[3])
 {
     out[0] = out[1] = out[2] = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float Y = (float)((y4 >> (8 * k)) & 0xFFu);
-        const float U = __fsub_rn((float)((u2 >> (8 * (k >> 1))) & 0xFFu), 128.f);
-        const float V = __fsub_rn((float)((v2 >> (8 * (k >> 1))) & 0xFFu), 128.f);
+        const float U = __fsub_rn((float)((uc >> (8 * (k >> WS))) & 0xFFu), 128.f);
+        const float V = __fsub_rn((float)((vc >> (8 * (k >> WS))) & 0xFFu), 128.f);
         const float px[3] = { __fadd_rn(Y, __fmul_rn(1.402f, V)),
                               __fsub_rn(__fsub_rn(Y, __fmul_rn(0.34414f, U)), __fmul_rn(0.71414f, V)),
                               __fadd_rn(Y, __fmul_rn(1.772f, U)) };
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const int byte = 3 * k + c;
-            out[byte >> 2] = rgb_put(px[c], (u32)(byte & 3), out[byte >> 2]);
+            if (PLANAR) out[c] = rgb_put(px[c], (u32)k, out[c]);
+            else {
+                const int byte = 3 * k + c;
+                out[byte >> 2] = rgb_put(px[c], (u32)(byte & 3), out[byte >> 2]);
+            }
         }
     }
 }
 
-/* WIDE: one lane = 16 samples of TWO rows that share their chroma (two 16-byte Y loads, one 8-byte U and V load; the chroma
- * products are computed once for the 2x2 samples they serve).  A lane's 48 output bytes per row are contiguous, but stored
- * straight from the lane every store instruction would write 16 of every 48 bytes -- three partial passes over each line.
- * So a wave turns its 3 KB of a row around in LDS: chunk c (16 bytes) of the wave's output belongs to lane c / 3, and store
- * instruction j of lane l writes chunk l + 64 j -- every instruction a contiguous kilobyte (r03: 0.53 -> see DESIGN.md 8 f3).
- * Needs width % 16 == 0 and an even height (4:2:0 has both); otherwise 4 samples of one row per lane. */
-template <bool WIDE>
-__global__ __launch_bounds__(256)
-void hvq_yuv420_rgb_kernel(const HvqRgbJob *__restrict__ jobs)
+/* YUV444P: the chroma of four samples at full resolution (WS = 1: bytes c0 c0 c1 c1) */
+template <int WS>
+__device__ __forceinline__ u32 chroma4(u32 c)
 {
-    const HvqRgbJob J = jobs[blockIdx.y];                    /* one picture per grid row */
+    return WS ? (c & 0xFFu) * 0x0101u | ((c >> 8) & 0xFFu) * 0x01010000u : c;
+}
+
+/* destinations are dword-aligned only (pitched exports): vectors of dwords at 4-byte alignment */
+typedef u32 u32x4d __attribute__((ext_vector_type(4))) __attribute__((aligned(4)));
+typedef u32 u32x4y __attribute__((ext_vector_type(4)));
+
+/* one picture.  WIDE: one lane = 16 samples of TWO rows (two 16-byte Y loads; per chroma row 8 bytes of U and V at WS = 1, 16 at
+ * WS = 0; at HS = 1 the rows share their chroma and its products are computed once for the 2x2 samples they serve).  RGB24: a lane's
+ * 48 output bytes per row are contiguous, but stored straight from the lane every store instruction would write 16 of every 48
+ * bytes -- three partial passes over each line.  So a wave turns its 3 KB of a row around in LDS (`s_w`): chunk c (16 bytes) of the
+ * wave's output belongs to lane c / 3, and store instruction j of lane l writes chunk l + 64 j -- every instruction a contiguous
+ * kilobyte (r03: 0.53 -> see DESIGN.md 8 f3).  Planar formats need no turn-around: a lane's 16 bytes per plane and row are
+ * contiguous.  Needs width % 16 == 0 (heights are even); otherwise 4 samples of one row per lane. */
+template <int FMT, bool WIDE, int WS, int HS>
+__device__ __forceinline__ void yuv_rgb_job(const HvqRgbJob &J, int idx, u32 *s_w)
+{
     /* global-address-space pointers like the rest of the file: generic ones become flat_* accesses, which count on the LDS
      * counter too -- and this kernel turns its output around in LDS */
-    const GLB uint8_t *__restrict__ yuv = (const GLB uint8_t *)J.yuv;
-    GLB uint8_t *__restrict__ rgb = (GLB uint8_t *)J.rgb;
-    const int w = J.w, h = J.h;
+    const GLB uint8_t *__restrict__ py = (const GLB uint8_t *)J.y;
+    const GLB uint8_t *__restrict__ pu = (const GLB uint8_t *)J.u;
+    const GLB uint8_t *__restrict__ pv = (const GLB uint8_t *)J.v;
+    GLB uint8_t *__restrict__ dst = (GLB uint8_t *)J.dst;
+    const int w = J.w, h = J.h, cw = w >> WS;
+    const size_t rp = (size_t)J.row_pitch, pp = (size_t)J.plane_pitch;
     constexpr int S = WIDE ? 16 : 4;
     const int qw = w / S;                                    /* lanes per row */
     const int total = qw * (WIDE ? h / 2 : h);
-    const int idx = blockIdx.x * 256 + threadIdx.x;
     if (WIDE) {
-        __shared__ __attribute__((aligned(16))) u32 s_t[4][64 * 12];     /* per wave: 64 lanes x 48 bytes of one row */
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int lane = threadIdx.x & 63;
         const int wave_idx0 = idx - lane;
         if (wave_idx0 >= total) return;                      /* whole wave beyond the picture (uniform) */
         const bool live = idx < total;
+        if (FMT != HVQ_FMT_RGB24 && !live) return;           /* only the LDS turn-around needs every lane of the wave */
         const int li = live ? idx : total - 1;
         const int yr = li / qw, xq = li - yr * qw;
         const int y = 2 * yr;
-        const GLB uint8_t *yp = yuv + (size_t)y * w + S * xq;
-        const GLB uint8_t *up = yuv + (size_t)w * h + (size_t)(y >> 1) * (w >> 1) + (S / 2) * xq;
-        const GLB uint8_t *vp = up + (size_t)(w >> 1) * (h >> 1);
-        typedef u32 u32x4y __attribute__((ext_vector_type(4)));
+        const GLB uint8_t *yp = py + (size_t)y * w + S * xq;
         const u32x4y ya = *(const GLB u32x4y *)yp, yb = *(const GLB u32x4y *)(yp + w);
-        const u32x2 u8 = *(const GLB u32x2 *)up, v8 = *(const GLB u32x2 *)vp;
-        const u32 us[4] = { u8.x & 0xFFFFu, u8.x >> 16, u8.y & 0xFFFFu, u8.y >> 16 };
-        const u32 vs[4] = { v8.x & 0xFFFFu, v8.x >> 16, v8.y & 0xFFFFu, v8.y >> 16 };
-        /* where the three chunks this lane STORES live: chunk c = lane + 64 j belongs to lane c / 3 of the wave */
-        size_t chunk_off[3];
-        bool chunk_live[3];
-        const float rqw = 1.0f / (float)qw;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int c = lane + 64 * j, owner = (c * 21846) >> 16, part = c - 3 * owner;       /* c / 3 for c < 192 */
-            const int oi = wave_idx0 + owner;
-            int oyr = (int)((float)oi * rqw);                                                   /* estimate within +-1, fixed up */
-            int oxq = oi - oyr * qw;
-            if (oxq < 0) { oxq += qw; --oyr; } else if (oxq >= qw) { oxq -= qw; ++oyr; }
-            chunk_live[j] = oi < total;
-            chunk_off[j] = ((size_t)(2 * oyr) * w + (size_t)S * oxq) * 3 + 16 * (size_t)part;
-        }
-        typedef u32 u32x4t __attribute__((ext_vector_type(4)));
+        u32 us[2][4], vs[2][4];                              /* chroma of the four dwords of Y, per row */
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
-            const u32x4y y16 = row ? yb : ya;
-            const u32 ys[4] = { y16.x, y16.y, y16.z, y16.w };
-            u32 o[12];
+            if (HS && row) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) rgb4(ys[q], us[q], vs[q], o + 3 * q);     /* the chroma terms are common subexpressions of the two rows */
-            u32x4t *mine = (u32x4t *)&s_t[wave][lane * 12];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { const u32x4t v = { o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3] }; mine[q] = v; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (int q = 0; q < 4; ++q) { us[1][q] = us[0][q]; vs[1][q] = vs[0][q]; }
+                continue;
+            }
+            const size_t co = (size_t)((y + row) >> HS) * cw + (size_t)(S >> WS) * xq;
+            if (WS) {
+                const u32x2 u8 = *(const GLB u32x2 *)(pu + co), v8 = *(const GLB u32x2 *)(pv + co);
+                us[row][0] = u8.x & 0xFFFFu; us[row][1] = u8.x >> 16; us[row][2] = u8.y & 0xFFFFu; us[row][3] = u8.y >> 16;
+                vs[row][0] = v8.x & 0xFFFFu; vs[row][1] = v8.x >> 16; vs[row][2] = v8.y & 0xFFFFu; vs[row][3] = v8.y >> 16;
+            } else {
+                const u32x4y u16 = *(const GLB u32x4y *)(pu + co), v16 = *(const GLB u32x4y *)(pv + co);
+                us[row][0] = u16.x; us[row][1] = u16.y; us[row][2] = u16.z; us[row][3] = u16.w;
+                vs[row][0] = v16.x; vs[row][1] = v16.y; vs[row][2] = v16.z; vs[row][3] = v16.w;
+            }
+        }
+        if (FMT == HVQ_FMT_RGB24) {
+            /* where the three chunks this lane STORES live: chunk c = lane + 64 j belongs to lane c / 3 of the wave */
+            size_t chunk_off[3];
+            bool chunk_live[3];
+            const float rqw = 1.0f / (float)qw;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const u32x4t v = *(const u32x4t *)&s_t[wave][(lane + 64 * j) * 4];
-                if (chunk_live[j]) *(GLB u32x4t *)(rgb + chunk_off[j] + (size_t)row * 3 * w) = v;
+                const int c = lane + 64 * j, owner = (c * 21846) >> 16, part = c - 3 * owner;       /* c / 3 for c < 192 */
+                const int oi = wave_idx0 + owner;
+                int oyr = (int)((float)oi * rqw);                                                   /* estimate within +-1, fixed up */
+                int oxq = oi - oyr * qw;
+                if (oxq < 0) { oxq += qw; --oyr; } else if (oxq >= qw) { oxq -= qw; ++oyr; }
+                chunk_live[j] = oi < total;
+                chunk_off[j] = (size_t)(2 * oyr) * rp + (size_t)(3 * S) * oxq + 16 * (size_t)part;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();                 /* the second row overwrites the buffer */
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int row = 0; row < 2; ++row) {
+                const u32x4y y16 = row ? yb : ya;
+                const u32 ys[4] = { y16.x, y16.y, y16.z, y16.w };
+                u32 o[12];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) rgb4<WS, false>(ys[q], us[row][q], vs[row][q], o + 3 * q);   /* at HS = 1 the chroma terms are common subexpressions of the two rows */
+                u32x4y *mine = (u32x4y *)&s_w[lane * 12];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) { const u32x4y v = { o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3] }; mine[q] = v; }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const u32x4y v = *(const u32x4y *)&s_w[(lane + 64 * j) * 4];
+                    if (chunk_live[j]) *(GLB u32x4d *)(dst + chunk_off[j] + (size_t)row * rp) = v;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();             /* the second row overwrites the buffer */
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        } else {
+#pragma unroll
+            for (int row = 0; row < 2; ++row) {
+                const u32x4y y16 = row ? yb : ya;
+                const u32 ys[4] = { y16.x, y16.y, y16.z, y16.w };
+                u32 o[3][4];                                 /* [plane][dword] */
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (FMT == HVQ_FMT_RGBP) {
+                        u32 t[3];
+                        rgb4<WS, true>(ys[q], us[row][q], vs[row][q], t);
+                        o[0][q] = t[0]; o[1][q] = t[1]; o[2][q] = t[2];
+                    } else {
+                        o[0][q] = ys[q]; o[1][q] = chroma4<WS>(us[row][q]); o[2][q] = chroma4<WS>(vs[row][q]);
+                    }
+                }
+                GLB uint8_t *d = dst + (size_t)(y + row) * rp + (size_t)S * xq;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const u32x4y v = { o[c][0], o[c][1], o[c][2], o[c][3] };
+                    *(GLB u32x4d *)(d + (size_t)c * pp) = v;
+                }
+            }
         }
     } else {
         if (idx >= total) return;
         const int yr = idx / qw, xq = idx - yr * qw;
-        const GLB uint8_t *yp = yuv + (size_t)yr * w + S * xq;
-        const GLB uint8_t *up = yuv + (size_t)w * h + (size_t)(yr >> 1) * (w >> 1) + (S / 2) * xq;
-        const GLB uint8_t *vp = up + (size_t)(w >> 1) * (h >> 1);
-        GLB u32 *dst = (GLB u32 *)(rgb + ((size_t)yr * w + S * xq) * 3);
+        const u32 y4 = *(const GLB u32 *)(py + (size_t)yr * w + S * xq);
+        const size_t co = (size_t)(yr >> HS) * cw + (size_t)(S >> WS) * xq;
+        const u32 uc = WS ? (u32)*(const GLB uint16_t *)(pu + co) : *(const GLB u32 *)(pu + co);
+        const u32 vc = WS ? (u32)*(const GLB uint16_t *)(pv + co) : *(const GLB u32 *)(pv + co);
         u32 o[3];
-        rgb4(*(const GLB u32 *)yp, *(const GLB uint16_t *)up, *(const GLB uint16_t *)vp, o);
-        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+        if (FMT == HVQ_FMT_RGB24) {
+            rgb4<WS, false>(y4, uc, vc, o);
+            GLB u32 *d = (GLB u32 *)(dst + (size_t)yr * rp + (size_t)(3 * S) * xq);
+            d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
+        } else {
+            if (FMT == HVQ_FMT_RGBP) rgb4<WS, true>(y4, uc, vc, o);
+            else { o[0] = y4; o[1] = chroma4<WS>(uc); o[2] = chroma4<WS>(vc); }
+            GLB uint8_t *d = dst + (size_t)yr * rp + (size_t)S * xq;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) *(GLB u32 *)(d + (size_t)c * pp) = o[c];
+        }
     }
+}
+
+/* one picture per grid row; its sampling picks the body (uniform per workgroup), so one launch takes pictures of any geometry and
+ * sampling */
+template <int FMT, bool WIDE>
+__global__ __launch_bounds__(256)
+void hvq_yuv_rgb_kernel(const HvqRgbJob *__restrict__ jobs)
+{
+    const HvqRgbJob J = jobs[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    u32 *s_w = nullptr;
+    if constexpr (FMT == HVQ_FMT_RGB24 && WIDE) {
+        __shared__ __attribute__((aligned(16))) u32 s_t[4][64 * 12];     /* per wave: 64 lanes x 48 bytes of one row */
+        s_w = s_t[threadIdx.x >> 6];
+    }
+    if (J.hshift) yuv_rgb_job<FMT, WIDE, 1, 1>(J, idx, s_w);
+    else if (J.wshift) yuv_rgb_job<FMT, WIDE, 1, 0>(J, idx, s_w);
+    else yuv_rgb_job<FMT, WIDE, 0, 0>(J, idx, s_w);
 }
 
 /* bulk readback (hvq_read_pictures): `n` resident pictures gathered into one contiguous staging buffer, so that the copy to the
@@ -1367,16 +1450,22 @@ extern "C" hipError_t hvq_launch_gather(const uint64_t *src_dev, uint8_t *dst_de
     return hipGetLastError();
 }
 
-/* jobs_dev: array of {yuv, rgb, w, h} in device memory; max_lanes = max over jobs of (w/4)*h; wide = every
- * width is a multiple of 16 */
-extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, hipStream_t stream)
+template <int FMT>
+static void launch_rgb(const HvqRgbJob *jobs_dev, int njobs, int max_lanes, bool wide, hipStream_t stream)
+{
+    if (wide) hvq_yuv_rgb_kernel<FMT, true><<<dim3((max_lanes / 8 + 255) / 256, njobs), dim3(256), 0, stream>>>(jobs_dev);
+    else hvq_yuv_rgb_kernel<FMT, false><<<dim3((max_lanes + 255) / 256, njobs), dim3(256), 0, stream>>>(jobs_dev);
+}
+
+/* jobs_dev: HvqRgbJob[njobs] in device memory; max_lanes = max over jobs of (w/4)*h; wide = every width is a multiple of 16;
+ * format: HVQ_FMT_* */
+extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, int format, hipStream_t stream)
 {
     if (njobs <= 0) return hipSuccess;
-    if (wide)
-        hipLaunchKernelGGL(hvq_yuv420_rgb_kernel<true>, dim3((max_lanes / 8 + 255) / 256, njobs), dim3(256), 0, stream,
-                           (const HvqRgbJob *)jobs_dev);
-    else
-        hipLaunchKernelGGL(hvq_yuv420_rgb_kernel<false>, dim3((max_lanes + 255) / 256, njobs), dim3(256), 0, stream,
-                           (const HvqRgbJob *)jobs_dev);
+    const HvqRgbJob *j = (const HvqRgbJob *)jobs_dev;
+    if (format == HVQ_FMT_RGB24) launch_rgb<HVQ_FMT_RGB24>(j, njobs, max_lanes, wide != 0, stream);
+    else if (format == HVQ_FMT_RGBP) launch_rgb<HVQ_FMT_RGBP>(j, njobs, max_lanes, wide != 0, stream);
+    else if (format == HVQ_FMT_YUV444P) launch_rgb<HVQ_FMT_YUV444P>(j, njobs, max_lanes, wide != 0, stream);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }

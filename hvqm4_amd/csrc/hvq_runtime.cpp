@@ -61,8 +61,7 @@ extern "C" hipError_t hvq_launch_table_div(uint32_t *out_dev, hipStream_t stream
 #ifdef HVQ_STAMPS
 extern "C" void hvq_set_stamps(unsigned long long *p);
 #endif
-extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, hipStream_t stream);
-struct RgbJob { const uint8_t *yuv; uint8_t *rgb; int w, h; };
+extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, int format, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -123,6 +122,7 @@ struct Stream {
     bool open = false;
     HvqParser *parser = nullptr;
     int w = 0, h = 0;
+    int wshift = 0, hshift = 0;              /* chroma subsampling (hvq_parser_create) */
     uint32_t pic_bytes = 0, slot_bytes = 0;
     uint8_t *dev = nullptr;                  /* (nslots + 1) slots; the last one stays zero */
     std::vector<Slot> slots;
@@ -254,8 +254,13 @@ struct HvqContext {
     std::atomic<uint64_t> copy_ns{ 0 };
     uint8_t *rgb_dev = nullptr;        /* scratch of the display epilogue */
     size_t rgb_cap = 0;
-    RgbJob *rgb_jobs_dev = nullptr;
+    HvqRgbJob *rgb_jobs_dev = nullptr;
     size_t rgb_jobs_cap = 0;
+    /* hvq_export_pictures: job tables in a ring, each reused once the export that read it has finished (its event); the newest
+     * export's event orders the next export and every later slot writer (export_fence) */
+    struct ExportTab { uint8_t *host = nullptr; HvqRgbJob *dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } ex[4];
+    int ex_next = 0, ex_last = -1;     /* table of the next export; of the newest one (-1: none yet) */
+    bool ex_unfenced = false;          /* an export was queued since c->stream last waited for one */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
      * reads one set while the parse of batch k + 1 fills the other.  ps_live is the set the code below means by PS(c). */
@@ -293,6 +298,25 @@ struct HvqContext {
 
 static inline HvqContext::ParseSet &PS(HvqContext *c) { return c->ps[c->ps_live]; }
 static inline const HvqContext::ParseSet &PS(const HvqContext *c) { return c->ps[c->ps_live]; }
+
+/* Every enqueue that writes picture slots (the reconstruction and self-reference launches of a flush or replay) comes behind the
+ * exports that may still read them (hvq_export_pictures, on the caller's streams): the launch stream waits for the newest export,
+ * which waited for every export before it.  Ahead of queues_fork, so that both launch queues inherit the wait; nothing when no
+ * export was queued since the last wait. */
+static int export_fence(HvqContext *c)
+{
+    if (!c->ex_unfenced) return HVQ_OK;
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ex[c->ex_last].ev, 0));
+    c->ex_unfenced = false;
+    return HVQ_OK;
+}
+
+/* host side of the same before a ring is freed (hvq_stream_close, hvq_context_destroy) */
+static int export_drain(HvqContext *c)
+{
+    if (c->ex_last >= 0) HIPCHK(hipEventSynchronize(c->ex[c->ex_last].ev));
+    return HVQ_OK;
+}
 
 static int arena_reserve(HvqContext *c, size_t need)
 {
@@ -479,6 +503,7 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     (void)flush_end(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    (void)export_drain(c);
     for (auto &s : c->streams) {
         if (s.parser) hvq_parser_destroy(s.parser);
         if (s.dev) (void)hipFree(s.dev);
@@ -519,6 +544,11 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     if (c->rb_tab_host) (void)hipHostFree(c->rb_tab_host);
     if (c->rgb_dev) (void)hipFree(c->rgb_dev);
     if (c->rgb_jobs_dev) (void)hipFree(c->rgb_jobs_dev);
+    for (auto &t : c->ex) {
+        if (t.host) (void)hipHostFree(t.host);
+        if (t.dev) (void)hipFree(t.dev);
+        if (t.ev) (void)hipEventDestroy(t.ev);
+    }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -548,6 +578,7 @@ HVQ_EXPORT int hvq_stream_open(HvqContext *c, int width, int height, int h_samp,
                         width, height, h_samp, v_samp);
     Stream s;
     s.open = true; s.parser = p; s.w = width; s.h = height;
+    s.wshift = h_samp == 2; s.hshift = v_samp == 2;
     s.pic_bytes = hvq_parser_pic_bytes(p);
     s.slot_bytes = (uint32_t)align_up((size_t)s.pic_bytes + 64, 256);
     s.slots.resize((size_t)nslots);
@@ -582,6 +613,7 @@ HVQ_EXPORT int hvq_stream_close(HvqContext *c, int sid)
     { int rcj = copy_join(c); if (rcj) return rcj; }
     { int rc = flush_end(c); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(c->stream));
+    { int rc = export_drain(c); if (rc) return rc; }
     Stream &s = c->streams[sid];
     hvq_parser_destroy(s.parser); s.parser = nullptr;
     HIPCHK(hipFree(s.dev)); s.dev = nullptr;
@@ -1841,7 +1873,8 @@ static int flush_end(HvqContext *c)
     /* 3. one launch per level */
     {
         bool two = false;
-        int rc = queues_fork(c, &two);
+        int rc = export_fence(c);
+        if (!rc) rc = queues_fork(c, &two);
         if (!rc) rc = run_launches(c);
         /* joined also when a launch failed: whatever the other queues hold is ordered in front of everything the main stream gets next */
         { const int rcj = queues_join(c, two); if (!rc) rc = rcj; }
@@ -1895,6 +1928,7 @@ HVQ_EXPORT int hvq_sync(HvqContext *c)
 static int replay_passes(HvqContext *c, bool joined, int reps)
 {
     bool two = false;
+    { int rc = export_fence(c); if (rc) return rc; }
     if (!joined) { int rc = queues_fork(c, &two); if (rc) return rc; }
     for (int r = 0; r < reps; ++r) {
         if (joined) { int rc = queues_fork(c, &two); if (rc) return rc; }
@@ -2001,8 +2035,15 @@ HVQ_EXPORT int hvq_read_picture(HvqContext *c, int sid, int ordinal, void *dst, 
     return HVQ_OK;
 }
 
-/* convert `n` resident pictures in one launch into consecutive regions of the RGB scratch; optional timing */
-static int rgb_run(HvqContext *c, RgbJob *jobs, int n, int reps, float *gpu_ms)
+/* a 4:2:0 picture (Y|U|V at `yuv`) to dense RGB24: the jobs of the display epilogue */
+static HvqRgbJob rgb420_job(const uint8_t *yuv, int w, int h)
+{
+    const size_t n = (size_t)w * h;
+    return HvqRgbJob{ yuv, yuv + n, yuv + n + n / 4, nullptr, (int64_t)w * 3, 0, w, h, 1, 1 };
+}
+
+/* convert `n` 4:2:0 pictures in one launch into consecutive regions of the RGB scratch; optional timing */
+static int rgb_run(HvqContext *c, HvqRgbJob *jobs, int n, int reps, float *gpu_ms)
 {
     size_t need = 0;
     int max_lanes = 0, wide = 1;
@@ -2015,15 +2056,15 @@ static int rgb_run(HvqContext *c, RgbJob *jobs, int n, int reps, float *gpu_ms)
     }
     if ((size_t)n > c->rgb_jobs_cap) {
         if (c->rgb_jobs_dev) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->rgb_jobs_dev)); }
-        HIPCHK(hipMalloc((void **)&c->rgb_jobs_dev, (size_t)n * sizeof(RgbJob)));
+        HIPCHK(hipMalloc((void **)&c->rgb_jobs_dev, (size_t)n * sizeof(HvqRgbJob)));
         c->rgb_jobs_cap = (size_t)n;
     }
     size_t off = 0;
-    for (int i = 0; i < n; ++i) { jobs[i].rgb = c->rgb_dev + off; off += (size_t)jobs[i].w * jobs[i].h * 3; }
-    HIPCHK(hipMemcpyAsync(c->rgb_jobs_dev, jobs, (size_t)n * sizeof(RgbJob), hipMemcpyHostToDevice, c->stream));
+    for (int i = 0; i < n; ++i) { jobs[i].dst = c->rgb_dev + off; off += (size_t)jobs[i].w * jobs[i].h * 3; }
+    HIPCHK(hipMemcpyAsync(c->rgb_jobs_dev, jobs, (size_t)n * sizeof(HvqRgbJob), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (gpu_ms) HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int r = 0; r < reps; ++r) HIPCHK(hvq_launch_rgb(c->rgb_jobs_dev, n, max_lanes, wide, c->stream));
+    for (int r = 0; r < reps; ++r) HIPCHK(hvq_launch_rgb(c->rgb_jobs_dev, n, max_lanes, wide, HVQ_FMT_RGB24, c->stream));
     if (gpu_ms) {
         HIPCHK(hipEventRecord(c->ev1, c->stream));
         HIPCHK(hipEventSynchronize(c->ev1));
@@ -2046,7 +2087,7 @@ HVQ_EXPORT int hvq_read_picture_rgb(HvqContext *c, int sid, int ordinal, void *d
     int slot = s.pic_slot[(size_t)ordinal];
     if (slot < 0) return fail(HVQ_E_STATE, "picture %d is no longer resident (slot reused)", ordinal);
     HIPCHK(hipSetDevice(c->device));
-    RgbJob job{ s.slot_ptr(slot), nullptr, s.w, s.h };
+    HvqRgbJob job = rgb420_job(s.slot_ptr(slot), s.w, s.h);
     int rc = rgb_run(c, &job, 1, 1, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(dst, c->rgb_dev, need, hipMemcpyDeviceToHost, c->stream));
@@ -2067,7 +2108,7 @@ HVQ_EXPORT int hvq_convert_yuv420_rgb(HvqContext *c, const void *yuv, int width,
     hipError_t e = hipMemcpyAsync(d, yuv, nyuv, hipMemcpyHostToDevice, c->stream);
     int rc = HVQ_OK;
     if (e != hipSuccess) rc = fail(HVQ_E_HIP, "upload: %s", hipGetErrorString(e));
-    RgbJob job{ d, nullptr, width, height };
+    HvqRgbJob job = rgb420_job(d, width, height);
     if (!rc) rc = rgb_run(c, &job, 1, 1, nullptr);
     if (!rc) {
         e = hipMemcpyAsync(rgb, c->rgb_dev, nrgb, hipMemcpyDeviceToHost, c->stream);
@@ -2174,18 +2215,81 @@ HVQ_EXPORT int hvq_picture_device_ptr(HvqContext *c, int sid, int ordinal, const
     return rc;
 }
 
+HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, int format,
+                                   const HvqExportDst *dst, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    if (format != HVQ_FMT_RGB24 && format != HVQ_FMT_RGBP && format != HVQ_FMT_YUV444P) return fail(HVQ_E_ARG, "bad format %d", format);
+    if (!n) return HVQ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    /* as hvq_read_pictures: the batch in flight is ended only when a requested picture belongs to it */
+    bool need_end = false;
+    for (int i = 0; i < n && !need_end; ++i)
+        if (streams[i] >= 0 && streams[i] < (int)c->streams.size() && ordinals[i] >= c->streams[(size_t)streams[i]].inflight_from) need_end = true;
+    if (need_end) { int rc = flush_end(c); if (rc) return rc; }
+    std::vector<HvqRgbJob> jobs((size_t)n);
+    int max_lanes = 0, wide = 1;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!src) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const int64_t dense = format == HVQ_FMT_RGB24 ? (int64_t)s.w * 3 : (int64_t)s.w;
+        const int64_t rp = dst[i].row_pitch ? dst[i].row_pitch : dense;
+        const int64_t pp = format == HVQ_FMT_RGB24 ? 0 : dst[i].plane_pitch ? dst[i].plane_pitch : rp * s.h;
+        if (!dst[i].ptr) return fail(HVQ_E_ARG, "null destination %d", i);
+        if (rp < dense || rp > ((int64_t)1 << 40) || (format != HVQ_FMT_RGB24 && dst[i].plane_pitch > ((int64_t)1 << 48)))
+            return fail(HVQ_E_ARG, "destination %d: row pitch %lld outside [%lld, 2^40] or plane pitch above 2^48", i, (long long)rp, (long long)dense);
+        if (format != HVQ_FMT_RGB24 && pp < rp * s.h)
+            return fail(HVQ_E_ARG, "destination %d: plane pitch %lld below row pitch x height %lld (planes overlap)", i, (long long)pp, (long long)(rp * s.h));
+        if (((uintptr_t)dst[i].ptr | (uint64_t)rp | (uint64_t)pp) & 3u)
+            return fail(HVQ_E_ARG, "destination %d: pointer, row pitch and plane pitch must be multiples of 4", i);
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        jobs[(size_t)i] = HvqRgbJob{ src, src + ny, src + ny + nc, (uint8_t *)dst[i].ptr, rp, pp, s.w, s.h, s.wshift, s.hshift };
+        if (s.w % 16) wide = 0;
+        max_lanes = std::max(max_lanes, (s.w >> 2) * s.h);
+    }
+    /* everything is checked: from here on the call enqueues.  The job table the export K calls ago used is free once that export
+     * has run (a host wait only when K exports are still queued) */
+    HvqContext::ExportTab &T = c->ex[c->ex_next];
+    if (!T.ev) HIPCHK(hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
+    else if (T.used) HIPCHK(hipEventSynchronize(T.ev));
+    const size_t bytes = (size_t)n * sizeof(HvqRgbJob);       /* a multiple of 16: hvq_launch_upload copies whole 16-byte units */
+    if (bytes > T.cap) {
+        if (T.host) { HIPCHK(hipHostFree(T.host)); T.host = nullptr; }
+        if (T.dev) { HIPCHK(hipFree(T.dev)); T.dev = nullptr; }
+        T.cap = 0;
+        const size_t ncap = align_up(bytes * 2, 4096);
+        HIPCHK(hipHostMalloc((void **)&T.host, ncap, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&T.dev, ncap));
+        T.cap = ncap;
+    }
+    memcpy(T.host, jobs.data(), bytes);
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(hipStreamWaitEvent(st, c->ev_read, 0));                          /* every flushed picture is reconstructed */
+    if (c->ex_last >= 0) HIPCHK(hipStreamWaitEvent(st, c->ex[c->ex_last].ev, 0));   /* chained: the newest export covers all */
+    HIPCHK(hvq_launch_upload(T.host, T.dev, bytes, st));
+    HIPCHK(hvq_launch_rgb(T.dev, n, max_lanes, wide, format, st));
+    HIPCHK(hipEventRecord(T.ev, st));
+    T.used = true;
+    c->ex_last = c->ex_next;
+    c->ex_next = (c->ex_next + 1) % (int)(sizeof c->ex / sizeof c->ex[0]);
+    c->ex_unfenced = true;
+    return HVQ_OK;
+}
+
 HVQ_EXPORT int hvq_rgb_bench(HvqContext *c, int reps, float *gpu_ms, uint64_t *bytes_per_rep, uint32_t *pictures)
 {
     if (!c || reps < 1) return fail(HVQ_E_ARG, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
     { int rc = flush_end(c); if (rc) return rc; }
-    std::vector<RgbJob> jobs;
+    std::vector<HvqRgbJob> jobs;
     uint64_t bytes = 0;
     for (auto &s : c->streams) {
         if (!s.open || s.npics == 0 || s.pic_bytes != (uint32_t)(s.w * s.h * 3 / 2)) continue;
         int slot = s.pic_slot[(size_t)s.npics - 1];
         if (slot < 0) continue;
-        jobs.push_back(RgbJob{ s.slot_ptr(slot), nullptr, s.w, s.h });
+        jobs.push_back(rgb420_job(s.slot_ptr(slot), s.w, s.h));
         bytes += (uint64_t)s.w * s.h * 9 / 2;              /* 1.5 B/px read + 3 B/px written */
     }
     if (jobs.empty()) return fail(HVQ_E_STATE, "no resident 4:2:0 picture");

@@ -163,7 +163,7 @@ int  hvq_read_pictures(HvqContext *ctx, int n, const int *streams, const int *or
 void *hvq_pinned_alloc(size_t bytes);
 void hvq_pinned_free(void *p);
 /* Device address of a resident picture for consumers on the GPU (valid until the stream's ring reuses the slot, `nslots`
- * pictures later at the earliest); order the consumer after hvq_sync(). */
+ * pictures later at the earliest); order the consumer after hvq_sync().  hvq_export_pictures does the ordering itself. */
 int  hvq_picture_device_ptr(HvqContext *ctx, int stream, int ordinal, const void **ptr);
 
 /* Display epilogue of the reference player (dumpRGB, h4m:897-926) on the GPU: converts a resident 4:2:0
@@ -174,6 +174,32 @@ int  hvq_convert_yuv420_rgb(HvqContext *ctx, const void *yuv, int width, int hei
 /* Measurement helper: converts the newest resident picture of every open 4:2:0 stream in ONE launch, `reps`
  * times, timed with HIP events on the launch stream.  bytes_per_rep = 1.5 B/px read + 3 B/px written. */
 int  hvq_rgb_bench(HvqContext *ctx, int reps, float *gpu_ms, uint64_t *bytes_per_rep, uint32_t *pictures);
+
+/* Export of resident pictures into the caller's device memory: `n` pictures, of any streams, sizes and samplings, converted in ONE
+ * kernel launch on the caller's HIP stream, without a host synchronisation.
+ *   Formats: HVQ_FMT_RGB24 -- interleaved (HWC), h rows of w*3 bytes; HVQ_FMT_RGBP -- planar (CHW), three planes of h rows of w
+ *   bytes; HVQ_FMT_YUV444P -- planar (CHW), Y copied, U and V replicated to full resolution.  RGB is the display epilogue's dumpRGB
+ *   arithmetic (h4m:897-926, bit-exact); output sample (i, j) reads chroma sample [(i >> hshift) * (w >> wshift) + (j >> wshift)]
+ *   -- dumpRGB itself at 4:2:0 (the reference converts only 4:2:0), the same rule with the stream's shifts at 4:2:2 and 4:4:4.
+ *   dst[i]: rows `row_pitch` bytes apart, planes `plane_pitch` bytes apart (planar formats; ignored for RGB24); 0 = dense (w*3 or
+ *   w; row_pitch * h).  ptr, row_pitch and plane_pitch must be multiples of 4, pitches at least the dense ones, planes must not
+ *   overlap (plane_pitch >= row_pitch * h).  The destination must hold what these describe: the library cannot check its size.
+ *   Pictures are looked up as hvq_read_pictures does: HVQ_E_STATE for a picture queued but not flushed, one whose slot was reused
+ *   or that was dropped; HVQ_E_ARG for a bad stream, ordinal, format, null pointer, pitch or alignment.  Every argument is checked
+ *   before anything is enqueued: a refused call enqueues nothing and leaves every destination untouched.  The batch in flight is
+ *   ended only when a requested picture belongs to it, so `hvq_flush_next; export(batch k)` keeps overlapping.
+ *   Ordering: `hip_stream` (NULL = the null stream) first waits for the reconstruction of every flushed picture and for the
+ *   previous export (of whatever stream), then converts; the call returns at once.  Work the caller queues on `hip_stream` after
+ *   the call sees the pictures; other streams order themselves after it with an event of their own.
+ *   Slot safety: later work of the library that writes picture slots (flushes, hvq_replay, hvq_replay_stage) waits on the GPU for
+ *   the exports before it; hvq_stream_close and hvq_context_destroy wait for them on the host before freeing a ring.  A picture
+ *   is therefore safe to export until its slot is handed to a later picture, and the export reads it whole. */
+#define HVQ_FMT_RGB24    0
+#define HVQ_FMT_RGBP     1
+#define HVQ_FMT_YUV444P  2
+typedef struct HvqExportDst { void *ptr; int64_t row_pitch, plane_pitch; } HvqExportDst;     /* pitches in bytes; 0 = dense */
+int  hvq_export_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, int format,
+                         const HvqExportDst *dst, void *hip_stream);
 
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
