@@ -59,6 +59,10 @@
 #define HVQ_F_CAPPED      0x0040u   /* an overflow-symbol loop (h4m:654-677: the reference sums for as long as the stream says) ended
                                        on this back end's cap instead of on the stream: the value differs from the reference's --
                                        the picture is refused, never decoded differently */
+#define HVQ_F_MALFORMED   0x0080u   /* P/B picture the reference decodes outside its own rules: a luma kind symbol above 15 (it lands in
+                                       the macroblock's type / proc bits, h4m:1701, 1927) or a type run that opens at value 3 (h4m:1591,
+                                       1606, 1950-1951); in any picture, a prefix tree with more inner nodes than 256 leaf bytes allow
+                                       (the device parser's GP_ST_BADTREE) -- refused, never decoded differently */
 
 typedef struct HvqPicHeader {
     uint32_t magic;

@@ -478,6 +478,7 @@ __device__ static void gfd_exp_write(GPic *g, int x0, int x1, int tid)
         if (gfd_ex(x, 1, 0) + gfd_ex(x, 1, 1) + gfd_ex(x, 1, 2) + gfd_ex(x, 1, 3) < e.N) { g->retry = 1; continue; }       /* not enough tokens */
         gfd_exp_range(&e, wave, &lo, &hi);
         for (int w = 0; w < wave; ++w) { z += gfd_ex(x, 0, w); at += gfd_ex(x, 1, w); }
+        uint32_t kinds = 0;
         for (uint32_t jb = lo; jb < hi && at < e.N; jb += 64) {
             uint32_t tok; bool live, bad;
             const uint32_t len = gfd_exp_step(&e, jb, hi, lane, &z, &tok, &live, &bad);
@@ -485,9 +486,11 @@ __device__ static void gfd_exp_write(GPic *g, int x0, int x1, int tid)
             at += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (live && mine < e.N) {                      /* tokens are consumed until the blocks are covered */
                 if (bad) g->retry = 1;                       /* not enough run lengths */
-                else if (tok) gf_exp_put(g, x, mine, tok);
+                else if (tok) { kinds |= tok; gf_exp_put(g, x, mine, tok); }
             }
         }
+        /* a P/B luma kind above 15: HVQ_F_MALFORMED in this thread's word of gfd_tags_assign (gf_exp_write) */
+        if (x == 0 && g->is_pb && (kinds & 0xFFu) > 15u) g->part[GP_PART2 + tid] |= HVQ_F_MALFORMED;
     }
 }
 

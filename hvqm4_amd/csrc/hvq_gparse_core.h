@@ -1025,6 +1025,7 @@ GP_FN void gp_mbtypes(GPic *g, const GCode *codes)
     const int cap = GP_UOVF_CAP((uint32_t)g->mw * (uint32_t)g->mh);
     uint32_t value = 0, count = 0, fl = 0;
     if (b.live) { value = gb_take(&b, 2); count = (uint32_t)gsym_uovf(c, &b, cap, &fl); }
+    if (value == 3u) fl |= HVQ_F_MALFORMED;       /* a first value of 3: refused like hvq_parse.c pb_tags does */
     const uint32_t n = (uint32_t)g->mw * (uint32_t)g->mh;
     uint32_t m = 0, nr = 0;
     while (m < n) {
@@ -1194,10 +1195,12 @@ GP_FN void gp_pbkinds(GPic *g, const GCode *codes, int which)
     g->nks[which] = n;
 }
 
-/* parallel, after the kinds chains: OR the recorded kinds into the type bytes */
+/* parallel, after the kinds chains: OR the recorded kinds into the type bytes.  A luma kind above 15 (it lands in the type / proc
+ * bits) raises HVQ_F_MALFORMED in this thread's word of gp_tags_assign, which the layout folds into the header */
 GP_FN void gp_kinds_scatter(GPic *g, int tid, int nthr)
 {
     if (g->status) return;
+    uint32_t bad = 0;
     for (int which = 0; which < 2; ++which) {
         const GPlane *q = &g->pl[which];
         const GP_G uint32_t *ks = g->clist + q->blk_first;
@@ -1208,10 +1211,11 @@ GP_FN void gp_kinds_scatter(GPic *g, int tid, int nthr)
             const uint32_t m = g->cmb[r], tag = g->mbtag[m];
             const int my = (int)(m / (uint32_t)g->mw), mx = (int)(m - (uint32_t)my * (uint32_t)g->mw);
             const int by = my * q->by_per + gp_dy((int)j), bx = mx * q->bx_per + gp_dx((int)j);
-            if (which == 0) gp_map_ent(g, 0, by, bx)[1] = (uint8_t)(tag | k);
+            if (which == 0) { bad |= k; gp_map_ent(g, 0, by, bx)[1] = (uint8_t)(tag | k); }
             else { gp_map_ent(g, 1, by, bx)[1] = (uint8_t)(tag | (k & 0xFu)); gp_map_ent(g, 2, by, bx)[1] = (uint8_t)(tag | ((k >> 4) & 0xFu)); }
         }
     }
+    if (bad > 15u) g->part[GP_PART2 + tid] |= HVQ_F_MALFORMED;
 }
 
 /* chain: DC values of the intra macroblocks of plane i (h4m:1742-1776): cumulative within a run of consecutive intra

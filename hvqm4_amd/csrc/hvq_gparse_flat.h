@@ -420,7 +420,7 @@ GP_FN void gf_exp_write(GPic *g, int x0, int x1, int tid, int nthr)           /*
         uint32_t lo, hi;
         if (!gf_exp(g, x, &e)) continue;
         if (g->tot[GF_I_LEN(x) - 16] < e.N) { g->retry = 1; continue; }       /* not enough tokens */
-        uint32_t z = g->part[GF_P(GF_I_ZERO(x), tid)], at = g->part[GF_P(GF_I_LEN(x), tid)];
+        uint32_t z = g->part[GF_P(GF_I_ZERO(x), tid)], at = g->part[GF_P(GF_I_LEN(x), tid)], bad = 0;
         gp_chunk8(e.ntok, tid, nthr, 8, &lo, &hi);
         for (uint32_t j0 = lo; j0 < hi && at < e.N; j0 += 8) {
             uint32_t t[8];
@@ -430,9 +430,11 @@ GP_FN void gf_exp_write(GPic *g, int x0, int x1, int tid, int nthr)           /*
                 if (t[k] == 0) {
                     if (z >= e.nrun) { g->retry = 1; at = e.N; break; }       /* not enough run lengths */
                     at += 1u + (uint32_t)e.run[z++];
-                } else { gf_exp_put(g, x, at, t[k]); ++at; }
+                } else { bad |= t[k]; gf_exp_put(g, x, at, t[k]); ++at; }
             }
         }
+        /* a P/B luma kind above 15: HVQ_F_MALFORMED in this thread's word of gp_tags_assign (gp_kinds_scatter) */
+        if (x == 0 && g->is_pb && (bad & 0xFFu) > 15u) g->part[GP_PART2 + tid] |= HVQ_F_MALFORMED;
     }
 }
 

@@ -73,7 +73,7 @@ static inline uint32_t br_take(BitRd *b, int n)      /* n <= 25 */
 
 /* ------------------------------------------------------------------ prefix trees (h4m:385-394, 604-651) */
 typedef struct {
-    int root, next;
+    int root, next, bad;          /* bad: more inner nodes than 256 leaf bytes allow */
     int16_t kid[2][512];
     int32_t leaf[256];
     uint32_t lut[1 << LUT_BITS];        /* [31:26] bits consumed; bit 25 set: [15:0] the leaf's VALUE (one look-up per symbol);
@@ -92,7 +92,7 @@ static int code_node(Code *c, BitRd *b, int is_signed, int scale, int depth)
     }
     /* more than 255 inner nodes cannot come from 256 leaf bytes: malformed; stop before node 511 can become its
      * own child (an endless walk in sym) */
-    if (c->next >= 511) return 0;
+    if (c->next >= 511) { c->bad = 1; return 0; }   /* the device parser's GP_ST_BADTREE: refused (HVQ_F_MALFORMED) */
     int id = c->next++;
     c->kid[0][id] = (int16_t)code_node(c, b, is_signed, scale, depth + 1);
     c->kid[1][id] = (int16_t)code_node(c, b, is_signed, scale, depth + 1);
@@ -114,6 +114,7 @@ static void code_lut(Code *c, int node, int depth, uint32_t prefix)
 static void code_read(Code *c, BitRd *carrier, int is_signed, int scale)     /* h4m:632-642 */
 {
     c->next = 0x100;
+    c->bad = 0;
     c->root = carrier->live ? code_node(c, carrier, is_signed, scale, 0) : 0;
     code_lut(c, c->root, 0, 0);
 }
@@ -210,7 +211,8 @@ struct HvqParser {
     uint32_t n_bases[3], n_resid[3];
     uint8_t *mb_tag;             /* P/B: per macroblock type << 5 | proc << 4 (0: intra), from the type / proc runs */
     int is_P;
-    uint8_t res[4];              /* P/B: residual bits of the vectors, h0 h1 v0 v1 (h4m:2023-2026) */
+    uint8_t res[8];              /* P/B: residual bits of the vectors, h0 h1 v0 v1 0 0 0 0 (h4m:2023-2026): indexed by reference 0..2 like
+                                    the device parser's (a type-3 macroblock, refused, still reads res[4]) */
     uint32_t tflags[8];          /* flags raised by the tasks of a phase (one word each: tasks run side by side) */
     uint32_t capped;             /* a task met an overflow run that does not end: the other tasks stop decoding values too */
     struct ParsePool *tp;        /* hvq_parser_set_threads: workers that run a phase's tasks beside the calling thread */
@@ -630,7 +632,7 @@ static void payload_phase_a(HvqParser *p, uint8_t *blob, int task)
 
 /* ---- pass 2, step b: the payload dwords of a range of macroblock rows of one plane, from the fixed-length section (byte addressed,
  * h4m:545-548) and the arrays of step a.  Where the range starts in each of them follows from row_cum. */
-typedef struct { const uint8_t *fx, *end; const int16_t *bt; const int32_t *sc; } AsmCur;
+typedef struct { const uint8_t *fx, *end; const int16_t *bt, *bt_end; const int32_t *sc, *sc_end; uint32_t clamped; } AsmCur;
 
 static AsmCur asm_cursor(const HvqParser *p, int i, int mrow)
 {
@@ -642,6 +644,11 @@ static AsmCur asm_cursor(const HvqParser *p, int i, int mrow)
     c.fx = (p->fx[i] <= p->end && at <= (size_t)(p->end - p->fx[i])) ? p->fx[i] + at : p->end;     /* beyond the picture: zeros, like the serial walk */
     c.bt = p->bt_sym[i] + rc->bases;
     c.sc = p->sc_val[i] + 2u * (size_t)rc->resid;
+    /* the ends of what step a decoded: layout and assembly count the same blocks, so these are never reached -- if they were, the
+     * rest reads zeros and the picture is flagged instead of reading past the arrays */
+    c.bt_end = p->bt_sym[i] + p->n_bases[i];
+    c.sc_end = p->sc_val[i] + 2u * (size_t)p->n_resid[i];
+    c.clamped = 0;
     return c;
 }
 
@@ -656,6 +663,18 @@ static inline void asm_literal(AsmCur *c, uint32_t *dst)                        
 static inline void asm_bases(AsmCur *c, uint32_t n, uint32_t *dst)
 {
     uint32_t run = 0;
+    if ((size_t)(c->bt_end - c->bt) < n) {                  /* never on a picture whose layout and assembly agree */
+        const uint32_t have = (uint32_t)(c->bt_end - c->bt);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint8_t *s = c->fx;
+            uint32_t word = 0;
+            if (s + 2 <= c->end) { word = be16(s); c->fx = s + 2; } else c->fx = c->end;
+            if (k < have) run += (uint32_t)(int32_t)*c->bt++;
+            dst[k] = HVQ_BASIS(word, (run + ((word >> 13) & 3u)) & 0x3FFFFu);
+        }
+        c->clamped = HVQ_F_CLAMPED;
+        return;
+    }
     for (uint32_t k = 0; k < n; ++k) {
         const uint8_t *s = c->fx;
         uint32_t word = 0;
@@ -666,7 +685,7 @@ static inline void asm_bases(AsmCur *c, uint32_t n, uint32_t *dst)
 }
 
 /* I picture: plane raster order == reference consumption order (h4m:2011-2015) */
-static void ipic_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1)
+static void ipic_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1, uint32_t *flags)
 {
     const PPlane *q = &p->pl[i];
     uint32_t *pool = (uint32_t *)(blob + p->fixed_bytes);
@@ -685,6 +704,7 @@ static void ipic_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1)
             else asm_bases(&c, k, dst);
         }
     }
+    *flags |= c.clamped;
 }
 
 /* the macroblock-row range of assembly task `task`: luma in four parts, the chroma planes whole */
@@ -699,7 +719,7 @@ static void ipic_phase2b(HvqParser *p, uint8_t *blob, int task)
 {
     int i, r0, r1;
     asm_range(p, task, &i, &r0, &r1);
-    ipic_assemble(p, blob, i, r0, r1);
+    ipic_assemble(p, blob, i, r0, r1, task_flags(p, task));
 }
 
 /* a prefix tree read from the head of its carrier section (h4m:632-642); the section's cursor goes through a copy on this thread's
@@ -774,6 +794,7 @@ static int parse_ipic(HvqParser *p, const uint8_t *pic, uint8_t *blob, size_t ca
     p->dc_hi = (int32_t)((uint32_t)0x7F << (p->dc_shift & 31));
     p->dc_lo = (int32_t)((uint32_t)-0x80 << (p->dc_shift & 31));
     run_phase(p, ipic_phase0, blob, 3);
+    if (p->c_bn.bad | p->c_run.bad | p->c_dc.bad | p->c_bt.bad) p->flags |= HVQ_F_MALFORMED;
     TMARK(0, 0);
     run_phase(p, ipic_phase1, blob, 5);
     TMARK(0, 1);
@@ -790,6 +811,7 @@ static int parse_ipic(HvqParser *p, const uint8_t *pic, uint8_t *blob, size_t ca
     TMARK(0, 2);
     run_phase(p, payload_phase_a, blob, 4);                       /* an I picture has no MC-residual scalars: tasks 0, 2, 3 decode, 1 is empty */
     run_phase(p, ipic_phase2b, blob, 6);
+    for (int t = 0; t < 6; ++t) p->flags |= p->tflags[t];          /* behind the header, like a P/B picture's pass 2 */
     TMARK(0, 3);
     if (p->flags & HVQ_F_HAS_NEST)
         pack_nest(blob + ((HvqPicHeader *)blob)->nest_off, p->nest);
@@ -811,6 +833,9 @@ static void pb_tags(HvqParser *p, int is_P)
     RunLen type = { 0, 0 }, proc = { 0, 0 };
     if (p->mproc.live) { proc.value = br_take(&p->mproc, 1); proc.count = (uint32_t)sym_uovf(&p->c_mcb, &p->mproc, cap, &p->flags); }
     if (p->mtype.live) { type.value = br_take(&p->mtype, 2); type.count = (uint32_t)sym_uovf(&p->c_mcb, &p->mtype, cap, &p->flags); }
+    /* a first type value of 3 (the transitions never lead to it): its macroblocks read a residual-bit count the stream does not set
+     * (h4m:1950-1951, past mc_residual_bits_v) and a run that leaves it indexes past mcbtypetrans (h4m:1591, 1606) -- refused */
+    if (type.value == 3) p->flags |= HVQ_F_MALFORMED;
     const int nmb = (p->w / 8) * (p->h / 8);
     uint8_t *tags = p->mb_tag;
     for (int m = 0; m < nmb; ++m) {
@@ -829,7 +854,7 @@ static void pb_tags(HvqParser *p, int is_P)
 
 /* block kinds of one plane group (g = 0 luma, 1 chroma: U in the low nibble, V in the high one) over all macroblocks (h4m:1670-1740):
  * every block's type byte = its macroblock's tag | its kind; plain-MC macroblocks (proc 1) carry no kinds */
-static void pb_kinds_group(HvqParser *p, uint8_t *blob, int g)
+static void pb_kinds_group(HvqParser *p, uint8_t *blob, int g, uint32_t *flags)
 {
     const int mw = p->w / 8, mh = p->h / 8;
     const uint8_t *tags = p->mb_tag;
@@ -846,6 +871,7 @@ static void pb_kinds_group(HvqParser *p, uint8_t *blob, int g)
                     uint8_t *t = &e[2 * Y->moff[j] + 1];
                     if (rl) { *t = tag; --rl; continue; }
                     int16_t k = (int16_t)sym(&p->c_bn, &bn);
+                    if ((uint16_t)k > 15u) *flags |= HVQ_F_MALFORMED;   /* lands in the type / proc bits (h4m:1701, 1927): refused */
                     if (k) *t = (uint8_t)(tag | k);
                     else { *t = tag; rl = (uint32_t)sym(&p->c_run, &bnr); }
                 }
@@ -932,7 +958,7 @@ static void pb_vectors(HvqParser *p, uint8_t *blob, uint32_t *flags)
 }
 
 /* pass 2 for a range of macroblock rows of one plane (h4m:1919-1967, 1789-1827, 1862-1910): macroblock raster order */
-static void pb_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1)
+static void pb_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1, uint32_t *flags)
 {
     const int mw = p->w / 8;
     const uint8_t *tags = p->mb_tag;
@@ -965,11 +991,14 @@ static void pb_assemble(HvqParser *p, uint8_t *blob, int i, int r0, int r1)
                 uint32_t *dst = pool + p->blk_off[i][b];
                 if (k == 6) { asm_literal(&c, dst); continue; }
                 asm_bases(&c, k - 1, dst + 2);
-                const int32_t s1 = *c.sc++, s2 = *c.sc++;           /* h4m:1405-1406 */
+                int32_t s1 = 0, s2 = 0;                             /* h4m:1405-1406 */
+                if (c.sc_end - c.sc >= 2) { s1 = c.sc[0]; s2 = c.sc[1]; c.sc += 2; }
+                else c.clamped = HVQ_F_CLAMPED;                     /* never on a picture whose layout and assembly agree */
                 dst[0] = (uint32_t)(s1 >> sh_dc) << sh_unk;
                 dst[1] = (uint32_t)(s2 >> sh_dc);
             }
         }
+    *flags |= c.clamped;
 }
 
 static void pb_tags(HvqParser *p, int is_P);
@@ -989,10 +1018,10 @@ static void pb_phase0(HvqParser *p, uint8_t *blob, int task)
 static void pb_phase1(HvqParser *p, uint8_t *blob, int task)
 {
     switch (task) {
-    case 0: pb_kinds_group(p, blob, 0); break;
+    case 0: pb_kinds_group(p, blob, 0, task_flags(p, task)); break;
     case 1: pb_dc_plane(p, blob, 0, task_flags(p, task)); break;
     case 2: pb_vectors(p, blob, task_flags(p, task)); break;
-    case 3: pb_kinds_group(p, blob, 1); break;
+    case 3: pb_kinds_group(p, blob, 1, task_flags(p, task)); break;
     default: pb_dc_plane(p, blob, task - 3, task_flags(p, task)); break;
     }
 }
@@ -1000,7 +1029,7 @@ static void pb_phase2b(HvqParser *p, uint8_t *blob, int task)
 {
     int i, r0, r1;
     asm_range(p, task, &i, &r0, &r1);
-    pb_assemble(p, blob, i, r0, r1);
+    pb_assemble(p, blob, i, r0, r1, task_flags(p, task));
 }
 
 static int parse_pbpic(HvqParser *p, int is_P, const uint8_t *pic, uint8_t *blob, size_t cap, size_t *blob_len)
@@ -1008,6 +1037,7 @@ static int parse_pbpic(HvqParser *p, int is_P, const uint8_t *pic, uint8_t *blob
     p->dc_shift = pic[0];
     p->unk_shift = pic[1];
     p->res[0] = pic[2]; p->res[1] = pic[4]; p->res[2] = pic[3]; p->res[3] = pic[5];     /* h0 h1 v0 v1 (h4m:2023-2026) */
+    p->res[4] = p->res[5] = p->res[6] = p->res[7] = 0;
     const uint8_t *tab = pic + 8, *data = pic + 8 + 0x44;
     common_sections(p, data, tab);
     p->mvh = section_bits(p, data, tab, 13);
@@ -1018,6 +1048,7 @@ static int parse_pbpic(HvqParser *p, int is_P, const uint8_t *pic, uint8_t *blob
     p->dc_lo = (int32_t)((uint32_t)-0x80 << (p->dc_shift & 31));
     p->is_P = is_P;
     run_phase(p, pb_phase0, blob, 4);
+    if (p->c_bn.bad | p->c_run.bad | p->c_dc.bad | p->c_bt.bad | p->c_mv.bad | p->c_mcb.bad) p->flags |= HVQ_F_MALFORMED;
     TMARK(1, 0);
     run_phase(p, pb_phase1, blob, 6);
     TMARK(1, 1);
@@ -1033,6 +1064,12 @@ static int parse_pbpic(HvqParser *p, int is_P, const uint8_t *pic, uint8_t *blob
     /* the header carries the flags known HERE, like the device parser's (the blobs are compared byte for byte); what pass 2 still
      * raises (a clamped vector target cannot come later, an endless overflow run in a block's scalars can) is in hvq_parser_last_flags */
     fill_header(p, blob, is_P ? HVQ_PIC_P : HVQ_PIC_B, pool_dwords, (uint32_t)total);
+    if (p->flags & HVQ_F_MALFORMED) {                               /* refused: the pool is never read, and its layout (from the stored
+                                                                       type bytes) does not describe what the stream holds */
+        p->flags |= late;
+        *blob_len = total;
+        return HVQ_OK;
+    }
     if (payload_arrays(p)) return HVQ_E_OVERFLOW;
     TMARK(1, 2);
     run_phase(p, payload_phase_a, blob, 6);

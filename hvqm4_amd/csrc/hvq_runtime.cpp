@@ -100,10 +100,14 @@ static uint32_t picture_workgroups(const uint32_t tile_first[4])
 /* Pictures this back end refuses instead of decoding them differently from the reference:
  *   HVQ_F_CAPPED    an overflow-symbol run ended on the parsers' cap: the reference would have gone on summing (h4m:654-677);
  *   HVQ_F_CLAMPED   a nest origin or vector target outside what the reference's arithmetic keeps in bounds was clamped
- *                   (malformed input); HVQM4_AMD_ALLOW_CLAMPED=1 decodes such pictures with the clamped values. */
+ *                   (malformed input); HVQM4_AMD_ALLOW_CLAMPED=1 decodes such pictures with the clamped values;
+ *   HVQ_F_MALFORMED a P/B luma kind symbol above 15, or a type run that opens at value 3: the reference decodes those outside its own
+ *                   rules (stored type / proc bits, a table index and a residual-bit count the stream does not set); or a prefix tree
+ *                   with more inner nodes than 256 leaf bytes allow (the GPU parser rejects it too).  Not opt-in. */
 static const char *unsupported_reason(uint32_t flags)
 {
     if (flags & HVQ_F_CAPPED) return "an overflow-symbol run is longer than this back end follows (the reference sums for as long as the stream says, h4m:654-677)";
+    if (flags & HVQ_F_MALFORMED) return "malformed picture: a P/B luma kind symbol above 15 (h4m:1701, 1927), a macroblock type run that opens at value 3 (h4m:1591, 1606, 1950-1951) or a prefix tree with more inner nodes than 256 leaves allow";
     if (flags & HVQ_F_CLAMPED) {
         const char *e = getenv("HVQM4_AMD_ALLOW_CLAMPED");
         if (!(e && atoi(e) > 0)) return "malformed picture: a nest origin or vector target had to be clamped (HVQM4_AMD_ALLOW_CLAMPED=1 decodes it anyway)";

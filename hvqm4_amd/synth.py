@@ -10,7 +10,9 @@ group (wiring at h4m:977-999), serialises it pre-order into the carrier stream
 
 Legality (keeps the *reference* in-bounds, Appendix C): every motion-compensated
 read and every MC-nest window address stays inside the Y|U|V picture buffer; no
-future-referencing macroblocks in P pictures; P/B kind symbols <= 15.
+future-referencing macroblocks in P pictures; P/B kind symbols <= 15.  Two opt-in knobs break the last rule
+and its twin on purpose (pb_big_kinds, mb_type3): pictures the decoders must refuse (HVQ_F_MALFORMED), written so that
+the reference and the oracle still consume them in step and in bounds.
 """
 from __future__ import annotations
 
@@ -84,6 +86,17 @@ class SynthConfig:
     predi_big: float = 0.0            # P/B pictures: probability that a scalar of an MC-residual block (h4m:1405-1406) lies beyond 16 bits
     p_proc1: float = -1.0             # >= 0: probability of a run of plain-MC (proc = 1) macroblocks, overriding the preset's
     p_zero: float = -1.0              # >= 0: probability of a zero-kind run start, overriding the preset's (small: nearly every block coded)
+    pb_big_kinds: float = 0.0         # P/B pictures: probability that a coded luma kind symbol is written as 16..255 (its low nibble
+                                      # is the kind; the reference ORs the rest into the type byte, h4m:1701).  In a macroblock's first
+                                      # luma block only bits that keep its type are set (the reference takes type / proc from that
+                                      # byte, h4m:1927): bit 7, the type's own bits, or bit 4 -- plain MC, no payload (inter) or a
+                                      # proc bit that intra decoding ignores; the other blocks take any high bits
+    mb_type3: float = 0.0             # P/B pictures: probability that the type run opens with value 3 (one or more macroblocks),
+                                      # then, unless it covers the picture, leaves it through transition bit 0 or 1 into one run to
+                                      # the end: value 1 resp. 2 as the oracle reads it (step[bit][3 % 3]).  Residual bits h0 = h1 and
+                                      # v0 = v1, so the reference's value 2 after bit 0 (mcbtypetrans[0][3]) consumes the same bits;
+                                      # after bit 1 it reads past its table (h4m:1606) and leaves the stream's step
+    mb_type3_exits: Sequence[int] = (0, 1)   # mb_type3: the transition bits a type-3 run may leave through
 
 
 class _Ops:
@@ -459,6 +472,9 @@ class _Gen:
         dc_shift = int(rng.choice(cfg.dc_shifts))
         unk_shift = int(rng.choice(cfg.unk_shifts))
         res = [int(rng.choice(cfg.mv_res_bits)) for _ in range(4)]    # h0 v0 h1 v1
+        type3 = bool(cfg.mb_type3) and rng.random() < cfg.mb_type3
+        if type3:
+            res[2], res[3] = res[0], res[1]
         pic.header = struct.pack(">BBBBBBBB", dc_shift, unk_shift, res[0], res[1], res[2], res[3], 0, 0)
         mw, mh = self.w // 8, self.h // 8
         nm = mw * mh
@@ -470,6 +486,16 @@ class _Gen:
         runs: List[Tuple[int, int]] = []
         i = 0
         cur = int(rng.choice(allowed, p=wts))
+        if type3:
+            n3 = int(rng.integers(1, nm + 1))
+            runs.append((3, n3))
+            types[:n3] = 3
+            i = n3
+            cur = 1 + int(rng.choice(cfg.mb_type3_exits))   # exit bit 0 -> 1, bit 1 -> 2 (oracle, step[bit][0])
+            if i < nm:
+                runs.append((cur, nm - i))
+                types[i:] = cur
+                i = nm
         while i < nm:
             n = self._run(self.mcb_run_mean, lo=1, hi=100000)
             runs.append((cur, n))
@@ -482,7 +508,7 @@ class _Gen:
         for lf in _uovf_leaves(runs[0][1]):
             ot.leaf(lf)
         for (pv, _), (cv, cn) in zip(runs[:-1], runs[1:]):
-            ot.raw(0 if cv == (pv + 1) % 3 else 1, 1)
+            ot.raw(0 if cv == (pv + 1) % 3 else 1, 1)      # from 3: (3 + 1) % 3 = 1 <- bit 0, 2 <- bit 1
             for lf in _uovf_leaves(cn):
                 ot.leaf(lf)
         # 2. proc runs over non-intra MCBs
@@ -519,7 +545,7 @@ class _Gen:
             if ref != prev_ref:
                 prev_ref = ref
                 mvh = mvv = 0
-            rh, rv = res[2 * ref], res[2 * ref + 1]
+            rh, rv = (res[2 * ref], res[2 * ref + 1]) if ref < 2 else (res[1], 0)   # type 3: v0, then a zero byte (h4m:502-506)
             Rh, Rv = 1 << (rh + 5), 1 << (rv + 5)
             x, y = (m % mw) * 8, (m // mw) * 8
             want_predi = procs[m] == 0
@@ -555,6 +581,7 @@ class _Gen:
         # 4. pass 1 (spread_PB_descMap): DC + kinds ; pass 2 payload ops are queued per MCB
         rleY = rleC = 0
         nc = self.cblk
+        plain = np.zeros(nm, dtype=bool)                      # first luma byte turned proc 1: no payload (pb_big_kinds)
         kinds = np.zeros((nm, 4 + 2 * nc), dtype=np.int32)   # Y TL,BL,BR,TR, then U blocks, then V blocks
         for m in range(nm):
             t = int(types[m])
@@ -582,7 +609,17 @@ class _Gen:
                 else:
                     k = self._intra_kind(False) if intra else self._inter_kind(pok)
                     k &= 0xF
-                    pic.ops[BN0].leaf(k)
+                    sym = k
+                    if cfg.pb_big_kinds and rng.random() < cfg.pb_big_kinds:
+                        if j:
+                            hi = int(rng.choice([0x10, 0x20, 0x30, 0x40, 0x50, 0x60, 0x70, 0x80, 0xF0]))
+                        elif intra:
+                            hi = int(rng.choice([0x80, 0x10, 0x90]))
+                        else:
+                            hi = int(rng.choice([0x80, t << 5, 0x10, (t << 5) | 0x90]))
+                            plain[m] = bool(hi & 0x10)
+                        sym = k | hi
+                    pic.ops[BN0].leaf(sym)
                     kinds[m, j] = k
             for jc in range(nc):
                 if rleC:
@@ -609,7 +646,7 @@ class _Gen:
                     if k == 0 or k == 8:
                         continue
                     self._emit_payload_intra(pic, p, k)
-            elif procs[m] == 0:
+            elif procs[m] == 0 and not plain[m]:
                 for j in range(4 + 2 * nc):
                     p = 0 if j < 4 else 1 if j < 4 + nc else 2
                     k = int(kinds[m, j])
