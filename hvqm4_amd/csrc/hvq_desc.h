@@ -55,7 +55,11 @@
                                        reconstructed data-parallel into a side buffer, then hvq_selfref_kernel walks the
                                        macroblocks in raster order like the reference does */
 #define HVQ_F_BIG_AOT     0x0010u   /* some block has more than 15 bases (I-luma type byte > 15) */
-#define HVQ_F_CLAMPED     0x0020u   /* malformed input: a value was clamped to keep the device in bounds */
+#define HVQ_F_CLAMPED     0x0020u   /* malformed input the reference reads foreign memory on: a nest origin whose window leaves the block map or a
+                                       vector target beyond 16 bits (clamped), a motion-compensated block or a sample of a used window basis
+                                       outside [0, pic_bytes) of the referenced picture, anything read from a section of size 0 or a section
+                                       whose size lies outside the picture (hvq_refuse.h) -- refused unless HVQM4_AMD_ALLOW_CLAMPED=1, under
+                                       which the kernels pin every address into the slot and the picture is invented */
 #define HVQ_F_CAPPED      0x0040u   /* an overflow-symbol loop (h4m:654-677: the reference sums for as long as the stream says) ended
                                        on this back end's cap instead of on the stream: the value differs from the reference's --
                                        the picture is refused, never decoded differently */

@@ -487,6 +487,7 @@ __device__ static void gfd_exp_write(GPic *g, int x0, int x1, int tid)
             if (live && mine < e.N) {                      /* tokens are consumed until the blocks are covered */
                 if (bad) g->retry = 1;                       /* not enough run lengths */
                 else if (tok) { kinds |= tok; gf_exp_put(g, x, mine, tok); }
+                else if (x >= 2) g->part[GP_RLEW(x - 2)] = 1u;    /* an I picture's DC loop reads a run length (hvq_refuse.h) */
             }
         }
         /* a P/B luma kind above 15: HVQ_F_MALFORMED in this thread's word of gfd_tags_assign (gf_exp_write) */
@@ -1098,6 +1099,8 @@ void hvq_parse_kernel_t(const HvqParseJob *__restrict__ jobs, HvqParseResult *__
             GP_STAMP(6);
             gfd_emit_merge(&g, tid);
             __syncthreads();
+            gp_reads_check(&g, tid, GPW);
+            __syncthreads();
         }
         GP_STAMP(7);
         if (tid == 0) {
@@ -1177,6 +1180,8 @@ void hvq_parse_kernel_t(const HvqParseJob *__restrict__ jobs, HvqParseResult *__
     __syncthreads();
     GP_STAMP(6);
     gp_emit_merge(&g, tid, GPW);
+    __syncthreads();
+    gp_reads_check(&g, tid, GPW);
     __syncthreads();
     GP_STAMP(7);
     if (tid == 0) {

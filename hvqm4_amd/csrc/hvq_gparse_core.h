@@ -43,6 +43,8 @@
 #define GP_G
 #endif
 
+#include "hvq_refuse.h"      /* after GP_G: its walk reads the blob through global-address-space pointers */
+
 /* Chains and the serial steps run WAVE-UNIFORM on the device: every lane of the wave executes the same chain with the
  * same values, so the compiler keeps cursors, reservoirs and counters in scalar registers and runs the bit-level
  * logic on the scalar unit (one scalar branch instead of an exec-mask dance per `if`).  Stores to HBM are issued by all
@@ -376,6 +378,7 @@ typedef struct {
     int32_t dc_lo, dc_hi;
     uint8_t res[8];              /* h0 h1 v0 v1 0 0 (h4m:2023-2026; indexed by reference 0..2 like hvq_parse.c) */
     uint32_t flags, status;
+    uint32_t dead;               /* bit i: section i of the offset table has size 0 */
     uint32_t max_items, max_pairs, pool_dwords, total;
     uint64_t fx_off[3];          /* byte offset of the fixed-length sections (basis words, literal blocks) */
     uint32_t nchain[3];          /* entries in clist per plane */
@@ -405,15 +408,20 @@ typedef struct {
  * k = 0-2 I-picture DC planes, 3-5 P/B intra DC planes, 6-8 MC-residual scalars, 9 type runs, 10 proc runs */
 #define GP_CAPW(k) (GP_MISC + 16 + (k))
 #define GP_NCAPW 11
+/* part[GP_RLEW(i)]: an I picture's DC loop of plane i read a run length (hvq_refuse.h); part[GP_READSW]: what gp_reads_check found */
+#define GP_RLEW(i) (GP_MISC + 16 + GP_NCAPW + (i))
+#define GP_READSW (GP_MISC + 15)
+#define GP_READS_DONE 0x40000000u          /* in part[GP_READSW]: gp_reads_check has walked the picture */
 
+/* bytes at or beyond the picture's length read as zero, byte by byte (like the bit readers) */
 GP_FN uint32_t gp_be32(const GPic *g, uint64_t off)
 {
-    if (off + 4 > g->len) return 0;
+    if (off >= g->len) return 0;
     const uint32_t i = (uint32_t)(off >> 2), sh = (uint32_t)(off & 3u) * 8u;
     const uint32_t w0 = __builtin_bswap32(g->d[i]);
-    if (!sh) return w0;
-    const uint32_t w1 = i + 1 < g->nd ? __builtin_bswap32(g->d[i + 1]) : 0u;
-    return (w0 << sh) | (w1 >> (32 - sh));
+    const uint32_t w1 = sh && i + 1 < g->nd ? __builtin_bswap32(g->d[i + 1]) : 0u;
+    const uint32_t v = sh ? (w0 << sh) | (w1 >> (32 - sh)) : w0;
+    return off + 4 > g->len ? v & (~0u << (8u * (uint32_t)(off + 4 - g->len))) : v;
 }
 
 GP_FN uint32_t gp_byte(const GPic *g, uint32_t off) { return (gp_be32(g, off & ~3u) >> (24 - 8 * (off & 3u))) & 0xFFu; }
@@ -496,14 +504,16 @@ GP_FN void gp_setup(GPic *g, const HvqParseJob *job)
     g->retry = 0; g->ncoded = 0; g->ntype0 = 0; g->ntrun = 0; g->nprun = 0; g->pend = 0; g->spins = 0;
     g->flags = 0; g->status = 0; g->max_items = 0; g->max_pairs = 0; g->pool_dwords = 0; g->total = 0;
     if (g->cap < g->fixed_bytes || g->len < 8 + 0x44 + 4) g->status |= GP_ST_BADARG;
-    for (int k = 0; k < GP_NCAPW; ++k) GP_ST(g->part[GP_CAPW(k)], 0u);
+    for (int k = 0; k < GP_NCAPW + 3; ++k) GP_ST(g->part[GP_CAPW(k)], 0u);
+    GP_ST(g->part[GP_READSW], 0u);
+    g->dead = 0;
 }
 
 /* sections (h4m:1061-1071, 1979-1993, 2030-2044): byte offset of the payload of section i, *live as in hvq_parse.c */
 GP_FN uint64_t gp_section(const GPic *g, uint32_t data_off, uint32_t tab_off, int i, int *live)
 {
     const uint64_t s = (uint64_t)data_off + gp_be32(g, tab_off + 4u * (uint32_t)i);
-    if (s + 4 > g->len) { *live = 0; return g->len; }
+    if (s + 4 > g->len) { *live = -1; return g->len; }             /* the size itself lies outside the picture */
     *live = gp_be32(g, s) != 0;
     return s + 4;
 }
@@ -513,7 +523,8 @@ GP_FN void gp_section_bits(GPic *g, GBits *b, uint32_t data_off, uint32_t tab_of
     int live;
     const uint64_t s = gp_section(g, data_off, tab_off, i, &live);
     g->sec_pay[i] = (uint32_t)s;
-    gb_init(b, g->d, g->nd, s, live, slot);
+    if (live <= 0) g->dead |= (1u << i) | (live < 0 ? HVQ_SEC_OUTSIDE : 0u);
+    gb_init(b, g->d, g->nd, s, live > 0, slot);
 }
 
 /* serial (thread 0): picture header fields and all section cursors */
@@ -540,7 +551,7 @@ GP_FN void gp_sections(GPic *g)
     for (int k = 0; k < 3; ++k) {
         gp_section_bits(g, &g->dc[k], data, tab, 4 + 3 * k, 4u + (uint32_t)k);
         gp_section_bits(g, &g->bt[k], data, tab, 5 + 3 * k, 7u + (uint32_t)k);
-        { int live; g->fx_off[k] = gp_section(g, data, tab, 6 + 3 * k, &live); g->sec_pay[6 + 3 * k] = (uint32_t)g->fx_off[k]; }
+        { int live; g->fx_off[k] = gp_section(g, data, tab, 6 + 3 * k, &live); g->sec_pay[6 + 3 * k] = (uint32_t)g->fx_off[k]; if (live <= 0) g->dead |= (1u << (6 + 3 * k)) | (live < 0 ? HVQ_SEC_OUTSIDE : 0u); }
     }
     if (g->is_pb) {
         gp_section_bits(g, &g->mvh, data, tab, 13, 10u);
@@ -656,7 +667,7 @@ GP_FN void gp_idc(GPic *g, const GCode *codes, int i, uint8_t *rowbuf)
     const GCode *c_dc = &codes[GC_DC], *c_run = &codes[GC_RUN];
     const int32_t lo = g->dc_lo, hi = g->dc_hi;
     for (int bx = 0; bx <= q->hb; ++bx) rowbuf[bx] = 0x7F;
-    uint32_t run = 0, fl = 0;
+    uint32_t run = 0, fl = 0, zr = 0;
     for (int by = 0; by < q->vb; ++by) {
         GP_G uint8_t *row = gp_map_ent(g, i, by, 0);
         uint8_t pred = by ? rowbuf[0] : 0x7F;
@@ -665,7 +676,7 @@ GP_FN void gp_idc(GPic *g, const GCode *codes, int i, uint8_t *rowbuf)
             if (run) --run;
             else {
                 delta = (uint32_t)gsym_sovf(c_dc, &dc, lo, hi, &fl);
-                if (delta == 0) run = (uint32_t)gsym(c_run, &rle);
+                if (delta == 0) { run = (uint32_t)gsym(c_run, &rle); zr = 1u; }
             }
             const uint8_t v = (uint8_t)(pred + delta);                  /* uint8 wrap: h4m:1145-1149 */
             GP_ST(row[2 * bx], v);
@@ -674,6 +685,7 @@ GP_FN void gp_idc(GPic *g, const GCode *codes, int i, uint8_t *rowbuf)
         }
     }
     GP_ST(g->part[GP_CAPW(i)], fl);
+    GP_ST(g->part[GP_RLEW(i)], zr);
 }
 
 /* parallel: nest from the luma DC values (h4m:1166-1239), nibble-packed as hvq_parse.c pack_nest */
@@ -966,12 +978,12 @@ GP_FN void gp_predi_params(GPic *g, const GCode *codes, int i)
 
 GP_FN uint32_t gp_be16(const GPic *g, uint64_t off)
 {
-    if (off + 2 > g->len) return 0;
+    if (off >= g->len) return 0;
     const uint32_t i = (uint32_t)(off >> 2), sh = (uint32_t)(off & 3u);
     const uint32_t w0 = __builtin_bswap32(g->d[i]);
-    if (sh < 3) return (w0 >> (16 - 8 * sh)) & 0xFFFFu;
-    const uint32_t w1 = i + 1 < g->nd ? __builtin_bswap32(g->d[i + 1]) : 0u;
-    return ((w0 & 0xFFu) << 8) | (w1 >> 24);
+    const uint32_t w1 = sh == 3 && i + 1 < g->nd ? __builtin_bswap32(g->d[i + 1]) : 0u;
+    const uint32_t v = sh < 3 ? (w0 >> (16 - 8 * sh)) & 0xFFFFu : ((w0 & 0xFFu) << 8) | (w1 >> 24);
+    return off + 2 > g->len ? v & 0xFF00u : v;                 /* the second byte lies past the end: zero */
 }
 
 /* parallel E4, after the chains: basis word + running sum -> basis dword (h4m:726-731), literal blocks copied */
@@ -1330,6 +1342,42 @@ GP_FN uint32_t gp_mvs(GPic *g, const GCode *codes, int comp, uint32_t list_slot)
     return comp ? gp_mvs_comp(g, codes, 1, list_slot) : gp_mvs_comp(g, codes, 0, list_slot);
 }
 
+/* parallel, last: what the finished blob reads (hvq_refuse.h), the 64-block runs dealt to the threads; a thread that finds
+ * something ORs it into one word */
+GP_FN void gp_reads_geom(const GPic *g, HvqReadsGeom *q)
+{
+    q->blob = g->blob;
+    for (int i = 0; i < 3; ++i) {
+        q->map_off[i] = g->pl[i].map_off; q->plane_off[i] = g->pl[i].plane_off; q->run_first[i] = g->pl[i].run_first;
+        q->hb[i] = g->pl[i].hb; q->vb[i] = g->pl[i].vb;
+    }
+    q->mv_off = g->mv_off; q->wave_base_off = g->wave_base_off; q->pool_off = g->fixed_bytes; q->pool_dwords = g->pool_dwords;
+    q->pic_bytes = g->pic_bytes; q->total_runs = g->total_runs;
+    q->w = g->w; q->wshift = g->wshift; q->hshift = g->hshift; q->is15 = g->is15; q->landscape = g->landscape; q->mcb_w = g->mw; q->is_pb = g->is_pb;
+}
+
+GP_FN uint32_t gp_reads_walk_all(const GPic *g)
+{
+    HvqReadsGeom q;
+    gp_reads_geom(g, &q);
+    return hvq_reads_walk(&q, 0u, 1u);
+}
+
+GP_FN void gp_reads_check(GPic *g, int tid, int nthr)
+{
+    if (g->status) return;
+    HvqReadsGeom q;
+    gp_reads_geom(g, &q);
+    const uint32_t found = hvq_reads_walk(&q, (uint32_t)tid, (uint32_t)nthr) | (tid == 0 ? GP_READS_DONE : 0u);
+    if (found) {
+#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
+        atomicOr((uint32_t *)&g->part[GP_READSW], found);
+#else
+        g->part[GP_READSW] |= found;
+#endif
+    }
+}
+
 /* serial (thread 0): result record */
 GP_FN void gp_result(const GPic *g, GP_G HvqParseResult *out, uint32_t extra_flags)
 {
@@ -1339,6 +1387,12 @@ GP_FN void gp_result(const GPic *g, GP_G HvqParseResult *out, uint32_t extra_fla
     {   /* proc runs: entries [0, inter macroblocks) are the ones the picture uses */
         const uint32_t at = g->part[GP_CAPW(10)], inter = (uint32_t)g->mw * (uint32_t)g->mh - g->ntype0;
         if (g->is_pb && at && at - 1u < inter) capped |= HVQ_F_CAPPED;
+    }
+    if (!g->status) {
+        uint32_t found = g->part[GP_READSW];
+        if (!(found & GP_READS_DONE) && !g->retry) found = gp_reads_walk_all(g);      /* a caller that did not run the parallel walk: serially, here */
+        if (!g->is_pb) for (int i = 0; i < 3; ++i) if (g->part[GP_RLEW(i)]) found |= 1u << HVQ_SEC_RLE(i);
+        extra_flags |= hvq_reads_flags(found, g->dead, g->is_pb);
     }
     out->flags = g->flags | extra_flags | capped | (g->is15 ? HVQ_F_IS15 : 0u) | (g->landscape ? HVQ_F_LANDSCAPE : 0u);
     out->max_items = g->max_items; out->max_pairs = g->max_pairs;

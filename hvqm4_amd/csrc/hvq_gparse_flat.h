@@ -429,6 +429,7 @@ GP_FN void gf_exp_write(GPic *g, int x0, int x1, int tid, int nthr)           /*
             for (uint32_t k = 0; k < m && at < e.N; ++k) {
                 if (t[k] == 0) {
                     if (z >= e.nrun) { g->retry = 1; at = e.N; break; }       /* not enough run lengths */
+                    if (x >= 2) g->part[GP_RLEW(x - 2)] = 1u;                 /* an I picture's DC loop reads a run length (hvq_refuse.h) */
                     at += 1u + (uint32_t)e.run[z++];
                 } else { bad |= t[k]; gf_exp_put(g, x, at, t[k]); ++at; }
             }

@@ -20,6 +20,8 @@
 #include <stdatomic.h>
 #include <time.h>
 
+#include "hvq_refuse.h"
+
 #define LUT_BITS 10
 /* caps of the overflow-symbol loops, identical in hvq_gparse_core.h (see there) */
 #define SOVF_CAP 4096
@@ -116,6 +118,8 @@ static void code_read(Code *c, BitRd *carrier, int is_signed, int scale)     /* 
     c->next = 0x100;
     c->bad = 0;
     c->root = carrier->live ? code_node(c, carrier, is_signed, scale, 0) : 0;
+    if (!carrier->live) c->leaf[0] = 0;              /* no tree in the stream: the reference keeps an earlier picture's leaf -- such a picture is
+                                                        refused when it reads a symbol (hvq_refuse.h), with the value the GPU parser uses */
     code_lut(c, c->root, 0, 0);
 }
 
@@ -171,8 +175,17 @@ static int32_t sym_uovf(const Code *c, BitRd *b, int cap, uint32_t *flags)     /
 {
     int32_t total = 0, v;
     int guard = 0;
-    (void)flags;
     do { v = sym(c, b); total += v; } while (v >= 0xFF && ++guard < cap);
+    /* ... unless the run never ends: still open where nothing but zero bits is left (a one-leaf tree of 0xFF, a tree whose all-zero
+     * code is 0xFF) -- the reference does not return from it; refused like an endless run of sym_sovf */
+    if (__builtin_expect(v >= 0xFF, 0)) {
+        if (b->end != (const uint8_t *)UINTPTR_MAX) {
+            const uint8_t *at = b->p - (b->cnt >> 3);
+            size_t left = at < b->end ? (size_t)(b->end - at) * 8u + 64u : 64u;
+            while (v >= 0xFF && left--) v = sym(c, b);
+        }
+        if (v >= 0xFF) *flags |= HVQ_F_CAPPED;
+    }
     return total;
 }
 
@@ -214,6 +227,10 @@ struct HvqParser {
     uint8_t res[8];              /* P/B: residual bits of the vectors, h0 h1 v0 v1 0 0 0 0 (h4m:2023-2026): indexed by reference 0..2 like
                                     the device parser's (a type-3 macroblock, refused, still reads res[4]) */
     uint32_t tflags[8];          /* flags raised by the tasks of a phase (one word each: tasks run side by side) */
+    uint32_t dead;               /* bit i: section i of the offset table has size 0 (hvq_refuse.h) */
+    uint32_t tfound[8];          /* what the tasks of the reads check found (hvq_reads_walk) */
+    uint32_t rle_read[3];        /* I picture: the plane's DC loop read a run length */
+    uint32_t pool_dwords;
     uint32_t capped;             /* a task met an overflow run that does not end: the other tasks stop decoding values too */
     struct ParsePool *tp;        /* hvq_parser_set_threads: workers that run a phase's tasks beside the calling thread */
     /* HVQM4_AMD_PARSE_TIMING=1 (development aid): wall time per stage, summed over the parser's pictures, on stderr at destroy */
@@ -304,21 +321,24 @@ uint32_t hvq_parser_pic_bytes(const HvqParser *p) { return p->pic_bytes; }
 static const uint8_t *section(const HvqParser *p, const uint8_t *data, const uint8_t *tab, int i, int *live)
 {
     const uint8_t *s = data + be32(tab + 4 * i);
-    if (s + 4 > p->end) { *live = 0; return p->end; }
+    if (s + 4 > p->end) { *live = -1; return p->end; }          /* the size itself lies outside the picture */
     *live = be32(s) != 0;
     return s + 4;
 }
 
-static BitRd section_bits(const HvqParser *p, const uint8_t *data, const uint8_t *tab, int i)
+static BitRd section_bits(HvqParser *p, const uint8_t *data, const uint8_t *tab, int i)
 {
     BitRd b = { 0 };
     b.p = section(p, data, tab, i, &b.live);
     b.end = p->end;
+    if (b.live <= 0) p->dead |= (1u << i) | (b.live < 0 ? HVQ_SEC_OUTSIDE : 0u);
+    b.live = b.live > 0;
     return b;
 }
 
 static void common_sections(HvqParser *p, const uint8_t *data, const uint8_t *tab)
 {
+    p->dead = 0;
     for (int i = 0; i < 2; ++i) {
         p->bn[i] = section_bits(p, data, tab, 2 * i);
         p->bnr[i] = section_bits(p, data, tab, 2 * i + 1);
@@ -328,6 +348,7 @@ static void common_sections(HvqParser *p, const uint8_t *data, const uint8_t *ta
         p->dc[k] = section_bits(p, data, tab, 4 + 3 * k);
         p->bt[k] = section_bits(p, data, tab, 5 + 3 * k);
         p->fx[k] = section(p, data, tab, 6 + 3 * k, &live);
+        if (live <= 0) p->dead |= (1u << (6 + 3 * k)) | (live < 0 ? HVQ_SEC_OUTSIDE : 0u);
     }
 }
 
@@ -561,7 +582,7 @@ static void ipic_dc_plane(HvqParser *p, uint8_t *blob, int i, uint32_t *flags)  
 {
     const PPlane *q = &p->pl[i];
     BitRd dc = p->dc[i], rle = p->rle[i];
-    uint32_t run = 0;
+    uint32_t run = 0, zr = 0;
     (void)blob;
     for (int by = 0; by < q->vb; ++by) {
         uint8_t *row = dcv_ent(p, i, by, 0);
@@ -572,13 +593,14 @@ static void ipic_dc_plane(HvqParser *p, uint8_t *blob, int i, uint32_t *flags)  
             if (run) --run;
             else {
                 delta = (uint32_t)t_sovf(p, &p->c_dc, &dc, flags);
-                if (delta == 0) run = (uint32_t)sym(&p->c_run, &rle);
+                if (delta == 0) { run = (uint32_t)sym(&p->c_run, &rle); zr = 1; }
             }
             uint8_t v = (uint8_t)(pred + delta);               /* uint8 wrap: h4m:1145-1149 */
             row[bx] = v;
             pred = (uint8_t)((v + up[bx + 1] + 1) / 2);
         }
     }
+    p->rle_read[i] = zr;
 }
 
 /* ---- pass 2, step a (I, P and B pictures): a plane's coefficient symbols (bufTree0, h4m:726) and MC-residual scalars (h4m:1405-1406)
@@ -656,7 +678,11 @@ static inline void asm_literal(AsmCur *c, uint32_t *dst)                        
 {
     const uint8_t *s = c->fx;
     if (s + 16 <= c->end) { memcpy(dst, s, 16); c->fx = s + 16; }
-    else { memset(dst, 0, 16); c->fx = c->end; }
+    else {                                                          /* bytes at or beyond the end read as zero, byte by byte */
+        memset(dst, 0, 16);
+        if (s < c->end) memcpy(dst, s, (size_t)(c->end - s));
+        c->fx = c->end;
+    }
 }
 
 /* `n` bases of one block: word from fixvl, coefficient from bufTree0 (h4m:691-692, 726-731 / 738-739, 767-772) */
@@ -668,7 +694,7 @@ static inline void asm_bases(AsmCur *c, uint32_t n, uint32_t *dst)
         for (uint32_t k = 0; k < n; ++k) {
             const uint8_t *s = c->fx;
             uint32_t word = 0;
-            if (s + 2 <= c->end) { word = be16(s); c->fx = s + 2; } else c->fx = c->end;
+            if (s + 2 <= c->end) { word = be16(s); c->fx = s + 2; } else { if (s < c->end) word = (uint32_t)*s << 8; c->fx = c->end; }
             if (k < have) run += (uint32_t)(int32_t)*c->bt++;
             dst[k] = HVQ_BASIS(word, (run + ((word >> 13) & 3u)) & 0x3FFFFu);
         }
@@ -678,7 +704,7 @@ static inline void asm_bases(AsmCur *c, uint32_t n, uint32_t *dst)
     for (uint32_t k = 0; k < n; ++k) {
         const uint8_t *s = c->fx;
         uint32_t word = 0;
-        if (s + 2 <= c->end) { word = be16(s); c->fx = s + 2; } else c->fx = c->end;
+        if (s + 2 <= c->end) { word = be16(s); c->fx = s + 2; } else { if (s < c->end) word = (uint32_t)*s << 8; c->fx = c->end; }
         run += (uint32_t)(int32_t)*c->bt++;
         dst[k] = HVQ_BASIS(word, (run + ((word >> 13) & 3u)) & 0x3FFFFu);
     }
@@ -720,6 +746,33 @@ static void ipic_phase2b(HvqParser *p, uint8_t *blob, int task)
     int i, r0, r1;
     asm_range(p, task, &i, &r0, &r1);
     ipic_assemble(p, blob, i, r0, r1, task_flags(p, task));
+}
+
+/* the last phase of every picture: what the finished blob reads (hvq_refuse.h), the 64-block runs dealt to six tasks */
+static void reads_phase(HvqParser *p, uint8_t *blob, int task)
+{
+    HvqReadsGeom g;
+    g.blob = blob;
+    g.total_runs = 0;
+    for (int i = 0; i < 3; ++i) {
+        g.map_off[i] = p->map_off[i]; g.plane_off[i] = p->plane_off[i];
+        g.hb[i] = p->pl[i].hb; g.vb[i] = p->pl[i].vb;
+        g.run_first[i] = g.total_runs;
+        g.total_runs += p->pl[i].ntiles * (HVQ_TILE_BLOCKS / 64);
+    }
+    g.mv_off = p->mv_off; g.wave_base_off = p->wave_base_off; g.pool_off = p->fixed_bytes; g.pool_dwords = p->pool_dwords;
+    g.pic_bytes = p->pic_bytes;
+    g.w = p->w; g.wshift = p->wshift; g.hshift = p->hshift; g.is15 = p->is15; g.landscape = p->landscape; g.mcb_w = p->w / 8;
+    g.is_pb = ((const HvqPicHeader *)blob)->pic_kind != HVQ_PIC_I;
+    p->tfound[task] = hvq_reads_walk(&g, (uint32_t)task, 6u);
+}
+
+static uint32_t reads_verdict(const HvqParser *p, int is_pb)
+{
+    uint32_t found = 0;
+    for (int t = 0; t < 6; ++t) found |= p->tfound[t];
+    if (!is_pb) for (int i = 0; i < 3; ++i) if (p->rle_read[i]) found |= 1u << HVQ_SEC_RLE(i);
+    return hvq_reads_flags(found, p->dead, is_pb);
 }
 
 /* a prefix tree read from the head of its carrier section (h4m:632-642); the section's cursor goes through a copy on this thread's
@@ -812,6 +865,9 @@ static int parse_ipic(HvqParser *p, const uint8_t *pic, uint8_t *blob, size_t ca
     run_phase(p, payload_phase_a, blob, 4);                       /* an I picture has no MC-residual scalars: tasks 0, 2, 3 decode, 1 is empty */
     run_phase(p, ipic_phase2b, blob, 6);
     for (int t = 0; t < 6; ++t) p->flags |= p->tflags[t];          /* behind the header, like a P/B picture's pass 2 */
+    p->pool_dwords = pool_dwords;
+    run_phase(p, reads_phase, blob, 6);
+    p->flags |= reads_verdict(p, 0);
     TMARK(0, 3);
     if (p->flags & HVQ_F_HAS_NEST)
         pack_nest(blob + ((HvqPicHeader *)blob)->nest_off, p->nest);
@@ -1074,8 +1130,10 @@ static int parse_pbpic(HvqParser *p, int is_P, const uint8_t *pic, uint8_t *blob
     TMARK(1, 2);
     run_phase(p, payload_phase_a, blob, 6);
     run_phase(p, pb_phase2b, blob, 6);
+    p->pool_dwords = pool_dwords;
+    run_phase(p, reads_phase, blob, 6);
     TMARK(1, 3);
-    p->flags |= late;
+    p->flags |= late | reads_verdict(p, 1);
     for (int t = 0; t < 6; ++t) p->flags |= p->tflags[t];
     if (p->flags & HVQ_F_HAS_NEST)
         pack_nest(blob + ((HvqPicHeader *)blob)->nest_off, p->nest);

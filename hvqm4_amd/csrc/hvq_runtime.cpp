@@ -99,8 +99,9 @@ static uint32_t picture_workgroups(const uint32_t tile_first[4])
 
 /* Pictures this back end refuses instead of decoding them differently from the reference:
  *   HVQ_F_CAPPED    an overflow-symbol run ended on the parsers' cap: the reference would have gone on summing (h4m:654-677);
- *   HVQ_F_CLAMPED   a nest origin or vector target outside what the reference's arithmetic keeps in bounds was clamped
- *                   (malformed input); HVQM4_AMD_ALLOW_CLAMPED=1 decodes such pictures with the clamped values;
+ *   HVQ_F_CLAMPED   a nest origin or vector target outside what the reference's arithmetic keeps in bounds was clamped, or the
+ *                   picture reads outside the referenced picture or from an empty section (hvq_refuse.h; malformed input);
+ *                   HVQM4_AMD_ALLOW_CLAMPED=1 decodes such pictures with clamped addresses;
  *   HVQ_F_MALFORMED a P/B luma kind symbol above 15, or a type run that opens at value 3: the reference decodes those outside its own
  *                   rules (stored type / proc bits, a table index and a residual-bit count the stream does not set); or a prefix tree
  *                   with more inner nodes than 256 leaf bytes allow (the GPU parser rejects it too).  Not opt-in. */
@@ -110,7 +111,7 @@ static const char *unsupported_reason(uint32_t flags)
     if (flags & HVQ_F_MALFORMED) return "malformed picture: a P/B luma kind symbol above 15 (h4m:1701, 1927), a macroblock type run that opens at value 3 (h4m:1591, 1606, 1950-1951) or a prefix tree with more inner nodes than 256 leaves allow";
     if (flags & HVQ_F_CLAMPED) {
         const char *e = getenv("HVQM4_AMD_ALLOW_CLAMPED");
-        if (!(e && atoi(e) > 0)) return "malformed picture: a nest origin or vector target had to be clamped (HVQM4_AMD_ALLOW_CLAMPED=1 decodes it anyway)";
+        if (!(e && atoi(e) > 0)) return "malformed picture: a nest origin or vector target had to be clamped, a motion-compensated block or window basis reads outside the referenced picture, or an empty section is read (HVQM4_AMD_ALLOW_CLAMPED=1 decodes it anyway)";
     }
     return nullptr;
 }
@@ -1658,7 +1659,10 @@ static int flush_end(HvqContext *c)
             const char *why = nullptr;
             int code = HVQ_OK;
             if ((!broken[(size_t)p.stream] || p.kind == HVQ_PIC_I) && !p.dropped && p.dev) {
-                if (p.status) { code = (p.status & GP_ST_OVERFLOW) ? HVQ_E_OVERFLOW : HVQ_E_ARG; why = "the GPU parser rejected the bitstream"; }
+                if (p.status == (int)GP_ST_BADTREE) {       /* what the host parser flags HVQ_F_MALFORMED: the same refusal on both parse paths */
+                    code = HVQ_E_UNSUPPORTED; why = unsupported_reason(HVQ_F_MALFORMED);
+                }
+                else if (p.status) { code = (p.status & GP_ST_OVERFLOW) ? HVQ_E_OVERFLOW : HVQ_E_ARG; why = "the GPU parser rejected the bitstream"; }
                 else if ((why = unsupported_reason(p.flags)) != nullptr) code = HVQ_E_UNSUPPORTED;
             }
             if (!broken[(size_t)p.stream] && !p.dropped && !code && p.kind == HVQ_PIC_P && p.old_slot == -2 && !p.host_old) {

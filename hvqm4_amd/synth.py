@@ -97,6 +97,10 @@ class SynthConfig:
                                       # v0 = v1, so the reference's value 2 after bit 0 (mcbtypetrans[0][3]) consumes the same bits;
                                       # after bit 1 it reads past its table (h4m:1606) and leaves the stream's step
     mb_type3_exits: Sequence[int] = (0, 1)   # mb_type3: the transition bits a type-3 run may leave through
+    plane_runoff: float = 0.0         # P/B pictures: probability that a macroblock's vector is chosen so that its MC reads LEAVE their
+                                      # plane and end anywhere inside the picture buffer [0, picsize): luma into U, U into V, chroma
+                                      # backwards into the preceding plane.  The reference's pictures are one allocation, Y|U|V
+                                      # (h4m:2347-2349), so these reads are defined and deterministic
 
 
 class _Ops:
@@ -457,6 +461,41 @@ class _Gen:
                 return False
         return True
 
+    def _mc_span(self, rx: int, ry: int):
+        """[(plane offset, plane samples, first, last)] per plane: the buffer offsets between which the MC reads of the macroblock's
+        blocks of that plane lie (h4m:1242-1294, 1327-1355)"""
+        out = []
+        off = 0
+        for p in range(3):
+            ws, hs = (self.cws, self.chs) if p else (0, 0)
+            pw, ph = self.w >> ws, self.h >> hs
+            pdx, pdy = rx >> ws, ry >> hs
+            hx, hy = (pdx & 1, pdy & 1) if self.is15 else (rx & 1, ry & 1)
+            lo = off + (pdy >> 1) * pw + (pdx >> 1)
+            hi = lo + ((8 >> hs) - 1 + hy) * pw + (8 >> ws) - 1 + hx
+            out.append((off, pw * ph, lo, hi))
+            off += pw * ph
+        return out
+
+    def _mv_in_buffer(self, rx: int, ry: int) -> bool:
+        """every MC read of every plane inside [0, picsize)"""
+        return all(lo >= 0 and hi <= self.picsize - 1 for _, _, lo, hi in self._mc_span(rx, ry))
+
+    def _mv_crosses(self, rx: int, ry: int) -> bool:
+        return any(lo < off or hi > off + n - 1 for off, n, lo, hi in self._mc_span(rx, ry))
+
+    def _window_in_buffer(self, rx: int, ry: int) -> bool:
+        """the whole MC-nest window (h4m:1862-1910) inside the buffer; C division, as the reference computes it"""
+        w = self.w
+        cx, cy = int(rx / 2), int(ry / 2)
+        if self.landscape:
+            o = cx + (cy - 16) * w - 32
+            mx = o + 37 * w + 69
+        else:
+            o = cx + (cy - 32) * w - 16
+            mx = o + 69 * w + 37
+        return o >= 0 and mx <= self.picsize - 1
+
     def _mv_sane(self, rx: int, ry: int) -> bool:
         """reads stay inside the picture rectangle of every plane"""
         if rx < 0 or ry < 0:
@@ -549,7 +588,19 @@ class _Gen:
             Rh, Rv = 1 << (rh + 5), 1 << (rv + 5)
             x, y = (m % mw) * 8, (m // mw) * 8
             want_predi = procs[m] == 0
-            for attempt in range(24):
+            wild = False
+            if cfg.plane_runoff > 0 and rng.random() < cfg.plane_runoff:
+                for _ in range(32):
+                    nh = int(rng.integers(-Rh, Rh)); nv = int(rng.integers(-Rv, Rv))
+                    if m == 0:
+                        # the first macroblock can reach BACKWARDS: a target in luma row 1 left of the picture is a luma read that
+                        # ends in row 0, while the chroma planes, half as wide, start in front of their plane (U in Y, V in U)
+                        nh = -int(rng.integers(1, min(Rh, 2 * self.w) + 1)); nv = int(rng.integers(2, 4))
+                    rx, ry = 2 * x + nh, 2 * y + nv
+                    if self._mv_in_buffer(rx, ry) and self._mv_crosses(rx, ry):
+                        wild = True
+                        break
+            for attempt in range(0 if wild else 24):
                 if attempt == 23:
                     nh, nv = 0, 0
                 elif self.smooth_mv and attempt < 8:
@@ -568,7 +619,7 @@ class _Gen:
                 ok = self._mv_legal(rx, ry, False) and (runoff or self._mv_sane(rx, ry))
                 if ok:
                     break
-            predi_ok[m] = want_predi and self._mv_legal(rx, ry, True)
+            predi_ok[m] = want_predi and (self._window_in_buffer(rx, ry) if wild else self._mv_legal(rx, ry, True))
             ref_xy[m] = (rx, ry)
             for (new, old, r, R, stream) in ((nh, mvh, rh, Rh, MVH), (nv, mvv, rv, Rv, MVV)):
                 d = new - old

@@ -114,8 +114,74 @@ def oracle():
         lib.hvqo_yuv420_to_rgb.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.hvqo_nest.restype = C.c_void_p
         lib.hvqo_nest.argtypes = [C.c_void_p]
+        lib.hvqc_create.restype = C.c_void_p
+        lib.hvqc_create.argtypes = [C.c_int] * 5
+        lib.hvqc_destroy.argtypes = [C.c_void_p]
+        lib.hvqc_picsize.restype = C.c_uint32
+        lib.hvqc_picsize.argtypes = [C.c_void_p]
+        lib.hvqo_check_picture.restype = C.c_uint32
+        lib.hvqo_check_picture.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _orc = lib
     return _orc
+
+
+# ---- the checked oracle (hvq_oracle_chk.c): one guarded decode per picture, a class instead of a wild read
+C_MEM, C_MAP, C_EMPTY, C_TREE, C_HANG, C_RULES = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+CLASS_NAMES = ((C_TREE, "tree"), (C_RULES, "rules"), (C_HANG, "hang"), (C_MEM, "mem"), (C_MAP, "map"), (C_EMPTY, "empty"))
+
+
+def class_name(cls: int) -> str:
+    """the class a refusal reports for the mask `cls`, in the order the product reports its flags (malformed, capped, clamped)"""
+    for bit, name in CLASS_NAMES:
+        if cls & bit:
+            return name
+    return "defined"
+
+
+class Report(C.Structure):
+    _fields_ = [("cls", C.c_uint32), ("past_bits", C.c_uint32), ("cross", C.c_uint32)]
+
+
+class CheckedPlayer:
+    """The checked oracle with the player's picture rotation (h4m:2087-2137).  `check` decodes a picture against the current
+    references WITHOUT moving the rotation (into a private copy of the picture being written) and returns (class mask, report,
+    picture or None); `advance` decodes the stream's own picture and rotates."""
+
+    def __init__(self, width: int, height: int, samp_h: int, samp_v: int, is15: bool):
+        self.lib = oracle()
+        self.o = self.lib.hvqc_create(width, height, samp_h, samp_v, 1 if is15 else 0)
+        self.ps = self.lib.hvqc_picsize(self.o)
+        self.buf = [np.zeros(self.ps, dtype=np.uint8) for _ in range(3)]     # past, present, future
+
+    def close(self) -> None:
+        if self.o:
+            self.lib.hvqc_destroy(self.o)
+            self.o = None
+
+    def refs(self, ft: int):
+        """(past, present, future) as the decode of a picture of type `ft` sees them"""
+        b = self.buf
+        return (b[0], b[1], b[2]) if ft == 0x30 else (b[2], b[1], b[0])
+
+    def check(self, ft: int, pic: bytes):
+        past, present, future = self.refs(ft)
+        out = present.copy()
+        rep = Report()
+        cls = self.lib.hvqo_check_picture(self.o, ft, pic, len(pic), out.ctypes.data, past.ctypes.data, future.ctypes.data, C.byref(rep))
+        return cls, rep, (out if cls == 0 else None)
+
+    def advance(self, ft: int, pic: bytes) -> np.ndarray:
+        b = self.buf
+        if ft != 0x30:
+            b[0], b[2] = b[2], b[0]
+        rep = Report()
+        cls = self.lib.hvqo_check_picture(self.o, ft, pic, len(pic), b[1].ctypes.data, b[0].ctypes.data, b[2].ctypes.data, C.byref(rep))
+        if cls:
+            raise RuntimeError(f"the stream's own picture is not defined: {class_name(cls)}")
+        out = b[1].copy()
+        if ft != 0x30:
+            b[1], b[2] = b[2], b[1]
+        return out
 
 
 def clip_picsize(data: bytes) -> int:

@@ -20,11 +20,47 @@
 
 #define API __attribute__((visibility("default")))
 
+#ifdef HVQO_CHECKED
+/* the second compile lives beside the first in one library: its objects have their own layout and their own entry points */
+#define hvqo_create hvqc_create
+#define hvqo_destroy hvqc_destroy
+#define hvqo_picsize hvqc_picsize
+#define hvqo_nest hvqc_nest
+#define hvqo_map hvqc_map
+#define hvqo_tables hvqc_tables
+#define hvqo_weight_block hvqc_weight_block
+#define hvqo_motion_comp hvqc_motion_comp
+#endif
+
+/*
+ * Checked mode (hvq_oracle_chk.c compiles this file a second time with HVQO_CHECKED): the same decode, with every access that the
+ * picture's bytes control behind a guard.  A guarded decode returns a class mask (HVQO_C_*, 0 = defined) instead of reading or
+ * looping where the reference would leave its own memory or never return:
+ *   - bits and bytes at or beyond the picture's length read as zero (the product's rule; counted, no class);
+ *   - HVQO_C_MEM    a motion-compensated block or a sample of a used window basis outside [0, picsize) of the referenced picture;
+ *   - HVQO_C_MAP    a nest origin whose window leaves the bordered map array;
+ *   - HVQO_C_EMPTY  a symbol, bit or byte read from a section of size 0 (the reference dereferences NULL, h4m:1061-1071), a
+ *                   symbol from a tree whose carrier section is empty (the reference returns a leaf of an earlier picture), or a
+ *                   section whose 4-byte size does not lie inside the picture (the reference reads it used or not);
+ *   - HVQO_C_TREE   a prefix tree with more inner nodes than 256 leaf bytes allow;
+ *   - HVQO_C_HANG   an overflow-symbol loop that cannot end: still open where nothing but zero bits is left;
+ *   - HVQO_C_RULES  a P/B luma kind symbol above 15, or a type run that opens at 3.
+ * The unchecked entry points compile exactly as before (every guard is behind the macro).
+ */
+#ifdef HVQO_CHECKED
+typedef struct { const uint8_t *pic; uint64_t len; uint32_t cls, past, cross; int hang; } Chk;
+static __thread Chk K;
+static inline uint32_t kbyte(uint64_t off) { if (off < K.len) return K.pic[off]; K.past += 8; return 0; }
+static inline uint32_t krd32(uint64_t o) { return (kbyte(o) << 24) | (kbyte(o + 1) << 16) | (kbyte(o + 2) << 8) | kbyte(o + 3); }
+#endif
+
 /* ---------- bit reader: MSB-first byte stream (== h4m:552-602 over BE32 words) ---------- */
+#ifndef HVQO_CHECKED
 typedef struct {
     const uint8_t *base;   /* NULL when the section is empty (h4m:1061-1071) */
     uint32_t pos;          /* in bits */
 } Bits;
+#define LIVE(b) ((b)->base != NULL)
 
 static inline uint32_t take1(Bits *b)
 {
@@ -32,6 +68,27 @@ static inline uint32_t take1(Bits *b)
     b->pos++;
     return v;
 }
+#else
+typedef struct {
+    uint64_t off;          /* byte offset of the section's payload inside the picture */
+    uint32_t pos;          /* in bits */
+    int live;              /* size != 0 */
+} Bits;
+#define LIVE(b) ((b)->live)
+
+static inline uint32_t take1(Bits *b)
+{
+    const uint64_t at = b->off + (b->pos >> 3);
+    uint32_t v = 0;
+    if (!b->live) K.cls |= HVQO_C_EMPTY;
+    if (at < K.len) v = (K.pic[at] >> (7 - (b->pos & 7))) & 1u;
+    else K.past++;
+    if (b->pos != UINT32_MAX) b->pos++;
+    return v;
+}
+/* nothing but zero bits from here on */
+static inline int exhausted(const Bits *b) { return b->off + (b->pos >> 3) >= K.len; }
+#endif
 
 static inline uint32_t take(Bits *b, int n)
 {
@@ -47,6 +104,7 @@ static uint32_t rd16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
 typedef struct {
     int root;              /* < 256: single leaf, >= 256: inner node */
     int next;
+    int dead;              /* checked mode: read from an empty carrier */
     int16_t kid[2][512];
     int32_t leaf[256];     /* value of leaf byte, after sign/scale/int16 truncation */
 } Code;
@@ -59,6 +117,9 @@ static int code_node(Code *c, Bits *b, int is_signed, int scale)
         c->leaf[byte] = (int16_t)((uint32_t)v << scale);      /* h4m:613-617: shifted in int, kept as int16 */
         return byte;
     }
+#ifdef HVQO_CHECKED
+    if (c->next >= 511) { K.cls |= HVQO_C_TREE; return 0; }
+#endif
     int id = c->next < 511 ? c->next++ : 511;
     int a = code_node(c, b, is_signed, scale);
     c->kid[0][id] = (int16_t)a;
@@ -70,12 +131,19 @@ static int code_node(Code *c, Bits *b, int is_signed, int scale)
 static void code_read(Code *c, Bits *carrier, int is_signed, int scale)   /* h4m:632-642 */
 {
     c->next = 0x100;
-    c->root = carrier->base ? code_node(c, carrier, is_signed, scale) : 0;
+    c->dead = !LIVE(carrier);
+#ifdef HVQO_CHECKED
+    if (c->dead) c->leaf[0] = 0;     /* the reference keeps an earlier picture's leaf: any symbol of this tree is HVQO_C_EMPTY */
+#endif
+    c->root = LIVE(carrier) ? code_node(c, carrier, is_signed, scale) : 0;
 }
 
 static inline int32_t sym(const Code *c, Bits *b)                          /* h4m:644-651 */
 {
     int n = c->root;
+#ifdef HVQO_CHECKED
+    if (c->dead || !b->live) K.cls |= HVQO_C_EMPTY;
+#endif
     while (n >= 0x100) n = c->kid[take1(b)][n];
     return c->leaf[n];
 }
@@ -83,6 +151,16 @@ static inline int32_t sym(const Code *c, Bits *b)                          /* h4
 static int32_t sym_sovf(const Code *c, Bits *b, int32_t lo, int32_t hi)    /* h4m:654-664 */
 {
     int32_t total = 0, v;
+#ifdef HVQO_CHECKED
+    if (K.hang) return 0;
+    for (;;) {
+        const int beyond = exhausted(b);          /* this symbol is decoded from zero bits alone: so is every later one */
+        const uint32_t at = b->pos;
+        v = sym(c, b); total = (int32_t)((uint32_t)total + (uint32_t)v);
+        if (!(v <= lo || v >= hi)) return total;
+        if (beyond || b->pos == at) { K.cls |= HVQO_C_HANG; K.hang = 1; return 0; }     /* ... or it consumed no bit (a one-leaf tree) */
+    }
+#endif
     do { v = sym(c, b); total = (int32_t)((uint32_t)total + (uint32_t)v); } while (v <= lo || v >= hi);
     return total;
 }
@@ -90,9 +168,30 @@ static int32_t sym_sovf(const Code *c, Bits *b, int32_t lo, int32_t hi)    /* h4
 static int32_t sym_uovf(const Code *c, Bits *b)                            /* h4m:667-677, max always 255 */
 {
     int32_t total = 0, v;
+#ifdef HVQO_CHECKED
+    for (;;) {
+        const int beyond = exhausted(b);
+        const uint32_t at = b->pos;
+        v = sym(c, b); total = (int32_t)((uint32_t)total + (uint32_t)v);
+        if (v < 0xFF) return total;
+        if (beyond || b->pos == at) { K.cls |= HVQO_C_HANG; return 0x7FFFFFFF; }      /* a run that covers whatever is left of the picture */
+        if (total > 0x40000000) total = 0x40000000;
+    }
+#endif
     do { v = sym(c, b); total += v; } while (v >= 0xFF);
     return total;
 }
+
+/* the fixed-length sections (basis words, literal blocks): a pointer, in checked mode an offset into the picture */
+#ifndef HVQO_CHECKED
+typedef const uint8_t *Fx;
+#define FX8(f, i) ((f)[i])
+#else
+typedef uint64_t Fx;
+#define FX_DEAD (1ull << 63)
+static inline uint32_t fx8(Fx f, int i) { if (f & FX_DEAD) K.cls |= HVQO_C_EMPTY; return kbyte((f & ~FX_DEAD) + (uint64_t)i); }
+#define FX8(f, i) fx8(f, i)
+#endif
 
 /* ---------- geometry (h4m:438-465, 843-870) ---------- */
 typedef struct {
@@ -115,13 +214,17 @@ struct HvqOracle {
     uint8_t nest[70 * 38];
     Code c_dc, c_run, c_bt, c_bn, c_mv, c_mcb;
     Bits bn[2], bnr[2], dc[3], bt[3], rle[3], mvh, mvv, mtype, mproc;
-    const uint8_t *fx[3];
+    Fx fx[3];
     int unk_shift, dc_shift;
     int32_t dc_lo, dc_hi;
     uint8_t res[6];        /* h0 h1 v0 v1 pad pad  (h4m:502-505 memory order) */
     int32_t divt[16];
     int32_t mcdiv[512];
     uint32_t picsize;
+#ifdef HVQO_CHECKED
+    const uint8_t *ref_base;   /* the referenced picture of the macroblock being decoded, and its window's offset in it */
+    int64_t win_off;
+#endif
 };
 
 static inline uint8_t *ent(const Plane *p, int by, int bx) { return p->map + 2 * ((by + 1) * p->stride + bx + 1); }
@@ -240,8 +343,12 @@ API void hvqo_motion_comp(uint8_t dst16[16], const uint8_t *src, uint32_t stride
 
 static void literal_block(HvqOracle *o, int plane, uint8_t *dst, int stride)   /* h4m:543-549 */
 {
-    const uint8_t *s = o->fx[plane];
+    Fx s = o->fx[plane];
+#ifdef HVQO_CHECKED
+    for (int y = 0; y < 4; ++y) for (int x = 0; x < 4; ++x) dst[y * stride + x] = (uint8_t)FX8(s, 4 * y + x);
+#else
     for (int y = 0; y < 4; ++y) memcpy(dst + y * stride, s + 4 * y, 4);
+#endif
     o->fx[plane] = s + 16;
 }
 
@@ -253,12 +360,24 @@ static void literal_block(HvqOracle *o, int plane, uint8_t *dst, int stride)   /
 static void aot_basis(HvqOracle *o, int plane, const uint8_t *nest, int nstride, int hi_nibble,
                       uint32_t *run, uint32_t acc[16])
 {
-    uint32_t word = rd16(o->fx[plane]);
+    uint32_t word = (FX8(o->fx[plane], 0) << 8) | FX8(o->fx[plane], 1);
     o->fx[plane] += 2;
     uint32_t off_long = word & 0x3F, off_short = (word >> 6) & 0x1F;
     uint32_t s_long = (word >> 11) & 1, s_short = (word >> 12) & 1;
     int xs, ys;
     const uint8_t *p;
+#ifdef HVQO_CHECKED
+    static const uint8_t zeros[4 * 140 + 8];
+    if (hi_nibble) {                                 /* a window basis: its 16 samples lie between the first and the last one */
+        int64_t q = o->win_off + (o->landscape ? (int64_t)nstride * off_short + off_long : (int64_t)nstride * off_long + off_short);
+        if (o->landscape) { xs = 1 << s_long; ys = nstride << s_short; } else { xs = 1 << s_short; ys = nstride << s_long; }
+        if (q < 0 || q + 3 * ys + 3 * xs >= (int64_t)o->picsize) { K.cls |= HVQO_C_MEM; p = zeros; xs = 1; ys = 4; }
+        else {
+            if (q + 3 * ys + 3 * xs >= (int64_t)o->pl[0].samples) K.cross++;
+            p = o->ref_base + q;
+        }
+    } else
+#endif
     if (o->landscape) { p = nest + (size_t)nstride * off_short + off_long; xs = 1 << s_long; ys = nstride << s_short; }
     else              { p = nest + (size_t)nstride * off_long + off_short; xs = 1 << s_short; ys = nstride << s_long; }
     uint8_t e[16];
@@ -328,6 +447,21 @@ static void predi_aot_block(HvqOracle *o, int plane, uint8_t *dst, const uint8_t
 }
 
 /* ---------- picture header / sections ---------- */
+#ifdef HVQO_CHECKED
+static Bits section_bits(const uint8_t *data, const uint8_t *tab, int i)
+{
+    const uint64_t s = (uint64_t)(data - K.pic) + krd32((uint64_t)(tab - K.pic) + 4u * (unsigned)i);
+    if (s + 4 > K.len) K.cls |= HVQO_C_EMPTY;        /* the reference reads the size wherever the table points, used or not */
+    Bits b = { s + 4, 0, s + 4 <= K.len && krd32(s) != 0 };
+    return b;
+}
+static Fx section_bytes(const uint8_t *data, const uint8_t *tab, int i)
+{
+    const uint64_t s = (uint64_t)(data - K.pic) + krd32((uint64_t)(tab - K.pic) + 4u * (unsigned)i);
+    if (s + 4 > K.len) K.cls |= HVQO_C_EMPTY;
+    return (s + 4 <= K.len && krd32(s)) ? s + 4 : (s + 4) | FX_DEAD;
+}
+#else
 static Bits section_bits(const uint8_t *data, const uint8_t *tab, int i)   /* h4m:1061-1071 */
 {
     const uint8_t *s = data + rd32(tab + 4 * i);
@@ -339,6 +473,7 @@ static const uint8_t *section_bytes(const uint8_t *data, const uint8_t *tab, int
     const uint8_t *s = data + rd32(tab + 4 * i);
     return rd32(s) ? s + 4 : NULL;
 }
+#endif
 
 static void common_sections(HvqOracle *o, const uint8_t *data, const uint8_t *tab)
 {
@@ -405,6 +540,10 @@ static void make_nest(HvqOracle *o, int nx, int ny)                        /* h4
     int mcols = o->nest_w - cols; if (mcols > cols) mcols = cols;
     int mrows = o->nest_h - rows; if (mrows > rows) mrows = rows;
     uint8_t *n = o->nest;
+#ifdef HVQO_CHECKED
+    /* ent() indexes the bordered map flat (h4m:1169): defined as long as the window's last entry lies inside the array */
+    if ((int64_t)(ny + rows) * Y->stride + nx + cols >= (int64_t)Y->stride * (Y->vb + 2)) { K.cls |= HVQO_C_MAP; return; }
+#endif
     memset(n, 0, sizeof o->nest);
     for (int r = 0; r < rows; ++r) {
         uint8_t *row = n + r * o->nest_w;
@@ -444,7 +583,17 @@ static void ipic_plane(HvqOracle *o, int p, uint8_t *dst)                  /* h4
     }
 }
 
-API void hvqo_decode_ipic(HvqOracle *o, const uint8_t *pic, uint8_t *present)   /* h4m:1970-2016 */
+#ifdef HVQO_CHECKED
+#define DECODE_IPIC static void chk_ipic
+#define DECODE_BPIC static void chk_bpic
+#define STOP_IF_REFUSED() do { if (K.cls & (HVQO_C_TREE | HVQO_C_HANG | HVQO_C_RULES)) return; } while (0)
+#else
+#define DECODE_IPIC API void hvqo_decode_ipic
+#define DECODE_BPIC API void hvqo_decode_bpic
+#define STOP_IF_REFUSED() do { } while (0)
+#endif
+
+DECODE_IPIC(HvqOracle *o, const uint8_t *pic, uint8_t *present)   /* h4m:1970-2016 */
 {
     o->dc_shift = pic[0];
     o->unk_shift = pic[1];
@@ -458,8 +607,10 @@ API void hvqo_decode_ipic(HvqOracle *o, const uint8_t *pic, uint8_t *present)   
     code_read(&o->c_bt, &o->bt[0], 0, 2);
     o->dc_hi = (int32_t)((uint32_t)0x7F << o->dc_shift);
     o->dc_lo = (int32_t)((uint32_t)-0x80 << o->dc_shift);
+    STOP_IF_REFUSED();
     ipic_kinds(o);
     ipic_dc(o);
+    STOP_IF_REFUSED();
     make_nest(o, nx, ny);
     for (int p = 0; p < 3; ++p) { ipic_plane(o, p, present); present += o->pl[p].samples; }
 }
@@ -484,6 +635,9 @@ static void pb_kinds(HvqOracle *o, int mx, int my, uint32_t proc, uint32_t type,
         uint8_t *t = &e[2 * Y->moff[j] + 1];
         if (rl[0]) { *t = tag; --rl[0]; continue; }
         int16_t k = (int16_t)sym(&o->c_bn, &o->bn[0]);
+#ifdef HVQO_CHECKED
+        if ((uint16_t)k > 15u) K.cls |= HVQO_C_RULES;
+#endif
         if (k) *t = (uint8_t)(tag | k);
         else { *t = tag; rl[0] = (uint32_t)sym(&o->c_run, &o->bnr[0]); }
     }
@@ -502,8 +656,11 @@ static void pb_pass1(HvqOracle *o)                                         /* h4
 {
     static const uint32_t step[2][3] = { { 1, 2, 0 }, { 2, 0, 1 } };
     RunLen type = { 0, 0 }, proc = { 0, 0 };
-    if (o->mproc.base) { proc.value = take1(&o->mproc); proc.count = (uint32_t)sym_uovf(&o->c_mcb, &o->mproc); }
-    if (o->mtype.base) { type.value = take(&o->mtype, 2); type.count = (uint32_t)sym_uovf(&o->c_mcb, &o->mtype); }
+    if (LIVE(&o->mproc)) { proc.value = take1(&o->mproc); proc.count = (uint32_t)sym_uovf(&o->c_mcb, &o->mproc); }
+    if (LIVE(&o->mtype)) { type.value = take(&o->mtype, 2); type.count = (uint32_t)sym_uovf(&o->c_mcb, &o->mtype); }
+#ifdef HVQO_CHECKED
+    if (type.value == 3) { K.cls |= HVQO_C_RULES; return; }
+#endif
     uint32_t rl[2] = { 0, 0 };
     uint32_t pbdc[3] = { 0x7F, 0x7F, 0x7F };
     for (int my = 0; my < o->h / 8; ++my)
@@ -568,19 +725,49 @@ static void pb_inter_mcb(HvqOracle *o, int mx, int my, int proc, int32_t rx, int
                          uint8_t *const base[3], const uint8_t *const ref[3])
 {
     const uint8_t *window;
+#ifdef HVQO_CHECKED
+    static const uint8_t zeros[5 * 8192 + 8];      /* what a refused read delivers (pictures are at most 8192 wide) */
+    window = NULL;
+    o->ref_base = ref[0];
+    o->win_off = o->landscape ? (int64_t)(rx / 2) + (int64_t)(ry / 2 - 16) * o->pl[0].pw - 32
+                              : (int64_t)(rx / 2) + (int64_t)(ry / 2 - 32) * o->pl[0].pw - 16;
+#else
     if (o->landscape) window = ref[0] + rx / 2 + (ry / 2 - 16) * o->pl[0].pw - 32;
     else              window = ref[0] + rx / 2 + (ry / 2 - 32) * o->pl[0].pw - 16;
+#endif
     for (int p = 0; p < 3; ++p) {
         Plane *P = &o->pl[p];
         const uint8_t *e = ent(P, my * P->by_per, mx * P->bx_per);
         uint8_t *d0 = base[p] + (size_t)my * (8 >> P->hshift) * P->pw + mx * (8 >> P->wshift);
         int32_t pdx = rx >> P->wshift, pdy = ry >> P->hshift;
         int hx = o->is15 ? (pdx & 1) : (rx & 1), hy = o->is15 ? (pdy & 1) : (ry & 1);   /* h4m:1337-1343, 1890-1896 */
+#ifdef HVQO_CHECKED
+        const int64_t plane_off = ref[p] - ref[0];
+        const int64_t s0_off = plane_off + (int64_t)(pdy >> 1) * P->pw + (pdx >> 1);
+#else
         const uint8_t *s0 = ref[p] + (pdy >> 1) * P->pw + (pdx >> 1);
+#endif
         for (int j = 0; j < P->nblk; ++j) {
             int k = proc ? 0 : (e[2 * P->moff[j] + 1] & 0xF);
             uint8_t *d = d0 + P->poff[j];
+#ifdef HVQO_CHECKED
+            /* the block's reads lie between its first sample and the last one of its last row (one more row / column at a half position) */
+            const int64_t lo = s0_off + P->poff[j], hi = lo + (int64_t)(3 + hy) * P->pw + 3 + hx;
+            const uint8_t *s = zeros;
+            if (k != 6) {
+                if (lo < 0 || hi >= (int64_t)o->picsize || P->pw > 8192) K.cls |= HVQO_C_MEM;
+                else {
+                    if (lo < plane_off || hi >= plane_off + (int64_t)P->samples) K.cross++;
+                    s = ref[0] + lo;
+                }
+            }
+            if (k == 6) literal_block(o, p, d, P->pw);
+            else if (k == 0) mc_block(d, P->pw, s, P->pw, hx, hy);
+            else predi_aot_block(o, p, d, s, P->pw, k, window, o->pl[0].pw, hx, hy);
+            continue;
+#else
             const uint8_t *s = s0 + P->poff[j];
+#endif
             if (k == 6) literal_block(o, p, d, P->pw);
             else if (k == 0) mc_block(d, P->pw, s, P->pw, hx, hy);
             else predi_aot_block(o, p, d, s, P->pw, k, window, o->pl[0].pw, hx, hy);
@@ -588,8 +775,8 @@ static void pb_inter_mcb(HvqOracle *o, int mx, int my, int proc, int32_t rx, int
     }
 }
 
-API void hvqo_decode_bpic(HvqOracle *o, const uint8_t *pic, uint8_t *present,
-                          const uint8_t *past, const uint8_t *future)     /* h4m:2018-2056, 1912-1968 */
+DECODE_BPIC(HvqOracle *o, const uint8_t *pic, uint8_t *present,
+            const uint8_t *past, const uint8_t *future)     /* h4m:2018-2056, 1912-1968 */
 {
     o->dc_shift = pic[0];
     o->unk_shift = pic[1];
@@ -609,7 +796,9 @@ API void hvqo_decode_bpic(HvqOracle *o, const uint8_t *pic, uint8_t *present,
     o->dc_hi = (int32_t)((uint32_t)0x7F << o->dc_shift);
     o->dc_lo = (int32_t)((uint32_t)-0x80 << o->dc_shift);
 
+    STOP_IF_REFUSED();
     pb_pass1(o);
+    STOP_IF_REFUSED();
 
     uint8_t *base[3];
     const uint8_t *pastp[3], *futp[3];
@@ -627,16 +816,43 @@ API void hvqo_decode_bpic(HvqOracle *o, const uint8_t *pic, uint8_t *present,
             if (r != cur_ref) { cur_ref = r; mh = mv = 0; }
             mvec(o, &mh, &o->mvh, o->res[r]);
             mvec(o, &mv, &o->mvv, o->res[2 + r]);
+            STOP_IF_REFUSED();
             int32_t rx = (int32_t)((uint32_t)mx * 16u + (uint32_t)mh), ry = (int32_t)((uint32_t)my * 16u + (uint32_t)mv);
             pb_inter_mcb(o, mx, my, (tag >> 4) & 1, rx, ry, base, r == 0 ? pastp : futp);
         }
 }
 
+#ifndef HVQO_CHECKED
 API void hvqo_decode_ppic(HvqOracle *o, const uint8_t *pic, uint8_t *present, const uint8_t *past)   /* h4m:2058-2061 */
 {
     hvqo_decode_bpic(o, pic, present, past, present);
 }
+#else
+/* One guarded decode.  frame_type 0x10 / 0x20 / 0x30; a P picture's `future` is ignored (it is the picture being written,
+ * h4m:2060).  The picture is decoded into an exactly sized private copy of `present`, which is copied back only when the class
+ * is 0 (defined).  A 4-byte header shorter than the section table counts as read past the end like any other byte. */
+API uint32_t hvqo_check_picture(HvqOracle *o, int frame_type, const uint8_t *pic, size_t len, uint8_t *present,
+                                const uint8_t *past, const uint8_t *future, HvqoReport *rep)
+{
+    uint8_t head[8 + 0x44 + 4] = { 0 };
+    uint8_t *work = malloc(o->picsize);
+    memset(&K, 0, sizeof K);
+    memcpy(work, present, o->picsize);
+    memcpy(head, pic, len < sizeof head ? len : sizeof head);
+    K.pic = pic; K.len = len;
+    o->dc_shift = head[0] & 31; o->unk_shift = head[1] & 31;
+    /* the fixed header bytes are read directly: decode from `pic` only when they are all there */
+    if (len < 8) K.cls |= HVQO_C_EMPTY;
+    else if (frame_type == 0x10) chk_ipic(o, pic, work);
+    else chk_bpic(o, pic, work, past, frame_type == 0x20 ? work : future);
+    if (!K.cls) memcpy(present, work, o->picsize);
+    free(work);
+    if (rep) { rep->cls = K.cls; rep->past_bits = K.past; rep->cross = K.cross; }
+    return K.cls;
+}
+#endif
 
+#ifndef HVQO_CHECKED
 /* ---------- container + picture rotation (h4m:2078-2138, 2427-2537; format SURVEY App. B) ---------- */
 typedef struct { HvqOracle *o; uint8_t *buf[3]; /* past, present, future */ } Play;
 
@@ -765,3 +981,4 @@ API void hvqo_yuv420_to_rgb(const uint8_t *yuv, int w, int h, uint8_t *rgb)
             *rgb++ = clampf255(r); *rgb++ = clampf255(g); *rgb++ = clampf255(b);
         }
 }
+#endif /* !HVQO_CHECKED */

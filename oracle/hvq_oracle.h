@@ -49,6 +49,26 @@ void hvqo_tables(int32_t div16[16], int32_t mcdiv512[512]);
 const uint8_t *hvqo_nest(const HvqOracle *o);           /* 70*38 bytes */
 const uint8_t *hvqo_map(const HvqOracle *o, int plane, uint32_t *stride, uint32_t *rows); /* {value,type} pairs incl. border */
 
+/* ---- checked mode (hvq_oracle_chk.c: hvq_oracle.c compiled with HVQO_CHECKED, see there).  A checked oracle is its own
+ * object: hvqc_create / hvqc_destroy / hvqc_picsize mirror the calls above. */
+#define HVQO_C_MEM    0x01u
+#define HVQO_C_MAP    0x02u
+#define HVQO_C_EMPTY  0x04u
+#define HVQO_C_TREE   0x08u
+#define HVQO_C_HANG   0x10u
+#define HVQO_C_RULES  0x20u
+typedef struct HvqoReport {
+    uint32_t cls;          /* HVQO_C_* of everything met up to where the decode had to stop; 0 = defined */
+    uint32_t past_bits;    /* bits read at or beyond the picture's length (they read as zero) */
+    uint32_t cross;        /* reads that left their plane inside the picture buffer (legal and deterministic) */
+} HvqoReport;
+HvqOracle *hvqc_create(int width, int height, int h_samp, int v_samp, int is15);
+void hvqc_destroy(HvqOracle *o);
+uint32_t hvqc_picsize(const HvqOracle *o);
+/* one guarded decode of a picture of `len` bytes; `present` is written only when the class is 0 */
+uint32_t hvqo_check_picture(HvqOracle *o, int frame_type, const uint8_t *pic, size_t len, uint8_t *present,
+                            const uint8_t *past, const uint8_t *future, HvqoReport *rep);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,14 @@ SMALL = [
     # MC-residual scalars beyond 16 bits (long overflow runs in the DC sections): the item records carry the payload offset instead
     ("bigscalars64x64", SynthConfig(width=64, height=64, gop="IPB", seed=42, predi_big=0.03, dc_shifts=(0,))),
     ("literals96x96", SynthConfig(width=96, height=96, gop="IPB", seed=40, literal_weight=400.0, p_zero=0.02)),
+    # MC reads that leave their plane inside the picture buffer (luma into U, U into V, chroma backwards into the plane before): the
+    # reference's picture is one allocation Y|U|V, so they are defined; one clip per sampling (tests/coverage.py "mc-crossplane")
+    # A macroblock's vector moves all three planes, and V ends the buffer: 4:2:0 reaches all four cells (luma forwards over the last
+    # rows, chroma backwards from the first macroblock); 4:2:2 only luma run-off behind the last row; in 4:4:4 the planes move alike,
+    # so no MC block can leave its plane without V leaving the buffer -- that clip carries window bases that end in U
+    ("crossplane420_64x48", SynthConfig(width=64, height=48, gop="IPBB", seed=47, plane_runoff=0.5)),
+    ("crossplane422_13_64x48", SynthConfig(width=64, height=48, gop="IPBB", seed=49, plane_runoff=0.5, sampling="422", version="1.3")),
+    ("crossplane444_48x64", SynthConfig(width=48, height=64, gop="IPBB", seed=49, plane_runoff=0.5, sampling="444")),
 ]
 
 # Clips that once caught a defect; compared with the oracle like the others, not part of the golden manifest.

@@ -29,7 +29,8 @@ def _kind_class(kind: int) -> str:
 def histogram(clip) -> Counter:
     """Counter over cells:
       ("blk", pic, plane, ctx, cls)   ctx = "intra" | "past" | "future" (+ "/proc" for proc = 1 macroblocks)
-      ("mc", version, "luma"|"chroma", ref, hx, hy)   half-sample case of every motion-compensated block"""
+      ("mc", version, "luma"|"chroma", ref, hx, hy)   half-sample case of every motion-compensated block
+      ("mc-crossplane", "luma"|"chroma", ref)         motion-compensated blocks whose reads leave their plane inside the picture buffer"""
     from hvqm4_amd._lib import lib
     l = lib()
     is15 = clip.version == "1.5"
@@ -69,6 +70,13 @@ def histogram(clip) -> Counter:
                         pdx, pdy = int(rx) >> ws, int(ry) >> hs
                         hx, hy = ((pdx & 1), (pdy & 1)) if is15 else (int(rx) & 1, int(ry) & 1)
                         h[("mc", clip.version, "luma" if p == 0 else "chroma", ctx, hx, hy)] += 1
+                        # a read that leaves its plane inside the picture buffer (defined: the picture is one allocation Y|U|V)
+                        pw = width >> ws
+                        poff = 0 if p == 0 else width * height + (p - 1) * pw * (height >> hs)
+                        lo = poff + ((pdy >> 1) + (by & (1 - hs)) * 4) * pw + (pdx >> 1) + (bx & (1 - ws)) * 4
+                        hi = lo + (3 + hy) * pw + 3 + hx
+                        if lo < poff or hi >= poff + pw * (height >> hs):
+                            h[("mc-crossplane", "luma" if p == 0 else "chroma", ctx)] += 1
     l.hvq_parser_destroy(prs)
     return h
 
@@ -94,4 +102,7 @@ def required_cells():
                 for hx in (0, 1):
                     for hy in (0, 1):
                         cells.append(("mc", version, comp, ref, hx, hy))
+    for comp in ("luma", "chroma"):
+        for ref in ("past", "future"):
+            cells.append(("mc-crossplane", comp, ref))
     return cells

@@ -156,6 +156,7 @@ again:
         extra |= gp_mvs(g, codes, 1, 18u);
         for (int t = 0; t < NTHR; ++t) gp_emit_merge(g, t, NTHR);
     }
+    for (int t = 0; t < NTHR; ++t) gp_reads_check(g, t, NTHR);
     gp_result(g, res, extra);
     res->pad[0] = retried;
     free(d); free(scratch); free(rowbuf); free(g); free(codes);

@@ -28,7 +28,7 @@ class Result(C.Structure):
 @pytest.fixture(scope="module")
 def emul():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    deps = [SRC] + [os.path.join(HERE, "..", "hvqm4_amd", "csrc", f) for f in ("hvq_gparse_core.h", "hvq_gparse_flat.h", "hvq_desc.h")]
+    deps = [SRC] + [os.path.join(HERE, "..", "hvqm4_amd", "csrc", f) for f in ("hvq_gparse_core.h", "hvq_gparse_flat.h", "hvq_desc.h", "hvq_refuse.h")]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.run(["gcc", "-O2", "-Wall", "-shared", "-fPIC", SRC, "-o", OUT], check=True)
     lib = C.CDLL(OUT)
