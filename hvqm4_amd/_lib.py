@@ -115,6 +115,8 @@ SYMBOLS = {
     "hvq_picture_device_ptr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "hvq_export_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "hvq_export_tensors": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "hvq_get_stats": (C.c_int, [C.c_void_p, C.POINTER(HvqStats)]),
     "hvq_debug_table_divisions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "hvq_last_error_string": (C.c_char_p, []),

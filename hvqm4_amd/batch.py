@@ -191,6 +191,35 @@ class Context:
         check(lib().hvq_export_pictures(self._h, n, a_s, a_o, FORMATS[fmt], C.cast(a_d, C.c_void_p),
                                            C.c_void_p(stream)))
 
+    def export_float(self, sids, ordinals, out, *, crop=None, mean=(0, 0, 0), std=(1, 1, 1), scale: float = 1 / 255) -> None:
+        """hvq_export_tensors: resident pictures as the float tensors a network eats -- crop, bilinear resize (half-sample centres
+        as F.interpolate(mode="bilinear", align_corners=False, antialias=False), taps clamped to the crop), (v * scale - mean) / std
+        per channel and the conversion to `out`'s dtype, planar RGB, in one launch on torch's current stream of `out`'s device.
+        `out` is one float32 / float16 / bfloat16 tensor [N, 3, H, W] or a list of N tensors [3, H_i, W_i]: their shapes pick the
+        output sizes (H, W equal to the crop's: no resampling, normalise only).  `crop`: None (whole pictures), one (x, y, w, h)
+        in luma samples for all, or a list per picture.  The arithmetic is specified in include/hvqm4_amd.h: v is the uint8
+        sample export(..., "rgbp") gives, as a float, and the call computes v * mul + add with mul = scale / std and
+        add = -mean / std rounded once to float32.  Ordering and slot safety are export()'s."""
+        import torch
+        from .export import HvqTensorDst, check_one_hip_runtime, crops, float_destinations, normalisation
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        mul, add = normalisation(mean, std, scale)
+        rects = crops(crop, [self._geom[s] for s in sids])
+        dtype, dsts = float_destinations(out, n)
+        check_one_hip_runtime()
+        dev = out.device if isinstance(out, torch.Tensor) else (out[0].device if n else torch.device("cuda"))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_d = (HvqTensorDst * n)(*[HvqTensorDst(p, r, pl, w, h, *rect) for (p, r, pl, w, h), rect in zip(dsts, rects)])
+        check(lib().hvq_export_tensors(self._h, n, a_s, a_o, dtype, (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
+                                       C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
+
     def rgb_bench(self, reps: int):
         """-> (gpu_ms, bytes_per_rep, pictures): batched display epilogue over the newest picture of every stream"""
         ms, by, n = C.c_float(0), C.c_uint64(0), C.c_uint32(0)

@@ -199,5 +199,27 @@ typedef struct HvqRgbJob {
     int32_t wshift, hshift;            /* chroma subsampling: (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 */
 } HvqRgbJob;
 
+/* one picture of the float export (hvq_yuv_tensor_kernel): crop rectangle (x0, y0, cw, ch) of the source in luma samples, resized
+ * to out_w x out_h, three planes `plane_pitch` bytes apart of out_h rows `row_pitch` bytes apart.  sx = cw / out_w and
+ * sy = ch / out_h are divided on the host.  dst and the pitches are multiples of the element size.  112 bytes: tables are uploaded
+ * in 16-byte units. */
+#define HVQ_TJ_IDENT  1u            /* out size == crop size, loads and stores vectorised: the streaming body */
+#define HVQ_TJ_VEC    2u            /* dst and pitches multiples of 16 bytes, out_w a multiple of the run length: 16-byte stores */
+typedef struct HvqTensorJob {
+    const uint8_t *y, *u, *v;
+    uint8_t *dst;
+    int64_t row_pitch, plane_pitch;    /* bytes */
+    int32_t w, h;                      /* source picture */
+    int32_t wshift, hshift;
+    int32_t x0, y0, cw, ch;
+    int32_t out_w, out_h;
+    float sx, sy;
+    uint32_t flags;
+    uint32_t pad[3];
+} HvqTensorJob;
+
+/* per call: o = v * mul[c] + add[c] */
+typedef struct HvqTensorNorm { float mul[3], add[3]; } HvqTensorNorm;
+
 
 #endif

@@ -1400,6 +1400,242 @@ void hvq_yuv_rgb_kernel(const HvqRgbJob *__restrict__ jobs)
     else yuv_rgb_job<FMT, WIDE, 0, 0>(J, idx, s_w);
 }
 
+/* ------------------------------------------------------------------------------------------------------
+ * Float export (hvq_export_tensors): crop, bilinear resize (half-sample centres, taps clamped to the crop), per-channel
+ * normalisation and the store as float32 / float16 / bfloat16 planar, in one pass over a resident picture.  The source value of a tap
+ * is the uint8 RGB sample of the export above (floor, saturate) as a float; coordinates, blend and normalisation are single
+ * precision with one rounding per operation; the 16-bit types are rounded to nearest even from the float result.  With this
+ * toolchain __fmul_rn / __fadd_rn are a plain multiply and add compiled under hipcc's default -ffp-contract=fast, which does fuse
+ * them, so the arithmetic below goes through t_mul / t_add / t_sub instead: the ISA of this kernel holds no float FMA.  Output-centric: one lane = one run of adjacent output samples of a row, R = 4
+ * (float32) or 8 (16-bit), for all three planes -- 16 bytes per plane.
+ */
+/* one IEEE operation each.  Written with the operators under contract(off): the instructions they become carry no licence to
+ * fuse, wherever they are inlined. */
+__device__ __forceinline__ float t_mul(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float t_add(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float t_sub(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+struct hvq_bf16 { uint16_t bits; };                          /* tag type of the bfloat16 instance */
+
+template <typename T> struct tensor_run { static constexpr int R = 16 / (int)sizeof(T); };
+
+/* float -> element of the output type, as raw bits */
+template <typename T> __device__ __forceinline__ u32 tensor_bits(float o);
+template <> __device__ __forceinline__ u32 tensor_bits<float>(float o) { return __float_as_uint(o); }
+template <> __device__ __forceinline__ u32 tensor_bits<_Float16>(float o)
+{
+    const _Float16 hval = (_Float16)o;                       /* v_cvt_f16_f32: round to nearest even, subnormals kept */
+    return (u32)__builtin_bit_cast(uint16_t, hval);
+}
+template <> __device__ __forceinline__ u32 tensor_bits<hvq_bf16>(float o)
+{
+    const u32 b = __float_as_uint(o);                        /* finite or infinite (mul and add are finite): no NaN to keep quiet */
+    return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
+}
+
+/* the three RGB samples of one (Y, U, V) byte triple as floats: rgb4's arithmetic, floor, saturate */
+__device__ __forceinline__ void tensor_rgb(u32 y, u32 u, u32 v, float px[3])
+{
+    const float Y = (float)y;
+    const float U = t_sub((float)u, 128.f);
+    const float V = t_sub((float)v, 128.f);
+    px[0] = t_add(Y, t_mul(1.402f, V));
+    px[1] = t_sub(t_sub(Y, t_mul(0.34414f, U)), t_mul(0.71414f, V));
+    px[2] = t_add(Y, t_mul(1.772f, U));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = __builtin_fminf(__builtin_fmaxf(__builtin_floorf(px[c]), 0.f), 255.f);
+}
+
+/* four normalised samples -> dwords of the output type: four (float32) or two (16-bit, the earlier sample in the low half) */
+template <typename T>
+__device__ __forceinline__ void tensor_pack4(const float o[4], u32 *q)
+{
+    if (sizeof(T) == 4) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) q[r] = tensor_bits<T>(o[r]);
+    } else {
+        q[0] = tensor_bits<T>(o[0]) | (tensor_bits<T>(o[1]) << 16);
+        q[1] = tensor_bits<T>(o[2]) | (tensor_bits<T>(o[3]) << 16);
+    }
+}
+
+__device__ __forceinline__ void tensor_store16(GLB uint8_t *p, const u32 q[4])
+{
+    const u32x4y v = { q[0], q[1], q[2], q[3] };
+    *(GLB u32x4y *)p = v;
+}
+
+/* the streaming body: output size == crop size, so every output sample is its source sample (lx = ly = 0 in the blend below) and
+ * only the normalisation remains.  One lane = R samples of a row: R bytes of Y in one load (a dword, or two), their chroma in
+ * one load per plane, one 16-byte store per plane; a wave-instruction stores a contiguous kilobyte.  The host picks this body only
+ * when x0 and the picture width are multiples of R (aligned loads) and HVQ_TJ_VEC holds. */
+template <typename T, int WS>
+__device__ __forceinline__ void tensor_ident(const HvqTensorJob &J, int idx, const HvqTensorNorm &nm)
+{
+    constexpr int R = tensor_run<T>::R, CB = R >> WS;        /* chroma bytes per lane: 2, 4 or 8 */
+    const int runs = J.out_w / R;
+    if (idx >= runs * J.out_h) return;
+    const int i = idx / runs, k = idx - i * runs;
+    const int sy = J.y0 + i, sx = J.x0 + R * k;
+    const GLB uint8_t *yp = (const GLB uint8_t *)J.y + (size_t)sy * J.w + sx;
+    const size_t co = (size_t)(sy >> J.hshift) * (size_t)(J.w >> WS) + (size_t)(sx >> WS);
+    const GLB uint8_t *up = (const GLB uint8_t *)J.u + co, *vp = (const GLB uint8_t *)J.v + co;
+    u32 yw[2] = { 0, 0 }, uw[2] = { 0, 0 }, vw[2] = { 0, 0 };
+    if (R == 4) yw[0] = *(const GLB u32 *)yp;
+    else { const u32x2 t = *(const GLB u32x2 *)yp; yw[0] = t.x; yw[1] = t.y; }
+    if (CB == 2) { uw[0] = *(const GLB uint16_t *)up; vw[0] = *(const GLB uint16_t *)vp; }
+    else if (CB == 4) { uw[0] = *(const GLB u32 *)up; vw[0] = *(const GLB u32 *)vp; }
+    else {
+        const u32x2 a = *(const GLB u32x2 *)up, b = *(const GLB u32x2 *)vp;
+        uw[0] = a.x; uw[1] = a.y; vw[0] = b.x; vw[1] = b.y;
+    }
+    u32 q[3][4];
+#pragma unroll
+    for (int g = 0; g < R / 4; ++g) {
+        float o[3][4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int r = 4 * g + rr, cr = r >> WS;
+            float px[3];
+            tensor_rgb((yw[r >> 2] >> (8 * (r & 3))) & 0xFFu, (uw[cr >> 2] >> (8 * (cr & 3))) & 0xFFu, (vw[cr >> 2] >> (8 * (cr & 3))) & 0xFFu, px);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c][rr] = t_add(t_mul(px[c], nm.mul[c]), nm.add[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tensor_pack4<T>(o[c], &q[c][g * (4 / (R / 4))]);
+    }
+    GLB uint8_t *d = (GLB uint8_t *)J.dst + (size_t)i * (size_t)J.row_pitch + (size_t)k * 16u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tensor_store16(d + (size_t)c * (size_t)J.plane_pitch, q[c]);
+}
+
+/* source coordinate of output sample j along one axis: scale s = crop extent / output extent, n = crop extent */
+__device__ __forceinline__ void tensor_tap(int j, float s, int n, int &a, int &b, float &l)
+{
+    const float f = __builtin_fmaxf(t_sub(t_mul(t_add((float)j, 0.5f), s), 0.5f), 0.f);
+    a = min((int)__builtin_floorf(f), n - 1);
+    b = min(a + 1, n - 1);
+    l = t_sub(f, (float)a);
+}
+
+/* the general body: four taps per output sample, read through the caches a byte at a time (neighbouring lanes and the two
+ * rows share lines; nothing to stage).  No barriers; every lane past the picture exits. */
+template <typename T, bool VEC>
+__device__ __forceinline__ void tensor_general(const HvqTensorJob &J, int idx, const HvqTensorNorm &nm)
+{
+    constexpr int R = tensor_run<T>::R;
+    const int runs = (J.out_w + R - 1) / R;
+    if (idx >= runs * J.out_h) return;
+    const int i = idx / runs, k = idx - i * runs;
+    const int ws = J.wshift, hs = J.hshift, w = J.w, cwid = w >> ws;
+    int ya, yb;
+    float ly;
+    tensor_tap(i, J.sy, J.ch, ya, yb, ly);
+    ya += J.y0; yb += J.y0;
+    const GLB uint8_t *py = (const GLB uint8_t *)J.y, *pu = (const GLB uint8_t *)J.u, *pv = (const GLB uint8_t *)J.v;
+    const size_t yrow[2] = { (size_t)ya * w, (size_t)yb * w };
+    const size_t crow[2] = { (size_t)(ya >> hs) * cwid, (size_t)(yb >> hs) * cwid };
+    const float my = t_sub(1.0f, ly);
+    GLB uint8_t *d = (GLB uint8_t *)J.dst + (size_t)i * (size_t)J.row_pitch + (size_t)k * 16u;
+    const size_t pp = (size_t)J.plane_pitch;
+    u32 q[3][4];
+    /* four samples at a time (two rounds for the 16-bit types, not unrolled: 48 byte loads in flight per lane are plenty and
+     * twice as many cost the streaming body, which shares the kernel's register count, half its waves) */
+#pragma unroll 1
+    for (int g = 0; g < R / 4; ++g) {
+        float o[3][4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int j = min(k * R + 4 * g + rr, J.out_w - 1);  /* a ragged run computes its last sample again and does not store it */
+            int xa, xb;
+            float lx;
+            tensor_tap(j, J.sx, J.cw, xa, xb, lx);
+            xa += J.x0; xb += J.x0;
+            const float mx = t_sub(1.0f, lx);
+            const int xs[2] = { xa, xb }, cs[2] = { xa >> ws, xb >> ws };
+            float p[2][2][3];                                /* [row][column][channel] */
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+                    tensor_rgb(py[yrow[a] + xs[b]], pu[crow[a] + cs[b]], pv[crow[a] + cs[b]], p[a][b]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float t = t_add(t_mul(p[0][0][c], mx), t_mul(p[0][1][c], lx));
+                const float bt = t_add(t_mul(p[1][0][c], mx), t_mul(p[1][1][c], lx));
+                const float v = t_add(t_mul(t, my), t_mul(bt, ly));
+                o[c][rr] = t_add(t_mul(v, nm.mul[c]), nm.add[c]);
+            }
+        }
+        if (VEC) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                u32 t[4];
+                tensor_pack4<T>(o[c], t);
+                if (sizeof(T) == 4) { q[c][0] = t[0]; q[c][1] = t[1]; q[c][2] = t[2]; q[c][3] = t[3]; }
+                else if (g == 0) { q[c][0] = t[0]; q[c][1] = t[1]; }
+                else { q[c][2] = t[0]; q[c][3] = t[1]; }
+            }
+        } else {
+            /* destinations aligned to their element size only, ragged row ends: element stores */
+            const int n = J.out_w - (k * R + 4 * g);             /* samples left in the row from this group on */
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    if (rr >= n) break;
+                    GLB uint8_t *e = d + (size_t)c * pp + (size_t)(4 * g + rr) * sizeof(T);
+                    if (sizeof(T) == 4) *(GLB u32 *)e = tensor_bits<T>(o[c][rr]);
+                    else *(GLB uint16_t *)e = (uint16_t)tensor_bits<T>(o[c][rr]);
+                }
+        }
+    }
+    if (VEC) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tensor_store16(d + (size_t)c * pp, q[c]);
+    }
+}
+
+/* one picture per grid row; the job's flags pick the body (uniform per workgroup), so one launch takes any mix of geometries,
+ * samplings, crops and output sizes */
+template <typename T>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+void hvq_yuv_tensor_kernel(const HvqTensorJob *__restrict__ jobs, HvqTensorNorm nm)
+{
+    const HvqTensorJob J = jobs[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (J.flags & HVQ_TJ_IDENT) {
+        if (J.wshift) tensor_ident<T, 1>(J, idx, nm);
+        else tensor_ident<T, 0>(J, idx, nm);
+    } else if (J.flags & HVQ_TJ_VEC) tensor_general<T, true>(J, idx, nm);
+    else tensor_general<T, false>(J, idx, nm);
+}
+
+/* jobs_dev: HvqTensorJob[njobs] in device memory; max_lanes = max over jobs of ceil(out_w / R) * out_h, R = 16 / element size */
+extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max_lanes, int dtype, const HvqTensorNorm *nm, hipStream_t stream)
+{
+    if (njobs <= 0 || max_lanes <= 0) return hipSuccess;
+    const HvqTensorJob *j = (const HvqTensorJob *)jobs_dev;
+    const dim3 grid((max_lanes + 255) / 256, njobs), block(256);
+    if (dtype == HVQ_T_F32) hvq_yuv_tensor_kernel<float><<<grid, block, 0, stream>>>(j, *nm);
+    else if (dtype == HVQ_T_F16) hvq_yuv_tensor_kernel<_Float16><<<grid, block, 0, stream>>>(j, *nm);
+    else if (dtype == HVQ_T_BF16) hvq_yuv_tensor_kernel<hvq_bf16><<<grid, block, 0, stream>>>(j, *nm);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 /* bulk readback (hvq_read_pictures): `n` resident pictures gathered into one contiguous staging buffer, so that the copy to the
  * host is one large transfer instead of `n` small ones */
 __global__ __launch_bounds__(256)

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +63,7 @@ extern "C" hipError_t hvq_launch_table_div(uint32_t *out_dev, hipStream_t stream
 extern "C" void hvq_set_stamps(unsigned long long *p);
 #endif
 extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, int format, hipStream_t stream);
+extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max_lanes, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -261,9 +263,9 @@ struct HvqContext {
     size_t rgb_cap = 0;
     HvqRgbJob *rgb_jobs_dev = nullptr;
     size_t rgb_jobs_cap = 0;
-    /* hvq_export_pictures: job tables in a ring, each reused once the export that read it has finished (its event); the newest
+    /* hvq_export_pictures / hvq_export_tensors: job tables in a ring, each reused once the export that read it has finished (its event); the newest
      * export's event orders the next export and every later slot writer (export_fence) */
-    struct ExportTab { uint8_t *host = nullptr; HvqRgbJob *dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } ex[4];
+    struct ExportTab { uint8_t *host = nullptr; uint8_t *dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } ex[4];
     int ex_next = 0, ex_last = -1;     /* table of the next export; of the newest one (-1: none yet) */
     bool ex_unfenced = false;          /* an export was queued since c->stream last waited for one */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
@@ -2223,18 +2225,56 @@ HVQ_EXPORT int hvq_picture_device_ptr(HvqContext *c, int sid, int ordinal, const
     return rc;
 }
 
+/* What the two exports share, first half: the batch in flight is ended only when a requested picture belongs to it (as
+ * hvq_read_pictures) */
+static int export_begin(HvqContext *c, int n, const int *streams, const int *ordinals)
+{
+    HIPCHK(hipSetDevice(c->device));
+    bool need_end = false;
+    for (int i = 0; i < n && !need_end; ++i)
+        if (streams[i] >= 0 && streams[i] < (int)c->streams.size() && ordinals[i] >= c->streams[(size_t)streams[i]].inflight_from) need_end = true;
+    return need_end ? flush_end(c) : HVQ_OK;
+}
+
+/* ... second half, once everything is checked: from here on the call enqueues.  The job table the export K calls ago used is free
+ * once that export has run (a host wait only when K exports are still queued); `launch(table in device memory, stream)` queues the
+ * kernel behind the table's upload, the reconstruction of every flushed picture and the previous export */
+template <class Launch>
+static int export_enqueue(HvqContext *c, const void *jobs, size_t bytes, void *hip_stream, Launch launch)
+{
+    HvqContext::ExportTab &T = c->ex[c->ex_next];
+    if (!T.ev) HIPCHK(hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
+    else if (T.used) HIPCHK(hipEventSynchronize(T.ev));
+    if (bytes > T.cap) {                                      /* bytes: a multiple of 16, hvq_launch_upload copies whole 16-byte units */
+        if (T.host) { HIPCHK(hipHostFree(T.host)); T.host = nullptr; }
+        if (T.dev) { HIPCHK(hipFree(T.dev)); T.dev = nullptr; }
+        T.cap = 0;
+        const size_t ncap = align_up(bytes * 2, 4096);
+        HIPCHK(hipHostMalloc((void **)&T.host, ncap, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&T.dev, ncap));
+        T.cap = ncap;
+    }
+    memcpy(T.host, jobs, bytes);
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(hipStreamWaitEvent(st, c->ev_read, 0));                          /* every flushed picture is reconstructed */
+    if (c->ex_last >= 0) HIPCHK(hipStreamWaitEvent(st, c->ex[c->ex_last].ev, 0));   /* chained: the newest export covers all */
+    HIPCHK(hvq_launch_upload(T.host, T.dev, bytes, st));
+    HIPCHK(launch((const void *)T.dev, st));
+    HIPCHK(hipEventRecord(T.ev, st));
+    T.used = true;
+    c->ex_last = c->ex_next;
+    c->ex_next = (c->ex_next + 1) % (int)(sizeof c->ex / sizeof c->ex[0]);
+    c->ex_unfenced = true;
+    return HVQ_OK;
+}
+
 HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, int format,
                                    const HvqExportDst *dst, void *hip_stream)
 {
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
     if (format != HVQ_FMT_RGB24 && format != HVQ_FMT_RGBP && format != HVQ_FMT_YUV444P) return fail(HVQ_E_ARG, "bad format %d", format);
     if (!n) return HVQ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    /* as hvq_read_pictures: the batch in flight is ended only when a requested picture belongs to it */
-    bool need_end = false;
-    for (int i = 0; i < n && !need_end; ++i)
-        if (streams[i] >= 0 && streams[i] < (int)c->streams.size() && ordinals[i] >= c->streams[(size_t)streams[i]].inflight_from) need_end = true;
-    if (need_end) { int rc = flush_end(c); if (rc) return rc; }
+    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
     std::vector<HvqRgbJob> jobs((size_t)n);
     int max_lanes = 0, wide = 1;
     for (int i = 0; i < n; ++i) {
@@ -2257,33 +2297,68 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
         if (s.w % 16) wide = 0;
         max_lanes = std::max(max_lanes, (s.w >> 2) * s.h);
     }
-    /* everything is checked: from here on the call enqueues.  The job table the export K calls ago used is free once that export
-     * has run (a host wait only when K exports are still queued) */
-    HvqContext::ExportTab &T = c->ex[c->ex_next];
-    if (!T.ev) HIPCHK(hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
-    else if (T.used) HIPCHK(hipEventSynchronize(T.ev));
-    const size_t bytes = (size_t)n * sizeof(HvqRgbJob);       /* a multiple of 16: hvq_launch_upload copies whole 16-byte units */
-    if (bytes > T.cap) {
-        if (T.host) { HIPCHK(hipHostFree(T.host)); T.host = nullptr; }
-        if (T.dev) { HIPCHK(hipFree(T.dev)); T.dev = nullptr; }
-        T.cap = 0;
-        const size_t ncap = align_up(bytes * 2, 4096);
-        HIPCHK(hipHostMalloc((void **)&T.host, ncap, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&T.dev, ncap));
-        T.cap = ncap;
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqRgbJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_rgb(tab, n, max_lanes, wide, format, st); });
+}
+
+HVQ_EXPORT int hvq_export_tensors(HvqContext *c, int n, const int *streams, const int *ordinals, int dtype,
+                                  const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream)
+{
+    static_assert(sizeof(HvqTensorJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+    if (!c || n < 0 || !mul || !add || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    if (dtype != HVQ_T_F32 && dtype != HVQ_T_F16 && dtype != HVQ_T_BF16) return fail(HVQ_E_ARG, "bad dtype %d", dtype);
+    HvqTensorNorm nm;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(mul[k]) || !std::isfinite(add[k])) return fail(HVQ_E_ARG, "mul / add of channel %d is not finite", k);
+        nm.mul[k] = mul[k]; nm.add[k] = add[k];
     }
-    memcpy(T.host, jobs.data(), bytes);
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(hipStreamWaitEvent(st, c->ev_read, 0));                          /* every flushed picture is reconstructed */
-    if (c->ex_last >= 0) HIPCHK(hipStreamWaitEvent(st, c->ex[c->ex_last].ev, 0));   /* chained: the newest export covers all */
-    HIPCHK(hvq_launch_upload(T.host, T.dev, bytes, st));
-    HIPCHK(hvq_launch_rgb(T.dev, n, max_lanes, wide, format, st));
-    HIPCHK(hipEventRecord(T.ev, st));
-    T.used = true;
-    c->ex_last = c->ex_next;
-    c->ex_next = (c->ex_next + 1) % (int)(sizeof c->ex / sizeof c->ex[0]);
-    c->ex_unfenced = true;
-    return HVQ_OK;
+    if (!n) return HVQ_OK;
+    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
+    const int64_t es = dtype == HVQ_T_F32 ? 4 : 2;
+    const int run = (int)(16 / es);                          /* output samples of a row per lane */
+    std::vector<HvqTensorJob> jobs((size_t)n);
+    int max_lanes = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!src) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const HvqTensorDst &d = dst[i];
+        if (!d.ptr) return fail(HVQ_E_ARG, "null destination %d", i);
+        if (d.out_w < 1 || d.out_h < 1 || d.out_w > 16384 || d.out_h > 16384)
+            return fail(HVQ_E_ARG, "destination %d: output size %d x %d outside [1, 16384]", i, d.out_w, d.out_h);
+        int x0 = 0, y0 = 0, cw = s.w, ch = s.h;
+        if (d.crop_w) { x0 = d.crop_x; y0 = d.crop_y; cw = d.crop_w; ch = d.crop_h; }
+        else if (d.crop_x || d.crop_y || d.crop_h) return fail(HVQ_E_ARG, "destination %d: crop_w == 0 takes the whole picture, the other crop fields must be 0", i);
+        if (x0 < 0 || y0 < 0 || cw < 1 || ch < 1 || (int64_t)x0 + cw > s.w || (int64_t)y0 + ch > s.h)
+            return fail(HVQ_E_ARG, "destination %d: crop (%d, %d, %d, %d) is empty or leaves the %d x %d picture", i, x0, y0, cw, ch, s.w, s.h);
+        const int64_t dense = (int64_t)d.out_w * es;
+        const int64_t rp = d.row_pitch ? d.row_pitch : dense;
+        const int64_t pp = d.plane_pitch ? d.plane_pitch : rp * d.out_h;
+        if (rp < dense || rp > ((int64_t)1 << 40) || d.plane_pitch > ((int64_t)1 << 48))
+            return fail(HVQ_E_ARG, "destination %d: row pitch %lld outside [%lld, 2^40] or plane pitch above 2^48", i, (long long)rp, (long long)dense);
+        if (pp < rp * d.out_h)
+            return fail(HVQ_E_ARG, "destination %d: plane pitch %lld below row pitch x height %lld (planes overlap)", i, (long long)pp, (long long)(rp * d.out_h));
+        const uint64_t bits = (uint64_t)(uintptr_t)d.ptr | (uint64_t)rp | (uint64_t)pp;
+        if (bits & (uint64_t)(es - 1))
+            return fail(HVQ_E_ARG, "destination %d: pointer, row pitch and plane pitch must be multiples of the element size %d", i, (int)es);
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        HvqTensorJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.y = src; j.u = src + ny; j.v = src + ny + nc;
+        j.dst = (uint8_t *)d.ptr; j.row_pitch = rp; j.plane_pitch = pp;
+        j.w = s.w; j.h = s.h; j.wshift = s.wshift; j.hshift = s.hshift;
+        j.x0 = x0; j.y0 = y0; j.cw = cw; j.ch = ch; j.out_w = d.out_w; j.out_h = d.out_h;
+        j.sx = (float)cw / (float)d.out_w;                   /* divided here: the device divides nothing */
+        j.sy = (float)ch / (float)d.out_h;
+        if (!(bits & 15u) && d.out_w % run == 0) {
+            j.flags |= HVQ_TJ_VEC;
+            if (d.out_w == cw && d.out_h == ch && x0 % run == 0 && s.w % run == 0) j.flags |= HVQ_TJ_IDENT;
+        }
+        max_lanes = std::max(max_lanes, (d.out_w + run - 1) / run * d.out_h);
+    }
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqTensorJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_tensor(tab, n, max_lanes, dtype, &nm, st); });
 }
 
 HVQ_EXPORT int hvq_rgb_bench(HvqContext *c, int reps, float *gpu_ms, uint64_t *bytes_per_rep, uint32_t *pictures)

@@ -201,6 +201,35 @@ typedef struct HvqExportDst { void *ptr; int64_t row_pitch, plane_pitch; } HvqEx
 int  hvq_export_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, int format,
                          const HvqExportDst *dst, void *hip_stream);
 
+/* Export of resident pictures as the float tensors a network eats: crop, bilinear resize, per-channel normalisation and the
+ * conversion to float32 / float16 / bfloat16, planar RGB (CHW: three planes of out_h rows of out_w elements), in ONE kernel launch
+ * for any mix of streams, crops and output sizes.  Lookup, HVQ_E_STATE cases, ordering and slot safety are hvq_export_pictures'
+ * (the two kinds of export share one chain: each waits for the previous export of either kind).
+ *   Arithmetic, all single precision with one rounding per operation (never fused):
+ *   source   P_c(y, x), 0 <= y < crop_h, 0 <= x < crop_w: the uint8 HVQ_FMT_RGBP sample at luma position (crop_y + y, crop_x + x),
+ *            as a float (crop offsets may be odd: the chroma index rule above takes care of them);
+ *   columns  sx = (float)crop_w / (float)out_w;  fx = max((j + 0.5f) * sx - 0.5f, 0);  xa = min((int)floorf(fx), crop_w - 1);
+ *            xb = min(xa + 1, crop_w - 1);  lx = fx - (float)xa;  rows likewise with sy, out_h, crop_h -> ya, yb, ly
+ *            (half-sample centres, taps clamped to the crop: bilinear "crop, then resize" without antialiasing);
+ *   blend    t = P(ya,xa) * (1 - lx) + P(ya,xb) * lx;  b = P(yb,xa) * (1 - lx) + P(yb,xb) * lx;  v = t * (1 - ly) + b * ly;
+ *   output   o = v * mul[c] + add[c], c = R, G, B; the 16-bit types are rounded to nearest even from o.
+ *   With out size == crop size the blend is the identity (v == P exactly) and the kernel streams.
+ *   dst[i]: pitches in bytes, 0 = dense (out_w * element size; row_pitch * out_h); crop_w == 0 (with crop_x, crop_y, crop_h 0)
+ *   takes the whole picture.  HVQ_E_ARG for a bad dtype, null pointer, non-finite mul / add, out_w or out_h outside [1, 16384], a
+ *   crop that is empty or leaves the picture, pitches below dense, overlapping planes, or a pointer or pitch that is not a
+ *   multiple of the element size.  16-byte stores are used when ptr and the pitches are multiples of 16 and out_w is a multiple of
+ *   16 / element size; the values do not depend on it. */
+#define HVQ_T_F32   0
+#define HVQ_T_F16   1
+#define HVQ_T_BF16  2
+typedef struct HvqTensorDst {
+    void *ptr; int64_t row_pitch, plane_pitch;      /* bytes; 0 = dense */
+    int32_t out_w, out_h;
+    int32_t crop_x, crop_y, crop_w, crop_h;         /* luma samples; crop_w == 0: the whole picture */
+} HvqTensorDst;
+int  hvq_export_tensors(HvqContext *ctx, int n, const int *streams, const int *ordinals, int dtype,
+                        const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
