@@ -11,8 +11,8 @@
  *   hvq_recon_inline_kernel   per dependency level, the default: descriptors (map, vectors, payload pool) -> block records, item
  *                      queue and pair list in registers and LDS -> flat / weighted-DC / motion-compensated blocks by the owning
  *                      lane, pairs -> nest or window gather, gain, 16 products -> LDS accumulators (ds_add), items -> samples;
- *                      the tile is assembled in LDS and leaves as 16-byte row segments (every store instruction of a wave
- *                      writes four complete 256-byte runs, every output line reaches HBM once and whole)
+ *                      a finished block stays in the registers of its owner lane (an item's block passes through one LDS column) and
+ *                      leaves as four row stores (every store instruction of a wave writes one contiguous 256-byte run)
  *   hvq_selfref_kernel P pictures with future-referencing macroblocks: the reference's raster-order walk
  *   hvq_yuv_rgb_kernel, hvq_gather_kernel      display epilogue and picture export, bulk readback
  *   - sample arithmetic is SIMD-within-register: v_lerp_u8 for the 2-tap and 4-tap half-sample filters, 16-bit packed math for
@@ -256,15 +256,6 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 v)
 __device__ __forceinline__ u32 lanes_below(unsigned long long mask)
 {
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
-}
-
-__device__ __forceinline__ void block_coords(u32 b, i32 hb, float rhb, i32 &bx, i32 &by)
-{
-    i32 q = (i32)((float)b * rhb);                 /* b < 2^22: estimate within +-1, fixed below without branches */
-    i32 r = (i32)b - q * hb;
-    const i32 lo = r < 0 ? 1 : 0, hi = r >= hb ? 1 : 0;
-    by = q - lo + hi;
-    bx = r + (lo - hi) * hb;
 }
 
 #define HVQ_NW (HVQ_WG / 64)
@@ -531,7 +522,7 @@ __device__ __forceinline__ void window_finish(const uint64_t q[4], bool x2, u32 
  *   - payload offset, intra pair count and MC-residual pair count come out of ONE packed wave scan instead of two;
  *   - the pair list is written by a short unrolled sequence of predicated stores at ascending addresses instead of a loop
  *     with a bounds test per entry;
- *   - phase C re-derives its rows' coordinates the same way.
+ *   - phase C stores from the owner lanes' registers at the offset trip 2 derived (round 7; an LDS tile carried the blocks before).
  *
  *   trip 1  the picture's job record (scalar): its common part, then -- round 6 -- the workgroup's ONE plane record by a dependent load
  *   trip 2  per block: map entry with both horizontal neighbours (one unaligned 8-byte load), the vertical neighbours, the
@@ -541,7 +532,7 @@ __device__ __forceinline__ void window_finish(const uint64_t q[4], bool x2, u32 
  *           accumulator rows from the bottom, MC-residual items from the top: no total is needed before a slot can be handed out)
  *   trip 3  motion-compensation rows
  *   barrier 1, phase B1 (lane = pair: basis dword from LDS, decoded here, nest rows from LDS or window rows from the
- *   reference), barrier 2, phase B2 (lane = item), barrier 3, phase C (16-byte row segments, complete 256-byte runs).
+ *   reference), barrier 2, phase B2 (lane = item), barrier 3, phase C (lane = block: four row stores, 256-byte runs per wave).
  */
 template <int CTX>   /* 0 I-picture luma (kind = the whole type byte, h4m:1093), 1 I-picture chroma, 2 P/B picture */
 __device__ __forceinline__ void inl_classify(u32 T, bool valid, u32 &cls, u32 &nb, u32 &npay, bool &lit, bool &mc, bool &wdc, bool &flat)
@@ -566,18 +557,43 @@ __device__ __forceinline__ void inl_classify(u32 T, bool valid, u32 &cls, u32 &n
 template <int N> struct InlCtx { static constexpr int value = N; };
 #define HVQ_W64(i) ((uint64_t)cw[i] | ((uint64_t)cw[(i) + 1] << 32))
 
+/* Static LDS of the kernel, ONE set of sizes for its arrays and for what the host is told (hvq_recon_inline_static_lds): the packed nest
+ * padded to 16 bytes, then per item 16 accumulator dwords, the 4 dwords of its block (s_res) and 3 record dwords, then the slot counter
+ * (padded to 16).  No part depends on the tiles per workgroup: finished blocks stay in the registers of their owner lanes. */
+constexpr u32 HVQ_INL_NEST_LDS = (HVQ_NESTP_BYTES + 8 + 15) / 16 * 16;
+constexpr u32 HVQ_INL_ACC_DW = 16, HVQ_INL_RES_DW = 4, HVQ_INL_REC_DW = 3;
+constexpr u32 HVQ_INL_CTR_LDS = 16;
+constexpr u32 hvq_inl_static_lds(u32 items_cap)
+{
+    return HVQ_INL_NEST_LDS + 4u * (HVQ_INL_ACC_DW + HVQ_INL_RES_DW + HVQ_INL_REC_DW) * items_cap + HVQ_INL_CTR_LDS;
+}
+/* Two kernels from one template: the one-tile instantiations and the small two-tile ones (sparse streams, eight workgroups per CU by LDS)
+ * are allocated for eight waves per SIMD -- 64 vector and 80 scalar registers, above which a CU takes seven workgroups whatever the
+ * compiler reports (hazard 7).  Two tiles with accumulators for 128 items and more never fit eight times into a CU's LDS:
+ * they are allocated for the seven they can reach (72 vector registers, and the scalar registers that carried 36 spills at 80). */
+#ifndef HVQ_SEVEN_WG_CAP
+#define HVQ_SEVEN_WG_CAP 128
+#endif
+constexpr int hvq_inl_waves(int tpw, int items_cap) { return (tpw >= 2 && items_cap >= HVQ_SEVEN_WG_CAP) ? 7 : HVQ_MIN_WAVES; }
+template <int ITEMS_CAP, int TPW> struct InlWaves { static constexpr int value = hvq_inl_waves(TPW, ITEMS_CAP); };
+
 template <int ITEMS_CAP, int TPW>
-__global__ __launch_bounds__(HVQ_WG, HVQ_MIN_WAVES)
+__global__ __launch_bounds__(HVQ_WG, (InlWaves<ITEMS_CAP, TPW>::value))
 void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 pool_cap HVQ_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) u32 s_dyn[];       /* [pair_cap] item | pool index << 9, then [pool_cap] staged pool dwords */
-    __shared__ __attribute__((aligned(16))) uint8_t s_nest[HVQ_NESTP_BYTES + 8];
-    __shared__ __attribute__((aligned(16))) u32 s_out[TPW][4][HVQ_WG];
-    __shared__ __attribute__((aligned(16))) u32 s_acc[16 * ITEMS_CAP];
+    __shared__ __attribute__((aligned(16))) uint8_t s_nest[HVQ_INL_NEST_LDS];
+    __shared__ __attribute__((aligned(16))) u32 s_acc[HVQ_INL_ACC_DW * ITEMS_CAP];
+    /* an item's block, one column per item: the owner of an MC-residual item leaves its motion-compensated block here (phase A), the item
+     * lane reads it, and writes the finished block of either kind of item back (phase B2); the owner takes it behind barrier 3.  Only
+     * those two lanes ever touch a column, the owner before barrier 1 and after barrier 3, the item lane between barriers 2 and 3. */
+    __shared__ __attribute__((aligned(16))) u32 s_res[HVQ_INL_RES_DW * ITEMS_CAP];
     __shared__ u32 s_item0[ITEMS_CAP];   /* owner (tile of the workgroup * 256 + lane) | map entry << 10 */
     __shared__ u32 s_item1[ITEMS_CAP];   /* pool index of the block's payload */
     __shared__ u32 s_item2[ITEMS_CAP];   /* MC-residual items: the macroblock vector (the pair lanes derive the origin of the 70x38 window from it, h4m:1865-1868) */
-    __shared__ unsigned long long s_ctr64;   /* intra items | MC-residual items << 10 | intra pairs << 20 | MC-residual pairs << 42 handed out */
+    __shared__ __attribute__((aligned(16))) unsigned long long s_ctr64;   /* intra items | MC-residual items << 10 | intra pairs << 20 | MC-residual pairs << 42 handed out */
+    static_assert(sizeof(s_nest) + sizeof(s_acc) + sizeof(s_res) + sizeof(s_item0) + sizeof(s_item1) + sizeof(s_item2) + HVQ_INL_CTR_LDS == hvq_inl_static_lds(ITEMS_CAP)
+                  && ITEMS_CAP % 4 == 0 && sizeof(s_ctr64) <= HVQ_INL_CTR_LDS, "the host sizes launches by hvq_inl_static_lds");
     u32 *const s_pair = s_dyn;
     u32 *const s_pool = s_dyn + pair_cap;
 
@@ -699,6 +715,10 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
     u32 bx[TPW], by[TPW];
     uint64_t row8[TPW];
     u32 nt[TPW], nbt[TPW], mvw[TPW];
+    /* what a lane keeps to the end: its block (four packed rows), where that goes in the plane (~0: no block), and the item column its
+     * finished block comes from when an item lane completes it (~0: the lane completes it itself) */
+    Blk blk[TPW];
+    u32 doff[TPW], rslot[TPW];
 #pragma unroll
     for (int h = 0; h < TPW; ++h) {
         /* A wave's 64 blocks are consecutive in raster order: the first one is split into (row, column) on the SCALAR unit --
@@ -719,6 +739,7 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
         if (hb >= 64u) q = t >= hb ? 1u : 0u;
         else q = __umul24(t, magic16) >> 16;
         bx[h] = t - __umul24(q, hb); by[h] = by0 + q;
+        doff[h] = valid[h] ? __umul24(by[h] << 2, pw) + (bx[h] << 2) : 0xFFFFFFFFu;      /* sample row 4 by < 2^16, pw < 2^14 */
         /* entry (by, bx) of the bordered map = b + 2 by + hb + 3 */
         const GLB uint8_t *mw = map + 2u * (size_t)(bws + 2u * by0 + hb + 3u);
         const u32 vo2 = 2u * (l + 2u * q);
@@ -891,6 +912,7 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
                 slotq[h] = b1 + lanes_below(m1[h]);
                 pstart[h] = bp1 + pinI[h] - nb[h];
             }
+            rslot[h] = cls[h] && slotq[h] < (u32)ITEMS_CAP ? slotq[h] : 0xFFFFFFFFu;
         }
         /* accumulators zeroed: 16 * ITEMS_CAP dwords, ITEMS_CAP a multiple of 32 */
         {
@@ -946,9 +968,14 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
             } else if (flatb[h]) {
                 const u32 v = (u32)V * 0x01010101u;
                 o.r[0] = o.r[1] = o.r[2] = o.r[3] = v;
-            } else continue;
+            } else {
+                o.r[0] = o.r[1] = o.r[2] = o.r[3] = 0;                         /* an intra item or a literal block: filled below */
+            }
+            blk[h] = o;
+            if (CTX == 2 && cls[h] == 2 && rslot[h] != 0xFFFFFFFFu) {          /* MC residual: the item lane adds to the MC block */
 #pragma unroll
-            for (int y = 0; y < 4; ++y) s_out[h][y][tid] = o.r[y];
+                for (int y = 0; y < 4; ++y) s_res[y * ITEMS_CAP + (int)rslot[h]] = o.r[y];
+            }
         }
         STAMP(7, 0);                                                           /* phase A */
         /* the nest and the pool range were staged by LDS-DMA (global_load_lds), which completes on the VECTOR-memory counter: s_barrier
@@ -963,7 +990,7 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
         for (int h = 0; h < TPW; ++h)
             if (lit[h]) {
 #pragma unroll
-                for (int y = 0; y < 4; ++y) s_out[h][y][tid] = pool_at(off[h] + (u32)y);
+                for (int y = 0; y < 4; ++y) blk[h].r[y] = pool_at(off[h] + (u32)y);
             }
     };
     if (is_pb) front(InlCtx<2>{});
@@ -1056,80 +1083,94 @@ void hvq_recon_inline_kernel(const HvqJob *__restrict__ jobs, u32 pair_cap, u32 
                 it = v < nI ? v : (u32)ITEMS_CAP - 1u - (v - nI);
             }
             const u32 item = s_item0[it];
-            const u32 owner = item & 1023u, q16 = item >> 10;
+            const u32 q16 = item >> 10;
             const u32 poff = s_item1[it];
             u32 r[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) r[i] = s_acc[i * ITEMS_CAP + it];
-            u32 *so = &s_out[0][0][0] + (owner >> 8) * (4 * HVQ_WG) + (owner & 255u);
+            u32 *const so = s_res + it;                      /* the item's column */
             Blk o;
             if (HVQ_ABL == 32) {
                 o.r[0] = r[0] ^ poff; o.r[1] = r[5]; o.r[2] = r[10]; o.r[3] = r[15] ^ q16;
             } else if (item_mc) {
-                Blk m;                                       /* the owner left the MC block in the tile */
+                Blk m;                                       /* the owner left the MC block in the column */
 #pragma unroll
-                for (int y = 0; y < 4; ++y) m.r[y] = so[y * HVQ_WG];
+                for (int y = 0; y < 4; ++y) m.r[y] = so[y * ITEMS_CAP];
                 o = predi_finish(r, m, pool_at(poff), pool_at(poff + 1u), unk);
             } else {
                 o = intra_finish(r, (i32)(q16 & 0xFF), unk);
             }
 #pragma unroll
-            for (int y = 0; y < 4; ++y) so[y * HVQ_WG] = o.r[y];
+            for (int y = 0; y < 4; ++y) so[y * ITEMS_CAP] = o.r[y];
         }
     }
     STAMP(11, 0);                                                              /* item phase */
 #if HVQ_PRIO == 3
     __builtin_amdgcn_s_setprio(3);                                             /* 3: the stores of a finished tile go first */
 #endif
-    __syncthreads();                                                           /* barrier 3: tiles complete in LDS */
+    __syncthreads();                                                           /* barrier 3: the items' blocks complete in LDS */
     STAMP(12, 0);
 
-    /* ---- phase C: tiles -> HBM ---- */
-    if ((HVQ_ABL == 35 || HVQ_ABL == 37) && s_out[0][0][tid] != 0x12345678u) return;
-    /* The wave's first block is split into (row, column) AGAIN here, on the scalar unit (six instructions), from copies of b0, hb and
-     * nblocks the compiler cannot connect with the head's: what trip 2 derived -- per tile the two coordinates and three 64-bit lane
-     * masks -- would otherwise stay in scalar registers from the head to this point, the kernel sits at its cap of 80 (above it a CU
-     * takes seven workgroups, not eight), and the surplus went to vector-register lanes: 7 (one tile) / 59 (two tiles) v_writelane and
-     * as many and more v_readlane per wave, each a vector instruction in a kernel bound by those. */
-    u32 b0c = b0, hbc = hb, nbc = nblocks;
-    asm volatile("" : "+s"(b0c), "+s"(hbc), "+s"(nbc));
+    /* ---- phase C: blocks -> HBM, from the registers of their owner lanes ---- */
+#pragma unroll
+    for (int h = 0; h < TPW; ++h)
+        if (rslot[h] != 0xFFFFFFFFu) {
+#pragma unroll
+            for (int y = 0; y < 4; ++y) blk[h].r[y] = s_res[y * ITEMS_CAP + (int)rslot[h]];
+        }
+    if ((HVQ_ABL == 35 || HVQ_ABL == 37) && blk[0].r[0] != 0x12345678u) return;
+    /* Store instructions are issued at a fixed rate whatever their width.  The instantiations of the sparse levels (little arithmetic
+     * beside the stores: flat -1 % with four 4-byte stores per block) turn rows that are multiples of four blocks into 16-byte pieces
+     * first: each wave passes its 64 blocks through 1 KB of its own in the accumulators, which nobody reads any more -- lane (g, r) then
+     * holds sample row r of blocks 4g .. 4g + 3 (one map row, all of them valid or none) and takes their offset from lane 4g.  No
+     * s_barrier: a wave's LDS operations complete in order, and a wave barrier (no instruction) keeps the compiler from moving the
+     * accesses of other lanes' dwords across each other.  On the dense levels the four LDS writes and the read cost more than three stores
+     * (dense -0.4 %, profiles/r07_two_tiles_dense.txt): their instantiations store rows from registers whatever the row length. */
+    constexpr bool WIDE = ITEMS_CAP < HVQ_SEVEN_WG_CAP;
+    static_assert(!WIDE || HVQ_INL_ACC_DW * ITEMS_CAP >= 4 * HVQ_WG, "a wave's 64 blocks of 16 bytes pass through the accumulators");
+    if (WIDE && (hb & 3u) == 0) {
+        auto wave_sync = [] {                                                  /* orders the wave's own LDS accesses for the compiler: no instruction */
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        };
+        u32 *const tw = s_acc + wave * 256u;
+        const u32 g4 = 4u * (lane & 15u), rr = lane >> 4;
+#pragma unroll
+        for (int h = 0; h < TPW; ++h) {
+#pragma unroll
+            for (int y = 0; y < 4; ++y) tw[y * 64 + (int)lane] = blk[h].r[y];
+            wave_sync();
+            const u32 d0 = (u32)__builtin_amdgcn_ds_bpermute((int)(g4 << 2), (int)doff[h]);
+            typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+            const u32x4 v = *(const u32x4 *)&tw[rr * 64u + g4];
+            wave_sync();                                                       /* the next tile's rows are written behind this read */
+            if (d0 == 0xFFFFFFFFu) continue;
+            const u32 a = d0 + __umul24(rr, pw);
+#if HVQ_NT_STORES
+            if (HVQ_NT_STORES == 2 || pic_kind == HVQ_PIC_B) asm volatile("global_store_dwordx4 %0, %1, %2 nt" :: "v"(a), "v"(v), "s"(plane) : "memory");
+            else
+#endif
+                *(GLB u32x4 *)(plane + (size_t)a) = v;
+        }
+    } else
+    /* the path of every row length: a lane stores the four rows of its block, a wave's 64 lanes one contiguous run of 256 bytes per
+     * sample row (wrapped at the ends of block rows) */
 #pragma unroll
     for (int h = 0; h < TPW; ++h) {
-        if (h >= ntl) continue;
-        const u32 bw = b0c + (u32)(h * HVQ_TILE_BLOCKS) + wave * 64u;
-        if ((hbc & 3u) == 0) {
-            /* lane (g, r): sample row r of blocks 4g .. 4g + 3 = 16 contiguous bytes of the plane (rows are multiples of 4 blocks) */
-            const u32 g4 = 4u * (lane & 15u), rr = lane >> 4;
-            const u32 gb = bw + g4;
-            if (gb < nbc) {
-                /* the row's four blocks lie in one map row (rows are multiples of 4 blocks, the wave's first block is one of 64) */
-                const u32 bws = bw < nbc ? bw : 0u;
-                u32 cy0 = __umulhi(bws, magic);
-                if ((i32)(bws - cy0 * hbc) < 0) cy0 -= 1u;
-                const u32 cx0 = bws - cy0 * hbc;
-                const u32 t = cx0 + g4;
-                u32 q;
-                if (hbc >= 64u) q = t >= hbc ? 1u : 0u;
-                else q = __umul24(t, magic16) >> 16;
-                const u32 gx = t - __umul24(q, hbc), gy = cy0 + q;
-                typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 v = *(const u32x4 *)&s_out[h][rr][wave * 64u + g4];
-                const u32 doff = (gy * 4u + rr) * pw + gx * 4u;
-                /* B pictures are never read again by a later picture: streaming stores keep them from displacing the anchors in L2.
-                 * Written as inline assembly: with __builtin_nontemporal_store on one side of the branch the compiler merges the two
-                 * stores into one and drops the hint (rounds 2-4 shipped without it, unnoticed: the ISA had no `nt`). */
+        if (doff[h] == 0xFFFFFFFFu) continue;
+        /* B pictures are never read again by a later picture: streaming stores keep them from displacing the anchors in L2.
+         * Written as inline assembly: with __builtin_nontemporal_store on one side of the branch the compiler merges the two
+         * stores into one and drops the hint (rounds 2-4 shipped without it, unnoticed: the ISA had no `nt`). */
 #if HVQ_NT_STORES
-                if (HVQ_NT_STORES == 2 || pic_kind == HVQ_PIC_B) asm volatile("global_store_dwordx4 %0, %1, %2 nt" :: "v"(doff), "v"(v), "s"(plane) : "memory");
-                else
-#endif
-                    *(GLB u32x4 *)(plane + (size_t)doff) = v;
-            }
-        } else if (bw + lane < nbc) {
-            i32 sx, sy;
-            block_coords(bw + lane, (i32)hbc, __builtin_amdgcn_rcpf((float)hbc), sx, sy);
-            GLB uint8_t *dst = plane + (size_t)(sy * 4) * pw + sx * 4;
+        if (HVQ_NT_STORES == 2 || pic_kind == HVQ_PIC_B) {
 #pragma unroll
-            for (int y = 0; y < 4; ++y) *(GLB u32 *)(dst + (size_t)y * pw) = s_out[h][y][tid];
+            for (int y = 0; y < 4; ++y) asm volatile("global_store_dword %0, %1, %2 nt" :: "v"(doff[h] + (u32)y * pw), "v"(blk[h].r[y]), "s"(plane) : "memory");
+        } else
+#endif
+        {
+#pragma unroll
+            for (int y = 0; y < 4; ++y) *(GLB u32 *)(plane + (size_t)(doff[h] + (u32)y * pw)) = blk[h].r[y];
         }
     }
     STAMP(13, 0);                                                              /* stores issued */
@@ -1151,15 +1192,22 @@ static void launch_recon_inline(const HvqJob *jobs_dev, uint32_t nslots, uint32_
 }
 
 /* dynamic LDS in bytes of a launch with these caps (as hvq_launch_recon_inline rounds them) */
-extern "C" uint32_t hvq_recon_inline_dyn_lds(uint32_t pair_cap, uint32_t pool_cap)
+extern "C" __attribute__((visibility("default"))) uint32_t hvq_recon_inline_dyn_lds(uint32_t pair_cap, uint32_t pool_cap)
 {
     return 4u * (((std::max(pair_cap, 1u) + 3u) & ~3u) + ((pool_cap + 3u) & ~3u));
 }
 
-/* static LDS of hvq_recon_inline_kernel<items_cap, tpw> (the host sizes the dynamic part against the CU's 160 KB) */
-extern "C" uint32_t hvq_recon_inline_static_lds(uint32_t tiles_per_wg, uint32_t items_cap)
+/* workgroups (of four waves, one per SIMD) a CU takes of hvq_recon_inline_kernel<items_cap, tpw> by its registers */
+extern "C" __attribute__((visibility("default"))) uint32_t hvq_recon_inline_max_wgs(uint32_t tiles_per_wg, uint32_t items_cap)
 {
-    return (uint32_t)(HVQ_NESTP_BYTES + 8 + 15) / 16u * 16u + tiles_per_wg * 4u * HVQ_WG * 4u + 64u * items_cap + 12u * items_cap + 16u;
+    return (uint32_t)hvq_inl_waves((int)tiles_per_wg, (int)std::min(items_cap, 512u));
+}
+
+/* static LDS of hvq_recon_inline_kernel<items_cap, tpw> (the host sizes the dynamic part against the CU's 160 KB) */
+extern "C" __attribute__((visibility("default"))) uint32_t hvq_recon_inline_static_lds(uint32_t tiles_per_wg, uint32_t items_cap)
+{
+    (void)tiles_per_wg;                                /* the blocks of both tiles stay in registers: nothing in LDS is per tile */
+    return hvq_inl_static_lds(items_cap);
 }
 
 /* One launch = one dependency level (of one launch queue).  jobs_dev: the launch's picture slots, one job each (count a multiple of 8 when
@@ -1175,17 +1223,17 @@ extern "C" hipError_t hvq_launch_recon_inline(const HvqJob *jobs_dev, uint32_t n
     pair_cap = (std::max(pair_cap, 1u) + 3u) & ~3u;
     pool_cap = (pool_cap + 3u) & ~3u;
     if (tiles_per_wg >= 2) {
-        if (items_cap <= 32) launch_recon_inline<32, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
-        else if (items_cap <= 64) launch_recon_inline<64, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
+        if (items_cap <= 64) launch_recon_inline<64, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 96) launch_recon_inline<96, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 128) launch_recon_inline<128, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
+        else if (items_cap <= 160) launch_recon_inline<160, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 192) launch_recon_inline<192, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
+        else if (items_cap <= 224) launch_recon_inline<224, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 256) launch_recon_inline<256, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 384) launch_recon_inline<384, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else launch_recon_inline<512, 2>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
     } else {
-        if (items_cap <= 32) launch_recon_inline<32, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
-        else if (items_cap <= 64) launch_recon_inline<64, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
+        if (items_cap <= 64) launch_recon_inline<64, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 96) launch_recon_inline<96, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 128) launch_recon_inline<128, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);
         else if (items_cap <= 192) launch_recon_inline<192, 1>(jobs_dev, nslots, max_wgs, pair_cap, pool_cap, stream);

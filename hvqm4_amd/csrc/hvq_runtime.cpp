@@ -54,6 +54,7 @@ extern "C" hipError_t hvq_launch_recon_inline(const HvqJob *jobs_dev, uint32_t n
                                               uint32_t items_cap, uint32_t pair_cap, uint32_t pool_cap, hipStream_t stream);
 extern "C" uint32_t hvq_recon_inline_static_lds(uint32_t tiles_per_wg, uint32_t items_cap);
 extern "C" uint32_t hvq_recon_inline_dyn_lds(uint32_t pair_cap, uint32_t pool_cap);
+extern "C" uint32_t hvq_recon_inline_max_wgs(uint32_t tiles_per_wg, uint32_t items_cap);
 extern "C" hipError_t hvq_launch_gather(const uint64_t *src_dev, uint8_t *dst_dev, uint32_t n, uint32_t pic_bytes, hipStream_t stream);
 extern "C" hipError_t hvq_launch_upload(const void *src_pinned, void *dst_dev, size_t bytes, hipStream_t stream);
 extern "C" hipError_t hvq_launch_selfref(const HvqJob *job_dev, const uint8_t *side, uint8_t *dst, hipStream_t stream);
@@ -66,6 +67,75 @@ extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_la
 extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max_lanes, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
+
+/* ---- LDS sizing of one launch of hvq_recon_inline_kernel (pure apart from the two environment caps HVQM4_AMD_PAIR_CAP and
+ * HVQM4_AMD_POOL_CAP, read once per process: hvq_flush_end calls it per launch, tests/test_recon_plan.py directly) ----
+ * The kernel keeps its item queue, pair list and the tile range of the pool in LDS: accumulator rows and a block column for the items of
+ * the launch's fullest tile (x tiles per workgroup), a pair list for its pairs, the staged pool for its bases, scalars and a few literal
+ * blocks.  A CU has 160 KB of LDS and takes 8 workgroups of 4 waves; the two-tile kernels with accumulators for 128 items and more are
+ * allocated for 7 (hvq_kernels.hip, InlWaves). */
+static const uint32_t HVQ_CU_LDS = 163840u;
+static const uint32_t HVQ_LIT_RESERVE = 128u;            /* staged-pool dwords per tile kept for literal blocks (4 dwords each) */
+
+HVQ_EXPORT uint32_t hvq_recon_inline_residency(uint32_t tpw, uint32_t items_cap, uint32_t lds_bytes)
+{
+    return std::min(hvq_recon_inline_max_wgs(tpw, items_cap), HVQ_CU_LDS / std::max(lds_bytes, 1u));
+}
+
+/* the shape of a launch with `t` tiles per workgroup whose fullest tile has `mi` items and `mp` pairs */
+static uint32_t inline_sized(uint32_t t, uint32_t mi, uint32_t mp, uint32_t *cap, uint32_t *pairs, uint32_t *pool)
+{
+    /* the kernel's instantiations (hvq_launch_recon_inline); 64 is the least: a wave's blocks pass through its accumulators on their way out */
+    static const uint32_t steps2[] = { 64, 96, 128, 160, 192, 224, 256, 384, 512 }, steps1[] = { 64, 96, 128, 192, 256 };
+    /* more pairs than the list holds: the items walk their bases (HVQM4_AMD_PAIR_CAP, tests: ordinary clips reach that path) */
+    static const uint32_t pair_lim = getenv("HVQM4_AMD_PAIR_CAP") ? (uint32_t)std::max(1, atoi(getenv("HVQM4_AMD_PAIR_CAP"))) : 4096u;
+    /* HVQM4_AMD_POOL_CAP (tests): a smaller staging area, so that ordinary clips reach the read-from-HBM path of tiles
+     * whose payload exceeds it */
+    static const uint32_t pool_lim = getenv("HVQM4_AMD_POOL_CAP") ? (uint32_t)std::max(0, atoi(getenv("HVQM4_AMD_POOL_CAP"))) : 1536u;
+    const uint32_t want = std::min(256u * t, std::max(64u, t * mi));
+    uint32_t ic = t == 2 ? 512u : 256u;
+    for (uint32_t v : steps2) if (t == 2 && v >= want) { ic = v; break; }
+    for (uint32_t v : steps1) if (t == 1 && v >= want) { ic = v; break; }
+    *cap = ic;
+    *pairs = std::max(1u, std::min(pair_lim, t * mp));
+    *pool = std::min(pool_lim, t * (mp + 2u * mi + HVQ_LIT_RESERVE));
+    const uint32_t reserve = *pool - std::min(*pool, t * (mp + 2u * mi));      /* what the limit left of the literal reserve */
+    if (*pool) *pool = (*pool + 4u + 3u) & ~3u;      /* + 4: the staged range starts at the 16-byte boundary below the tile's first dword */
+    uint32_t bytes = hvq_recon_inline_static_lds(t, ic) + hvq_recon_inline_dyn_lds(*pairs, *pool);
+    /* A launch that misses the next residency step by no more than the literal reserve its pool holds gives that much of it up -- never
+     * room for bases and scalars: a pool the limit has clipped below them has no reserve and is not trimmed.  Only the staged pool is
+     * ever trimmed: it is the one part that overflows gracefully (payload beyond it is read from HBM); a short pair list turns the tile
+     * serial, items beyond the cap are dropped. */
+    const uint32_t res = hvq_recon_inline_residency(t, ic, (bytes + 511u) & ~511u);
+    if (res < hvq_recon_inline_residency(t, ic, 1u)) {
+        const uint32_t target = HVQ_CU_LDS / (res + 1u) & ~511u;
+        const uint32_t cut = bytes > target ? (bytes - target + 15u) / 16u * 4u : 0u;      /* dwords, in the pool's 16-byte pieces */
+        if (cut && cut <= reserve) {
+            *pool -= cut;
+            bytes = hvq_recon_inline_static_lds(t, ic) + hvq_recon_inline_dyn_lds(*pairs, *pool);
+        }
+    }
+    return (bytes + 511u) & ~511u;
+}
+
+/* One or two tiles per workgroup, and the launch's LDS shape.  force_tpw: 0 = decide here, 1 / 2 = that many (HVQM4_AMD_TILES_PER_WG).
+ * lds_bytes: static + dynamic LDS of the launch, rounded up to 512. */
+HVQ_EXPORT void hvq_recon_inline_plan(uint32_t max_items, uint32_t max_pairs, int force_tpw, uint32_t *tpw, uint32_t *items_cap,
+                                      uint32_t *pair_cap, uint32_t *pool_cap, uint32_t *lds_bytes)
+{
+    uint32_t cap1, pr1, po1, cap2, pr2, po2;
+    const uint32_t lds1 = inline_sized(1, max_items, max_pairs, &cap1, &pr1, &po1), lds2 = inline_sized(2, max_items, max_pairs, &cap2, &pr2, &po2);
+    const uint32_t tiles1 = hvq_recon_inline_residency(1, cap1, lds1), tiles2 = 2u * hvq_recon_inline_residency(2, cap2, lds2);
+    /* Two tiles per workgroup when they keep at least 1.5 times the tiles of the one-tile launch resident.  Measured on the dense stream
+     * (profiles/r07_two_tiles_dense.txt, one box, three runs each, ms per step): two tiles at seven workgroups per CU 0.919, at six
+     * (HVQM4_AMD_LDS_PAD) 0.925, one tile at eight 0.929 -- six still wins by less than the spread of a run (0.5 %), so the rule stays
+     * where round 4 put it (sparse streams: 16 tiles against 8) and a launch whose fullest tile needs accumulators for 192 items keeps
+     * its two tiles at six. */
+    const bool two = lds2 <= 65536u && (force_tpw ? force_tpw >= 2 : 2u * tiles2 >= 3u * tiles1);
+    *tpw = two ? 2u : 1u;
+    *items_cap = two ? cap2 : cap1; *pair_cap = two ? pr2 : pr1; *pool_cap = two ? po2 : po1;
+    *lds_bytes = two ? lds2 : lds1;
+}
 
 static thread_local std::string g_err;
 static thread_local int g_sdk_err = 0;
@@ -1815,36 +1885,11 @@ static int flush_end(HvqContext *c)
         Launch &L = c->fl_launches[li];
         const uint32_t mi = lmi[li], mp = lmp[li];
         static const int force_tpw = getenv("HVQM4_AMD_TILES_PER_WG") ? atoi(getenv("HVQM4_AMD_TILES_PER_WG")) : 0;
-        {
-            /* hvq_recon_inline_kernel keeps its item queue, pair list and the tile range of the pool in LDS: accumulator rows
-             * for the fullest tile (x tiles per workgroup), a pair list for its pairs, the staged pool for its bases, scalars and a
-             * few literal blocks (what does not fit is read from HBM; more pairs than the list holds: the items walk their bases).
-             * Two tiles per workgroup when that keeps more tiles resident on a CU (8 workgroups by waves, 160 KB of LDS). */
-            static const uint32_t pair_lim = getenv("HVQM4_AMD_PAIR_CAP") ? (uint32_t)std::max(1, atoi(getenv("HVQM4_AMD_PAIR_CAP"))) : 4096u;
-            auto sized = [&](uint32_t t, uint32_t *cap, uint32_t *pairs, uint32_t *pool) -> uint32_t {
-                static const uint32_t steps2[] = { 32, 64, 96, 128, 192, 256, 384, 512 }, steps1[] = { 32, 64, 96, 128, 192, 256 };
-                const uint32_t want = std::min(256u * t, std::max(32u, t * mi));
-                uint32_t ic = t == 2 ? 512u : 256u;
-                for (uint32_t v : steps2) if (t == 2 && v >= want) { ic = v; break; }
-                for (uint32_t v : steps1) if (t == 1 && v >= want) { ic = v; break; }
-                *cap = ic;
-                *pairs = std::max(1u, std::min(pair_lim, t * mp));
-                /* HVQM4_AMD_POOL_CAP (tests): a smaller staging area, so that ordinary clips reach the read-from-HBM path of tiles
-                 * whose payload exceeds it */
-                static const uint32_t pool_lim = getenv("HVQM4_AMD_POOL_CAP") ? (uint32_t)std::max(0, atoi(getenv("HVQM4_AMD_POOL_CAP"))) : 1536u;
-                *pool = std::min(pool_lim, t * (mp + 2u * mi + 128u));
-                if (*pool) *pool = (*pool + 4u + 3u) & ~3u;      /* + 4: the staged range starts at the 16-byte boundary below the tile's first dword */
-                return (hvq_recon_inline_static_lds(t, ic) + hvq_recon_inline_dyn_lds(*pairs, *pool) + 511u) & ~511u;
-            };
-            uint32_t cap1, pr1, po1, cap2, pr2, po2;
-            const uint32_t lds1 = sized(1, &cap1, &pr1, &po1), lds2 = sized(2, &cap2, &pr2, &po2);
-            const uint32_t res1 = std::min(8u, 163840u / lds1), res2 = 2u * std::min(8u, 163840u / lds2);
-            /* measured (profiles/r04b_*): two tiles pay when they double the resident tiles (natural, flat), not for +25 % (dense) */
-            const bool two = lds2 <= 65536u && (force_tpw ? force_tpw >= 2 : 2u * res2 >= 3u * res1);
-            L.tpw = two ? 2u : 1u;
-            L.items_cap = two ? cap2 : cap1; L.pair_cap = two ? pr2 : pr1; L.pool_cap = two ? po2 : po1;
-        }
-        (void)mp;
+        uint32_t lds = 0;
+        hvq_recon_inline_plan(mi, mp, force_tpw, &L.tpw, &L.items_cap, &L.pair_cap, &L.pool_cap, &lds);
+        if (flush_timing())
+            fprintf(stderr, "[flush] launch %zu (level %d, queue %d): fullest tile %u items, %u pairs -> %u tile(s) per workgroup, items %u, pairs %u, pool %u, %u B of LDS = %u workgroups per CU\n",
+                    li, (int)L.level, (int)L.queue, mi, mp, L.tpw, L.items_cap, L.pair_cap, L.pool_cap, lds, hvq_recon_inline_residency(L.tpw, L.items_cap, lds));
         L.max_tiles = L.max_wg[L.tpw - 1]; L.workgroups = L.wgs[L.tpw - 1];
         st.workgroups += L.workgroups;
     }
