@@ -117,6 +117,11 @@ SYMBOLS = {
                                       C.c_void_p]),
     "hvq_export_tensors": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "hvq_export_resampled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
+    "hvq_resample_tile_rows": (C.c_int, [C.c_int] * 4),
     "hvq_get_stats": (C.c_int, [C.c_void_p, C.POINTER(HvqStats)]),
     "hvq_debug_table_divisions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "hvq_last_error_string": (C.c_char_p, []),

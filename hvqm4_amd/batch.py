@@ -191,7 +191,8 @@ class Context:
         check(lib().hvq_export_pictures(self._h, n, a_s, a_o, FORMATS[fmt], C.cast(a_d, C.c_void_p),
                                            C.c_void_p(stream)))
 
-    def export_float(self, sids, ordinals, out, *, crop=None, mean=(0, 0, 0), std=(1, 1, 1), scale: float = 1 / 255) -> None:
+    def export_float(self, sids, ordinals, out, *, crop=None, mean=(0, 0, 0), std=(1, 1, 1), scale: float = 1 / 255,
+                     antialias: bool = False) -> None:
         """hvq_export_tensors: resident pictures as the float tensors a network eats -- crop, bilinear resize (half-sample centres
         as F.interpolate(mode="bilinear", align_corners=False, antialias=False), taps clamped to the crop), (v * scale - mean) / std
         per channel and the conversion to `out`'s dtype, planar RGB, in one launch on torch's current stream of `out`'s device.
@@ -199,7 +200,16 @@ class Context:
         output sizes (H, W equal to the crop's: no resampling, normalise only).  `crop`: None (whole pictures), one (x, y, w, h)
         in luma samples for all, or a list per picture.  The arithmetic is specified in include/hvqm4_amd.h: v is the uint8
         sample export(..., "rgbp") gives, as a float, and the call computes v * mul + add with mul = scale / std and
-        add = -mean / std rounded once to float32.  Ordering and slot safety are export()'s."""
+        add = -mean / std rounded once to float32.  Ordering and slot safety are export()'s.
+        antialias=True resizes with hvq_export_resampled's triangle filter instead -- F.interpolate(..., antialias=True),
+        torchvision's Resize default: the filter to take when the output is smaller than the crop.  Same destinations, crops and
+        normalisation; at the crop's own size the same bits."""
+        from .export import FILTER_TRIANGLE
+        self._export_float(sids, ordinals, out, crop, mean, std, scale, FILTER_TRIANGLE if antialias else None)
+
+    def _export_float(self, sids, ordinals, out, crop, mean, std, scale, filt) -> None:
+        """export_float; filt = None: hvq_export_tensors, else hvq_export_resampled with that HVQ_FILTER_* (tools and tests pass
+        FILTER_TRIANGLE_DIRECT)"""
         import torch
         from .export import HvqTensorDst, check_one_hip_runtime, crops, float_destinations, normalisation
         n = len(sids)
@@ -217,8 +227,12 @@ class Context:
         a_s = (C.c_int * n)(*sids)
         a_o = (C.c_int * n)(*ordinals)
         a_d = (HvqTensorDst * n)(*[HvqTensorDst(p, r, pl, w, h, *rect) for (p, r, pl, w, h), rect in zip(dsts, rects)])
-        check(lib().hvq_export_tensors(self._h, n, a_s, a_o, dtype, (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
-                                       C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
+        if filt is None:
+            check(lib().hvq_export_tensors(self._h, n, a_s, a_o, dtype, (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
+                                           C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
+        else:
+            check(lib().hvq_export_resampled(self._h, n, a_s, a_o, dtype, int(filt), (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
+                                             C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
 
     def rgb_bench(self, reps: int):
         """-> (gpu_ms, bytes_per_rep, pictures): batched display epilogue over the newest picture of every stream"""

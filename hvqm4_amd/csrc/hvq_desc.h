@@ -221,5 +221,37 @@ typedef struct HvqTensorJob {
 /* per call: o = v * mul[c] + add[c] */
 typedef struct HvqTensorNorm { float mul[3], add[3]; } HvqTensorNorm;
 
+/* one picture of the antialiased float export (hvq_yuv_resample_kernel, hvq_export_resampled with HVQ_FILTER_TRIANGLE).  The weight
+ * tables of the two axes lie behind the job records in the same upload; xtab / ytab are byte offsets from the table base (the end of
+ * the records), multiples of 16.  One axis table of `n_out` outputs: int32 first[n_out] (first source index inside the crop),
+ * int32 start[n_out + 1] (weights of output j are w[start[j] .. start[j + 1])), float w[start[n_out]], padded to 16 bytes.
+ * Every member is a dword or a qword; 96 bytes: tables are uploaded in 16-byte units. */
+#define HVQ_RJ_VEC    1u            /* dst and pitches multiples of 16 bytes, out_w a multiple of the run length: 16-byte stores */
+#define HVQ_RJ_TILED  2u            /* a downscale whose largest tile footprint fits HVQ_RS_ROWS rows of LDS: the tiled body */
+#define HVQ_RS_TILE_W 64            /* output columns of a tile */
+#define HVQ_RS_ROWS   40            /* source rows of h the tiled body keeps in LDS: 3 * 40 * 64 floats = 30720 bytes per workgroup */
+typedef struct HvqResampleJob {
+    const uint8_t *y, *u, *v;
+    uint8_t *dst;
+    int64_t row_pitch, plane_pitch;    /* bytes */
+    int32_t w;                         /* samples per luma row of the source picture */
+    int32_t wshift, hshift;
+    int32_t x0, y0;                    /* crop origin */
+    int32_t out_w, out_h;
+    int32_t tile_h;                    /* HVQ_RJ_TILED: output rows of a tile (16 or 8) */
+    uint32_t xtab, ytab;
+    uint32_t flags;
+    uint32_t tiles_x;                  /* HVQ_RJ_TILED: tiles per tile row, ceil(out_w / HVQ_RS_TILE_W) */
+} HvqResampleJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqResampleJob) == 96, "HvqResampleJob must be 96 bytes");
+static_assert(sizeof(HvqResampleJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+static_assert(3 * HVQ_RS_ROWS * HVQ_RS_TILE_W * 4 == 30720, "five workgroups of the tiled body share a CU's 160 KiB of LDS");
+#else
+_Static_assert(sizeof(HvqResampleJob) == 96, "HvqResampleJob must be 96 bytes");
+_Static_assert(sizeof(HvqResampleJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

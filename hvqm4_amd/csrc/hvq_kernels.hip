@@ -1684,6 +1684,197 @@ extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max
     return hipGetLastError();
 }
 
+/* ------------------------------------------------------------------------------------------------------
+ * Antialiased float export (hvq_export_resampled, HVQ_FILTER_TRIANGLE): the separable triangle filter of include/hvqm4_amd.h,
+ * horizontal first.  The weight tables are built on the host and lie behind the job records; the kernel multiplies and adds in the
+ * tables' order, through t_mul / t_add like the kernel above.  A kernel of its own: its bodies need LDS and registers that
+ * hvq_yuv_tensor_kernel's streaming body must not pay for.  Two bodies, picked per job by HVQ_RJ_TILED (uniform per workgroup):
+ *   tiled   a workgroup owns HVQ_RS_TILE_W output columns x tile_h output rows.  Pass 1: h_c(y, j) for every source row of the tile's
+ *           vertical footprint and every tile column, as float32 in LDS (the host sets the flag only when the largest footprint of any
+ *           tile of the job fits HVQ_RS_ROWS rows); one barrier; pass 2: a lane sums its run of outputs down the LDS columns.
+ *   direct  one lane per run of adjacent output samples, nested loops over the ky x kx taps; h is recomputed per output row.
+ * h_c(y, j) and v_c(i, j) are the same left-to-right sums in both: the bodies agree bit for bit.  Every product is >= +0, so a sum
+ * that starts from 0.0f has the bits of one that starts from its first product.
+ */
+struct rs_axis { const GLB int *first; const GLB int *start; const GLB float *w; };
+
+__device__ __forceinline__ rs_axis rs_table(const uint8_t *tabs, u32 off, int n_out)
+{
+    const GLB int *p = (const GLB int *)(tabs + off);
+    rs_axis a = { p, p + n_out, (const GLB float *)(p + 2 * n_out + 1) };
+    return a;
+}
+
+/* h_c(y, j), c = R, G, B: `cnt` taps from luma column x (absolute) of luma row yy (absolute), weights wx[0 .. cnt) */
+__device__ __forceinline__ void rs_hsum(const HvqResampleJob &J, int yy, int x, int cnt, const GLB float *wx, float h[3])
+{
+    const GLB uint8_t *py = (const GLB uint8_t *)J.y + (size_t)yy * (size_t)J.w;
+    const size_t co = (size_t)(yy >> J.hshift) * (size_t)(J.w >> J.wshift);
+    const GLB uint8_t *pu = (const GLB uint8_t *)J.u + co, *pv = (const GLB uint8_t *)J.v + co;
+    const int ws = J.wshift;
+    h[0] = h[1] = h[2] = 0.f;
+#pragma unroll 2
+    for (int k = 0; k < cnt; ++k) {
+        const int xs = x + k;
+        float p[3];
+        tensor_rgb(py[xs], pu[xs >> ws], pv[xs >> ws], p);
+        const float wk = wx[k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) h[c] = t_add(h[c], t_mul(p[c], wk));
+    }
+}
+
+/* R normalised samples of one plane -> the destination: one 16-byte store, or element stores of the first `n` */
+template <typename T>
+__device__ __forceinline__ void rs_store(GLB uint8_t *d, const float *o, bool vec, int n)
+{
+    constexpr int R = tensor_run<T>::R;
+    if (vec) {
+        u32 q[4];
+        tensor_pack4<T>(o, q);
+        if constexpr (R == 8) tensor_pack4<T>(o + 4, q + 2);
+        tensor_store16(d, q);
+    } else {
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) {
+            if (rr >= n) break;
+            GLB uint8_t *e = d + (size_t)rr * sizeof(T);
+            if (sizeof(T) == 4) *(GLB u32 *)e = tensor_bits<T>(o[rr]);
+            else *(GLB uint16_t *)e = (uint16_t)tensor_bits<T>(o[rr]);
+        }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void resample_direct(const HvqResampleJob &J, const uint8_t *tabs, const HvqTensorNorm &nm)
+{
+    constexpr int R = tensor_run<T>::R;
+    const int runs = (J.out_w + R - 1) / R;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= runs * J.out_h) return;                       /* no barrier in this body */
+    const int i = idx / runs, kr = idx - i * runs;
+    const rs_axis X = rs_table(tabs, J.xtab, J.out_w), Y = rs_table(tabs, J.ytab, J.out_h);
+    const int fy = Y.first[i], ys = Y.start[i], ny = Y.start[i + 1] - ys;
+    const bool vec = (J.flags & HVQ_RJ_VEC) != 0;
+    const int n = min(R, J.out_w - kr * R);                  /* samples of this run inside the row */
+    float o[3][R];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) o[c][rr] = 0.f;
+#pragma unroll 1
+    for (int rr = 0; rr < n; ++rr) {
+        const int j = kr * R + rr;
+        const int fx = X.first[j], xs = X.start[j], nx = X.start[j + 1] - xs;
+        float v[3] = { 0.f, 0.f, 0.f };
+#pragma unroll 1
+        for (int ky = 0; ky < ny; ++ky) {
+            float h[3];
+            rs_hsum(J, J.y0 + fy + ky, J.x0 + fx, nx, X.w + xs, h);
+            const float wk = Y.w[ys + ky];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = t_add(v[c], t_mul(h[c], wk));
+        }
+        /* the loop over the run is not unrolled (its body holds the tap loops): the sample lands in its register by selects */
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float val = t_add(t_mul(v[c], nm.mul[c]), nm.add[c]);
+#pragma unroll
+            for (int q = 0; q < R; ++q) o[c][q] = rr == q ? val : o[c][q];
+        }
+    }
+    GLB uint8_t *d = (GLB uint8_t *)J.dst + (size_t)i * (size_t)J.row_pitch + (size_t)kr * 16u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rs_store<T>(d + (size_t)c * (size_t)J.plane_pitch, o[c], vec, n);
+}
+
+template <typename T>
+__device__ __forceinline__ void resample_tiled(const HvqResampleJob &J, const uint8_t *tabs, const HvqTensorNorm &nm,
+                                               float (*s_h)[HVQ_RS_ROWS][HVQ_RS_TILE_W])
+{
+    constexpr int R = tensor_run<T>::R, TW = HVQ_RS_TILE_W, RUNS = TW / R;
+    const int th = J.tile_h;
+    const int tiles_y = (J.out_h + th - 1) / th;
+    const int ty = (int)blockIdx.x / (int)J.tiles_x, tx = (int)blockIdx.x - ty * (int)J.tiles_x;
+    if (ty >= tiles_y) return;                               /* uniform: the whole workgroup leaves, ahead of the barrier */
+    const rs_axis X = rs_table(tabs, J.xtab, J.out_w), Y = rs_table(tabs, J.ytab, J.out_h);
+    const int i0 = ty * th, i1 = min(i0 + th, J.out_h) - 1, j0 = tx * TW;
+    const int fy0 = Y.first[i0];                             /* first and end are monotonic in the output index */
+    const int rows = min(Y.first[i1] + (Y.start[i1 + 1] - Y.start[i1]) - fy0, HVQ_RS_ROWS);   /* the host checked; never index past the array */
+    const int tid = (int)threadIdx.x;
+    /* pass 1: a lane keeps its column (256 lanes = 4 rows of 64 columns) and walks the rows */
+    {
+        const int col = tid & (TW - 1), j = j0 + col;
+        const bool live = j < J.out_w;
+        const int jj = live ? j : 0;
+        const int fx = X.first[jj], xs = X.start[jj], nx = live ? X.start[jj + 1] - xs : 0;
+        for (int r = tid / TW; r < rows; r += 256 / TW) {
+            float h[3];
+            rs_hsum(J, J.y0 + fy0 + r, J.x0 + fx, nx, X.w + xs, h);      /* a column past the row: no taps, zeros */
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s_h[c][r][col] = h[c];
+        }
+    }
+    __syncthreads();
+    /* pass 2: one lane per run of R outputs of a tile row, down the LDS columns in ascending k */
+    const bool vec = (J.flags & HVQ_RJ_VEC) != 0;
+    for (int it = tid; it < RUNS * th; it += 256) {
+        const int il = it / RUNS, kr = it - il * RUNS;
+        const int i = i0 + il, jb = j0 + kr * R;
+        if (i > i1 || jb >= J.out_w) continue;
+        const int ys = Y.start[i], ny = Y.start[i + 1] - ys;
+        const int r0 = Y.first[i] - fy0;
+        float v[3][R];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) v[c][rr] = 0.f;
+        for (int ky = 0; ky < ny; ++ky) {
+            const int r = min(r0 + ky, HVQ_RS_ROWS - 1);
+            const float wk = Y.w[ys + ky];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int rr = 0; rr < R; ++rr) v[c][rr] = t_add(v[c][rr], t_mul(s_h[c][r][kr * R + rr], wk));
+        }
+        const int n = min(R, J.out_w - jb);
+        GLB uint8_t *d = (GLB uint8_t *)J.dst + (size_t)i * (size_t)J.row_pitch + (size_t)jb * sizeof(T);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float o[R];
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) o[rr] = t_add(t_mul(v[c][rr], nm.mul[c]), nm.add[c]);
+            rs_store<T>(d + (size_t)c * (size_t)J.plane_pitch, o, vec, n);
+        }
+    }
+}
+
+/* one picture per grid row; tabs = the table base behind the njobs records */
+template <typename T>
+__global__ __launch_bounds__(256)
+void hvq_yuv_resample_kernel(const HvqResampleJob *__restrict__ jobs, const uint8_t *__restrict__ tabs, HvqTensorNorm nm)
+{
+    __shared__ __attribute__((aligned(16))) float s_h[3][HVQ_RS_ROWS][HVQ_RS_TILE_W];
+    const HvqResampleJob J = jobs[blockIdx.y];
+    if (J.flags & HVQ_RJ_TILED) resample_tiled<T>(J, tabs, nm, s_h);
+    else resample_direct<T>(J, tabs, nm);
+}
+
+/* jobs_dev: HvqResampleJob[njobs] in device memory with the tables behind them; max_wgs = max over jobs of their workgroups
+ * (tiled: tiles_x * ceil(out_h / tile_h); direct: ceil(ceil(out_w / R) * out_h / 256)) */
+extern "C" hipError_t hvq_launch_resample(const void *jobs_dev, int njobs, int max_wgs, int dtype, const HvqTensorNorm *nm, hipStream_t stream)
+{
+    if (njobs <= 0 || max_wgs <= 0) return hipSuccess;
+    const HvqResampleJob *j = (const HvqResampleJob *)jobs_dev;
+    const uint8_t *tabs = (const uint8_t *)(j + njobs);
+    const dim3 grid(max_wgs, njobs), block(256);
+    if (dtype == HVQ_T_F32) hvq_yuv_resample_kernel<float><<<grid, block, 0, stream>>>(j, tabs, *nm);
+    else if (dtype == HVQ_T_F16) hvq_yuv_resample_kernel<_Float16><<<grid, block, 0, stream>>>(j, tabs, *nm);
+    else if (dtype == HVQ_T_BF16) hvq_yuv_resample_kernel<hvq_bf16><<<grid, block, 0, stream>>>(j, tabs, *nm);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 /* bulk readback (hvq_read_pictures): `n` resident pictures gathered into one contiguous staging buffer, so that the copy to the
  * host is one large transfer instead of `n` small ones */
 __global__ __launch_bounds__(256)

@@ -65,6 +65,7 @@ extern "C" void hvq_set_stamps(unsigned long long *p);
 #endif
 extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, int format, hipStream_t stream);
 extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max_lanes, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
+extern "C" hipError_t hvq_launch_resample(const void *jobs_dev, int njobs, int max_wgs, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -2346,6 +2347,33 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
                           [=](const void *tab, hipStream_t st) { return hvq_launch_rgb(tab, n, max_lanes, wide, format, st); });
 }
 
+/* hvq_export_tensors' checks of one destination, for hvq_export_resampled: output size, crop, pitches, alignment (es = element size).
+ * The crop and the pitches in effect come back in *g; `bits` = pointer | pitches, for the alignment of the 16-byte stores. */
+struct TensorGeom { int x0, y0, cw, ch; int64_t rp, pp; uint64_t bits; };
+static int tensor_dst_check(const Stream &s, const HvqTensorDst &d, int i, int64_t es, TensorGeom *g)
+{
+    if (!d.ptr) return fail(HVQ_E_ARG, "null destination %d", i);
+    if (d.out_w < 1 || d.out_h < 1 || d.out_w > 16384 || d.out_h > 16384)
+        return fail(HVQ_E_ARG, "destination %d: output size %d x %d outside [1, 16384]", i, d.out_w, d.out_h);
+    int x0 = 0, y0 = 0, cw = s.w, ch = s.h;
+    if (d.crop_w) { x0 = d.crop_x; y0 = d.crop_y; cw = d.crop_w; ch = d.crop_h; }
+    else if (d.crop_x || d.crop_y || d.crop_h) return fail(HVQ_E_ARG, "destination %d: crop_w == 0 takes the whole picture, the other crop fields must be 0", i);
+    if (x0 < 0 || y0 < 0 || cw < 1 || ch < 1 || (int64_t)x0 + cw > s.w || (int64_t)y0 + ch > s.h)
+        return fail(HVQ_E_ARG, "destination %d: crop (%d, %d, %d, %d) is empty or leaves the %d x %d picture", i, x0, y0, cw, ch, s.w, s.h);
+    const int64_t dense = (int64_t)d.out_w * es;
+    const int64_t rp = d.row_pitch ? d.row_pitch : dense;
+    const int64_t pp = d.plane_pitch ? d.plane_pitch : rp * d.out_h;
+    if (rp < dense || rp > ((int64_t)1 << 40) || d.plane_pitch > ((int64_t)1 << 48))
+        return fail(HVQ_E_ARG, "destination %d: row pitch %lld outside [%lld, 2^40] or plane pitch above 2^48", i, (long long)rp, (long long)dense);
+    if (pp < rp * d.out_h)
+        return fail(HVQ_E_ARG, "destination %d: plane pitch %lld below row pitch x height %lld (planes overlap)", i, (long long)pp, (long long)(rp * d.out_h));
+    const uint64_t bits = (uint64_t)(uintptr_t)d.ptr | (uint64_t)rp | (uint64_t)pp;
+    if (bits & (uint64_t)(es - 1))
+        return fail(HVQ_E_ARG, "destination %d: pointer, row pitch and plane pitch must be multiples of the element size %d", i, (int)es);
+    *g = TensorGeom{ x0, y0, cw, ch, rp, pp, bits };
+    return HVQ_OK;
+}
+
 HVQ_EXPORT int hvq_export_tensors(HvqContext *c, int n, const int *streams, const int *ordinals, int dtype,
                                   const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream)
 {
@@ -2404,6 +2432,175 @@ HVQ_EXPORT int hvq_export_tensors(HvqContext *c, int n, const int *streams, cons
     }
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqTensorJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_tensor(tab, n, max_lanes, dtype, &nm, st); });
+}
+
+/* ---- the triangle filter's weight tables (include/hvqm4_amd.h: the specification).  Double arithmetic, one rounding per operation:
+ * contraction is off in these functions, so that the table is numpy's bit for bit on any host. ---- */
+struct ResampleSpan { int first, count; };
+static ResampleSpan resample_span(int n_src, int n_out, int j, double *scale_out, double *support_out, double *c_out)
+{
+#pragma clang fp contract(off)
+    const double scale = (double)n_src / (double)n_out;
+    const double support = scale > 1.0 ? scale : 1.0;
+    const double c = scale * ((double)j + 0.5);
+    const int first = std::max((int)(c - support + 0.5), 0);
+    const int end = std::min((int)(c + support + 0.5), n_src);
+    if (scale_out) { *scale_out = scale; *support_out = support; *c_out = c; }
+    return ResampleSpan{ first, end - first };
+}
+
+static bool resample_sizes_ok(int n_src, int n_out) { return n_src >= 1 && n_src <= 65535 && n_out >= 1 && n_out <= 16384; }
+
+static size_t resample_weights_len(int n_src, int n_out)
+{
+    size_t total = 0;
+    for (int j = 0; j < n_out; ++j) total += (size_t)resample_span(n_src, n_out, j, nullptr, nullptr, nullptr).count;
+    return total;
+}
+
+/* first[n_out], count[n_out], weights[resample_weights_len] */
+static void resample_fill(int n_src, int n_out, int32_t *first, int32_t *count, float *weights)
+{
+#pragma clang fp contract(off)
+    std::vector<double> u;
+    size_t at = 0;
+    for (int j = 0; j < n_out; ++j) {
+        double scale, support, c;
+        const ResampleSpan sp = resample_span(n_src, n_out, j, &scale, &support, &c);
+        u.resize((size_t)sp.count);
+        double t = 0.0;
+        for (int k = 0; k < sp.count; ++k) {
+            const double d = ((double)(k + sp.first) - c + 0.5) / support;
+            const double v = 1.0 - std::fabs(d);
+            u[(size_t)k] = v > 0.0 ? v : 0.0;
+            t = k ? t + u[(size_t)k] : u[0];
+        }
+        for (int k = 0; k < sp.count; ++k) weights[at + (size_t)k] = (float)(u[(size_t)k] / t);
+        first[j] = sp.first;
+        count[j] = sp.count;
+        at += (size_t)sp.count;
+    }
+}
+
+HVQ_EXPORT int hvq_resample_table(int n_src, int n_out, int32_t *first, int32_t *count, float *weights, size_t weights_cap, size_t *weights_len)
+{
+    if (!resample_sizes_ok(n_src, n_out)) return fail(HVQ_E_ARG, "n_src %d outside [1, 65535] or n_out %d outside [1, 16384]", n_src, n_out);
+    const size_t need = resample_weights_len(n_src, n_out);
+    if (weights_len) *weights_len = need;
+    if (!weights) return weights_len ? HVQ_OK : fail(HVQ_E_ARG, "a length query needs weights_len");
+    if (!first || !count) return fail(HVQ_E_ARG, "bad arguments");
+    if (weights_cap < need) return fail(HVQ_E_OVERFLOW, "the table holds %zu weights, room for %zu", need, weights_cap);
+    resample_fill(n_src, n_out, first, count, weights);
+    return HVQ_OK;
+}
+
+/* Output rows of a tile when the tiled body of hvq_yuv_resample_kernel takes a job (16, or 8), 0 when the direct body does: tiled for a
+ * downscale along either axis whose largest vertical tile footprint fits HVQ_RS_ROWS source rows.  first and end are monotonic in the
+ * output index, so a tile's footprint is [first of its first row, end of its last). */
+static int resample_tile_rows(int cw, int ch, int out_w, int out_h, const int32_t *yfirst, const int32_t *ycount)
+{
+    if (out_w >= cw && out_h >= ch) return 0;
+    for (int th : { 16, 8 }) {
+        int worst = 0;
+        for (int i0 = 0; i0 < out_h; i0 += th) {
+            const int i1 = std::min(i0 + th, out_h) - 1;
+            worst = std::max(worst, yfirst[i1] + ycount[i1] - yfirst[i0]);
+        }
+        if (worst <= HVQ_RS_ROWS) return th;
+    }
+    return 0;
+}
+
+HVQ_EXPORT int hvq_resample_tile_rows(int crop_w, int crop_h, int out_w, int out_h)
+{
+    if (!resample_sizes_ok(crop_w, out_w) || !resample_sizes_ok(crop_h, out_h)) return fail(HVQ_E_ARG, "crop or output size out of range");
+    std::vector<int32_t> first((size_t)out_h), count((size_t)out_h);
+    for (int i = 0; i < out_h; ++i) {
+        const ResampleSpan sp = resample_span(crop_h, out_h, i, nullptr, nullptr, nullptr);
+        first[(size_t)i] = sp.first; count[(size_t)i] = sp.count;
+    }
+    return resample_tile_rows(crop_w, crop_h, out_w, out_h, first.data(), count.data());
+}
+
+HVQ_EXPORT int hvq_export_resampled(HvqContext *c, int n, const int *streams, const int *ordinals, int dtype, int filter,
+                                    const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream)
+{
+    if (filter == HVQ_FILTER_BILINEAR) return hvq_export_tensors(c, n, streams, ordinals, dtype, mul, add, dst, hip_stream);
+    if (filter != HVQ_FILTER_TRIANGLE && filter != HVQ_FILTER_TRIANGLE_DIRECT) return fail(HVQ_E_ARG, "bad filter %d", filter);
+    if (!c || n < 0 || !mul || !add || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    if (dtype != HVQ_T_F32 && dtype != HVQ_T_F16 && dtype != HVQ_T_BF16) return fail(HVQ_E_ARG, "bad dtype %d", dtype);
+    HvqTensorNorm nm;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(mul[k]) || !std::isfinite(add[k])) return fail(HVQ_E_ARG, "mul / add of channel %d is not finite", k);
+        nm.mul[k] = mul[k]; nm.add[k] = add[k];
+    }
+    if (!n) return HVQ_OK;
+    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
+    const int64_t es = dtype == HVQ_T_F32 ? 4 : 2;
+    const int run = (int)(16 / es);
+    /* the upload: n job records, then every distinct (n_src, n_out) axis table once -- first[n_out], start[n_out + 1], weights, padded to
+     * 16 bytes; the records carry byte offsets from the end of the records */
+    struct AxisTab { int n_src, n_out; uint32_t off; std::vector<int32_t> first, count; };
+    std::vector<AxisTab> tabs;
+    std::vector<uint8_t> up((size_t)n * sizeof(HvqResampleJob));
+    auto axis = [&](int n_src, int n_out) -> int {
+        for (size_t t = 0; t < tabs.size(); ++t) if (tabs[t].n_src == n_src && tabs[t].n_out == n_out) return (int)t;
+        AxisTab T;
+        T.n_src = n_src; T.n_out = n_out;
+        T.first.resize((size_t)n_out); T.count.resize((size_t)n_out);
+        const size_t nw = resample_weights_len(n_src, n_out);
+        const size_t at = up.size(), words = 2u * (size_t)n_out + 1u + nw, bytes = align_up(words * 4u, 16);
+        if (at - (size_t)n * sizeof(HvqResampleJob) + bytes > ((size_t)1 << 31)) return -1;
+        up.resize(at + bytes);                               /* zero-filled, the padding included */
+        std::vector<float> w(nw);
+        resample_fill(n_src, n_out, T.first.data(), T.count.data(), w.data());
+        int32_t *p = (int32_t *)(up.data() + at);
+        memcpy(p, T.first.data(), (size_t)n_out * 4u);
+        int32_t sum = 0;
+        for (int j = 0; j < n_out; ++j) { p[n_out + j] = sum; sum += T.count[(size_t)j]; }
+        p[2 * n_out] = sum;
+        memcpy(p + 2 * n_out + 1, w.data(), nw * 4u);
+        T.off = (uint32_t)(at - (size_t)n * sizeof(HvqResampleJob));
+        tabs.push_back(std::move(T));
+        return (int)tabs.size() - 1;
+    };
+    int max_wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!src) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const HvqTensorDst &d = dst[i];
+        TensorGeom g;
+        rc = tensor_dst_check(s, d, i, es, &g);
+        if (rc) return rc;
+        const int tx = axis(g.cw, d.out_w), ty = tx < 0 ? -1 : axis(g.ch, d.out_h);
+        if (tx < 0 || ty < 0) return fail(HVQ_E_OVERFLOW, "the weight tables of the call exceed 2 GiB");
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        HvqResampleJob j;
+        memset(&j, 0, sizeof j);
+        j.y = src; j.u = src + ny; j.v = src + ny + nc;
+        j.dst = (uint8_t *)d.ptr; j.row_pitch = g.rp; j.plane_pitch = g.pp;
+        j.w = s.w; j.wshift = s.wshift; j.hshift = s.hshift;
+        j.x0 = g.x0; j.y0 = g.y0; j.out_w = d.out_w; j.out_h = d.out_h;
+        j.xtab = tabs[(size_t)tx].off; j.ytab = tabs[(size_t)ty].off;
+        if (!(g.bits & 15u) && d.out_w % run == 0) j.flags |= HVQ_RJ_VEC;
+        const int th = filter == HVQ_FILTER_TRIANGLE_DIRECT ? 0
+                     : resample_tile_rows(g.cw, g.ch, d.out_w, d.out_h, tabs[(size_t)ty].first.data(), tabs[(size_t)ty].count.data());
+        int wgs;
+        if (th) {
+            j.flags |= HVQ_RJ_TILED;
+            j.tile_h = th;
+            j.tiles_x = (uint32_t)((d.out_w + HVQ_RS_TILE_W - 1) / HVQ_RS_TILE_W);
+            wgs = (int)j.tiles_x * ((d.out_h + th - 1) / th);
+        } else {
+            wgs = ((d.out_w + run - 1) / run * d.out_h + 255) / 256;
+        }
+        memcpy(up.data() + (size_t)i * sizeof(HvqResampleJob), &j, sizeof j);
+        max_wgs = std::max(max_wgs, wgs);
+    }
+    return export_enqueue(c, up.data(), up.size(), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_resample(tab, n, max_wgs, dtype, &nm, st); });
 }
 
 HVQ_EXPORT int hvq_rgb_bench(HvqContext *c, int reps, float *gpu_ms, uint64_t *bytes_per_rep, uint32_t *pictures)

@@ -84,6 +84,7 @@ def _destination(t, geom, fmt: str, i: int) -> Tuple[int, int, int]:
     return ptr, row, plane
 
 
+FILTER_BILINEAR, FILTER_TRIANGLE, FILTER_TRIANGLE_DIRECT = 0, 1, 0x101      # HVQ_FILTER_*
 DTYPES = {"float32": (0, 4), "float16": (1, 2), "bfloat16": (2, 2)}    # torch dtype name -> (HVQ_T_*, element size)
 MAX_OUT = 16384
 
@@ -123,6 +124,23 @@ def normalisation(mean=(0, 0, 0), std=(1, 1, 1), scale: float = 1 / 255) -> Tupl
             raise ValueError(f"channel {c}: scale / std or mean / std does not fit float32")
         mul.append(m); add.append(a)
     return mul, add
+
+
+def resample_table(n_src: int, n_out: int):
+    """hvq_resample_table: the triangle filter's table of one axis (n_src = crop size, n_out = output size) as numpy arrays
+    (first, count, weights) -- int32 [n_out], int32 [n_out], float32 [count.sum()]; the weights of output j start at
+    count[:j].sum().  Host only: no GPU needed.  HvqError for sizes outside [1, 65535] / [1, 16384]."""
+    import numpy as np
+    from ._lib import check, lib
+    n_src, n_out = int(n_src), int(n_out)
+    need = C.c_size_t(0)
+    check(lib().hvq_resample_table(n_src, n_out, None, None, None, 0, C.byref(need)))
+    first, count = np.empty(n_out, dtype=np.int32), np.empty(n_out, dtype=np.int32)
+    weights = np.empty(need.value, dtype=np.float32)
+    i32, f32 = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    check(lib().hvq_resample_table(n_src, n_out, first.ctypes.data_as(i32), count.ctypes.data_as(i32), weights.ctypes.data_as(f32),
+                                   need.value, C.byref(need)))
+    return first, count, weights
 
 
 def crops(crop, geoms: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int, int]]:

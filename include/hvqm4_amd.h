@@ -230,6 +230,45 @@ typedef struct HvqTensorDst {
 int  hvq_export_tensors(HvqContext *ctx, int n, const int *streams, const int *ordinals, int dtype,
                         const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream);
 
+/* The float export with a choice of resampling filter.  HVQ_FILTER_BILINEAR is hvq_export_tensors (the call forwards: same bits);
+ * HVQ_FILTER_TRIANGLE is the antialiased resize of PIL / torch `antialias=True`: a separable triangle filter, horizontal first,
+ * whose support grows with the downscale, so that every source sample of the crop contributes.  Use it when the output is
+ * smaller than the crop (640x480 -> 224x224 skips more than half of the samples with two taps); for upscaling it is an
+ * interpolation much like the bilinear one, at identity size it is the identity.  HvqTensorDst, lookup, HVQ_E_STATE cases,
+ * argument checks ("a refused call enqueues nothing"), ordering and slot safety are hvq_export_tensors'; the call joins the same
+ * export chain.  A bad `filter` is HVQ_E_ARG.
+ *   Tables, per axis (n_src = crop size, n_out = output size, 0 <= j < n_out), computed on the host in DOUBLE, one rounding per
+ *   operation, never contracted:
+ *       scale   = n_src / n_out;   support = max(scale, 1.0);   c = scale * (j + 0.5)
+ *       first_j = max((int)(c - support + 0.5), 0)                      (C truncation)
+ *       end_j   = min((int)(c + support + 0.5), n_src);   count_j = end_j - first_j      (>= 1, <= 2 * ceil(support) + 1)
+ *       u_k     = max(0.0, 1.0 - fabs((k + first_j - c + 0.5) / support)),   k = 0 .. count_j - 1
+ *       t       = u_0 + u_1 + ...  (left to right);   w_j[k] = (float)(u_k / t)        (the only rounding to float32)
+ *   Zero weights at the ends are kept (every term is >= 0: they cannot change a bit).
+ *   Pixels, all float32, one rounding per operation, never fused; P_c(y, x) is hvq_export_tensors' source sample; wx / fx are the
+ *   table of (crop_w, out_w), wy / fy that of (crop_h, out_h):
+ *       h_c(y, j) = P_c(y, fx_j) * wx_j[0];   then for k = 1 .. :  h = h + P_c(y, fx_j + k) * wx_j[k]
+ *       v_c(i, j) = h_c(fy_i, j) * wy_i[0];   then for k = 1 .. :  v = v + h_c(fy_i + k, j) * wy_i[k]
+ *       o = v * mul[c] + add[c];   the 16-bit types are rounded to nearest even from o.
+ *   At output size == crop size every row of weights is [1, 0], so v == P exactly: the bits of hvq_export_tensors.  Against torch's
+ *   F.interpolate(mode="bilinear", antialias=True, align_corners=False), which builds its weights in float32, the values differ
+ *   by a few thousandths of a 0..255 unit.
+ *   HVQ_FILTER_TRIANGLE_DIRECT gives the same bits through the kernel's untiled body alone: for measurements and tests (the
+ *   library picks the body per picture by itself). */
+#define HVQ_FILTER_BILINEAR        0
+#define HVQ_FILTER_TRIANGLE        1
+#define HVQ_FILTER_TRIANGLE_DIRECT 0x101
+int  hvq_export_resampled(HvqContext *ctx, int n, const int *streams, const int *ordinals, int dtype, int filter,
+                          const float mul[3], const float add[3], const HvqTensorDst *dst, void *hip_stream);
+/* Host only, no GPU needed: the table of one axis in CSR form -- first[n_out], count[n_out]; the weights of output j start at
+ * sum(count[0 .. j)).  weights == NULL: only *weights_len = the number of weights is returned.  HVQ_E_ARG for n_src outside
+ * [1, 65535] or n_out outside [1, 16384]; HVQ_E_OVERFLOW when weights_cap (in floats) is too small. */
+int  hvq_resample_table(int n_src, int n_out, int32_t *first, int32_t *count, float *weights, size_t weights_cap, size_t *weights_len);
+/* Host only: which body of the kernel HVQ_FILTER_TRIANGLE takes for a crop_w x crop_h -> out_w x out_h picture: the output rows per
+ * tile (16 or 8) of the tiled body -- a downscale whose tiles' source rows fit its LDS budget -- or 0 for the direct body
+ * (upscales, identity, very large ratios).  The values do not depend on it. */
+int  hvq_resample_tile_rows(int crop_w, int crop_h, int out_w, int out_h);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);

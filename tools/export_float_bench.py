@@ -8,6 +8,12 @@ Two measurements, each a child process of this driver under its own `timeout`:
   route   the fused call against the route a user of the uint8 export takes: export(..., "rgbp"), .to(dtype), crop,
           F.interpolate(bilinear), normalise in torch (in place).  Both event-timed on one stream, alternating rounds, 640x480 ->
           same size and -> 224x224, float32 and float16.
+  aa      the antialiased call (export_float(antialias=True), hvq_export_resampled) for 128 pictures (16 streams of 8) 640x480 ->
+          224x224 and -> 320x240, float32 and float16, four legs: (a) the call as the library runs it (the tiled body at these shapes),
+          (b) the same forced to the direct body (HVQ_FILTER_TRIANGLE_DIRECT: an argument for this tool and the tests, not a switch
+          of the product), (c) the plain two-tap call at the same shapes, (d) the torch route export("rgbp") -> .float() ->
+          F.interpolate(antialias=True) -> normalise.  Event-timed on one stream in alternating rounds.
+  aa_trace  rocprofv3 --kernel-trace --stats around legs (a), (b), (c) in a fixed order: the kernel times of the legs.
 One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
 import argparse
 import csv
@@ -117,6 +123,106 @@ def child_route(args):
     print(json.dumps(res))
 
 
+AA_SHAPES = ((224, 224), (240, 320))
+AA_DTYPES = ("float32", "float16")
+
+
+def aa_setup(args):
+    args.streams, args.per = args.aa_streams, 8
+    return setup(args)
+
+
+def aa_legs(torch, ctx, all_s, all_o, hw, dt):
+    """the four legs of one shape and dtype as closures: {leg: (fn, result tensor getter)}"""
+    import torch.nn.functional as F
+    from hvqm4_amd.export import FILTER_TRIANGLE, FILTER_TRIANGLE_DIRECT, normalisation
+    n = len(all_s)
+    td = getattr(torch, dt)
+    mul, add = normalisation(MEAN, STD)
+    m = torch.tensor(mul, dtype=td, device="cuda").view(1, 3, 1, 1)
+    a = torch.tensor(add, dtype=td, device="cuda").view(1, 3, 1, 1)
+    outs = {k: torch.empty((n, 3) + hw, dtype=td, device="cuda") for k in "abc"}
+    u8 = torch.empty((n, 3, H, W), dtype=torch.uint8, device="cuda")
+    keep = {}
+
+    def leg_d():
+        ctx.export(all_s, all_o, u8, "rgbp")
+        keep["d"] = F.interpolate(u8.to(td), size=hw, mode="bilinear", align_corners=False, antialias=True).mul_(m).add_(a)
+
+    legs = {"a_tiled": lambda: ctx._export_float(all_s, all_o, outs["a"], None, MEAN, STD, 1 / 255, FILTER_TRIANGLE),
+            "b_direct": lambda: ctx._export_float(all_s, all_o, outs["b"], None, MEAN, STD, 1 / 255, FILTER_TRIANGLE_DIRECT),
+            "c_plain": lambda: ctx.export_float(all_s, all_o, outs["c"], mean=MEAN, std=STD),
+            "d_torch": leg_d}
+    return legs, outs, keep
+
+
+def child_aa(args):
+    torch, ctx, all_s, all_o = aa_setup(args)
+    from hvqm4_amd._lib import lib
+    res = {"pictures": len(all_s), "source": f"{W}x{H}", "reps": args.reps, "rounds": args.rounds}
+    for hw in AA_SHAPES:
+        for dt in AA_DTYPES:
+            legs, outs, keep = aa_legs(torch, ctx, all_s, all_o, hw, dt)
+            for fn in legs.values():
+                timed(torch, fn, args.warmup)
+            rows = {k: [] for k in legs}
+            for _ in range(args.rounds):
+                for k, fn in legs.items():
+                    rows[k].append(round(timed(torch, fn, args.reps), 4))
+            out = {k + "_ms": v for k, v in rows.items()}
+            out.update({k + "_median_ms": statistics.median(v) for k, v in rows.items()})
+            out["tile_rows"] = lib().hvq_resample_tile_rows(W, H, hw[1], hw[0])
+            out["bodies_equal_bits"] = bool(torch.equal(outs["a"], outs["b"]))
+            out["max_abs_difference_to_torch"] = float((outs["a"].float() - keep["d"].float()).abs().max())
+            res[f"{hw[1]}x{hw[0]}_{dt}"] = out
+            del legs, outs, keep
+            torch.cuda.empty_cache()
+    ctx.close()
+    print(json.dumps(res))
+
+
+def child_aa_trace(args):
+    """legs (a), (b), (c) in a fixed order, `reps` launches each after one warm-up launch: aa_trace_summary reads them by order"""
+    torch, ctx, all_s, all_o = aa_setup(args)
+    plan = []
+    for hw in AA_SHAPES:
+        for dt in AA_DTYPES:
+            legs, outs, keep = aa_legs(torch, ctx, all_s, all_o, hw, dt)
+            for k in ("a_tiled", "b_direct", "c_plain"):
+                for _ in range(1 + args.reps):
+                    legs[k]()
+                torch.cuda.synchronize()
+                plan.append([f"{hw[1]}x{hw[0]}_{dt}_{k}", 1 + args.reps])
+            del legs, outs, keep
+            torch.cuda.empty_cache()
+    ctx.close()
+    print(json.dumps({"plan": plan}))
+
+
+def aa_trace_summary(trace_dir, plan):
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        return {"error": f"no kernel trace under {trace_dir}"}
+    rows = []
+    with open(files[0], newline="") as f:
+        for row in csv.DictReader(f):
+            name = row.get("Kernel_Name") or row.get("Name") or ""
+            if "hvq_yuv_resample_kernel" in name or "hvq_yuv_tensor_kernel" in name:
+                rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), name.split("(")[0],
+                             row.get("VGPR_Count"), row.get("LDS_Block_Size")))
+    rows.sort()
+    if len(rows) != sum(c for _l, c in plan):
+        return {"error": f"{len(rows)} export launches in the trace, {sum(c for _l, c in plan)} planned"}
+    res, at = {}, 0
+    for label, count in plan:
+        part = rows[at + 1:at + count]                                            # without the warm-up launch
+        at += count
+        d = sorted(r[1] for r in part)
+        res[label] = {"kernel": part[0][2], "launches": len(d), "median_us": round(statistics.median(d) / 1e3, 1),
+                      "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1), "lds": part[0][4]}
+    return res
+
+
 def trace_summary(trace_dir, n):
     """median / min of every export kernel in the kernel trace -> share of 8 TB/s"""
     files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
@@ -156,7 +262,8 @@ def run(cmd, limit, log):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("identity", "route"), default=None)
+    ap.add_argument("--child", choices=("identity", "route", "aa", "aa_trace"), default=None)
+    ap.add_argument("--aa-streams", type=int, default=16, help="streams of 8 resident pictures for the aa steps (16: 128 pictures)")
     ap.add_argument("--streams", type=int, default=128)
     ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
     ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
@@ -168,11 +275,11 @@ def main():
     ap.add_argument("--out-dir", default="export_float_bench_out")
     args = ap.parse_args()
     if args.child:
-        return {"identity": child_identity, "route": child_route}[args.child](args)
+        return {"identity": child_identity, "route": child_route, "aa": child_aa, "aa_trace": child_aa_trace}[args.child](args)
     os.makedirs(args.out_dir, exist_ok=True)
     me = [sys.executable, os.path.abspath(__file__)]
     common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps),
-              "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
+              "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--aa-streams", str(args.aa_streams)]
     for step in args.steps.split(","):
         print(f"# step {step}", flush=True)
         if step == "trace":
@@ -182,6 +289,13 @@ def main():
             res = {"calls": json.loads(line), "kernels": trace_summary(tdir, args.streams * args.per)}
         elif step == "route":
             res = json.loads(run(me + ["--child", "route"] + common, args.step_timeout, os.path.join(args.out_dir, "route.log")))
+        elif step == "aa":
+            res = json.loads(run(me + ["--child", "aa"] + common, args.step_timeout, os.path.join(args.out_dir, "aa.log")))
+        elif step == "aa_trace":
+            tdir = os.path.join(args.out_dir, "aa_trace")
+            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "aa_trace"] + common,
+                       args.step_timeout, os.path.join(args.out_dir, "aa_trace.log"))
+            res = aa_trace_summary(tdir, json.loads(line)["plan"])
         else:
             sys.exit(f"unknown step {step}")
         line = json.dumps({step: res})
