@@ -292,11 +292,13 @@ struct HvqContext {
     size_t arena_cap_alt = 0;
     int arena_id = 0;                  /* which of the two the current one is */
     bool arena_waited = false;         /* copy_stream already waits for the last batch that used the current arena */
+    bool arena_host_ready = false;     /* the host has waited for that batch's upload: it may write into the current arena (arena_host_wait) */
     bool resv_active = false;          /* hvq_arena_reserve: [resv_base, resv_base + resv_bytes) of the arena being filled is the caller's to write */
     size_t resv_base = 0, resv_bytes = 0;
     hipStream_t copy_stream = nullptr, read_stream = nullptr;
     hipEvent_t ev_read = nullptr;
     hipEvent_t ev_copy = nullptr, ev_arena_free[2] = { nullptr, nullptr };
+    hipEvent_t ev_h2d[2] = { nullptr, nullptr };      /* per arena: its last batch's bitstreams / blobs have left the pinned arena */
     std::vector<Pending> pending;
     /* batch in flight */
     bool fl_active = false;
@@ -396,8 +398,24 @@ static int export_drain(HvqContext *c)
     return HVQ_OK;
 }
 
+/* Before the HOST writes into the arena being filled: the upload of the batch that used it two flushes ago has run.  The arena is pinned
+ * memory; that upload (arena_upload: copy commands on the copy stream) reads it when the GPU gets there, not when it is queued -- a caller
+ * that submits and flushes small batches faster than the GPU drains them (seven clips opened, submitted and flushed back to back) used to
+ * overwrite bitstreams and blobs that had not been copied yet, and the older batch was then parsed or reconstructed from the newer one's
+ * bytes.  Once per arena turn, at its first write (arena_reserve: every submit path reserves before it writes); the event is the upload's
+ * own (ev_h2d, begin_upload), not the end of the batch: the host copy of batch k + 1 still runs beside the reconstruction of batch k - 1.
+ * hvq_flush_next knows the arena idle without asking (arena_idle) and never waits here. */
+static int arena_host_wait(HvqContext *c)
+{
+    if (c->arena_host_ready) return HVQ_OK;
+    if (!c->arena_idle[c->arena_id]) HIPCHK(hipEventSynchronize(c->ev_h2d[c->arena_id]));
+    c->arena_host_ready = true;
+    return HVQ_OK;
+}
+
 static int arena_reserve(HvqContext *c, size_t need)
 {
+    { int rcw = arena_host_wait(c); if (rcw) return rcw; }
     if (c->arena_used + need <= c->arena_cap) return HVQ_OK;
     if (c->resv_active) return fail(HVQ_E_STATE, "the arena would have to grow while a reservation of it is outstanding (hvq_submit_many_arena first)");
     size_t ncap = c->arena_cap ? c->arena_cap : (size_t)64 << 20;
@@ -559,6 +577,8 @@ HVQ_EXPORT int hvq_context_create(int device, HvqContext **out)
     }
     HIPCHK(hipEventCreateWithFlags(&c->ev_arena_free[0], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_arena_free[1], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_h2d[0], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_h2d[1], hipEventDisableTiming));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
     guard.c = nullptr;
@@ -606,6 +626,7 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     for (auto &set : c->pin) for (auto &b : set) if (b.p) (void)hipHostFree(b.p);
     if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
     for (auto e : c->ev_arena_free) if (e) (void)hipEventDestroy(e);
+    for (auto e : c->ev_h2d) if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->read_stream) { (void)hipStreamSynchronize(c->read_stream); (void)hipStreamDestroy(c->read_stream); }
     for (int q = 1; q < 4; ++q) {
@@ -1562,6 +1583,7 @@ static int begin_upload(HvqContext *c)
     /* 1. descriptors / bitstreams -> HBM; the compute stream waits for the copy stream */
     { int rc = arena_upload(c, c->arena_used); if (rc) return rc; }
     HIPCHK(hipEventRecord(c->ev_copy, c->copy_stream));
+    HIPCHK(hipEventRecord(c->ev_h2d[c->arena_id], c->copy_stream));           /* the host may write this arena again behind this (arena_host_wait) */
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_copy, 0));
     return HVQ_OK;
 }
@@ -1601,7 +1623,7 @@ static int begin_rest(HvqContext *c, int rc)
     std::swap(c->dev_arena, c->dev_arena_alt);
     std::swap(c->arena_cap, c->arena_cap_alt);
     c->arena_id ^= 1;
-    c->arena_used = 0; c->arena_uploaded = 0; c->arena_waited = false;
+    c->arena_used = 0; c->arena_uploaded = 0; c->arena_waited = false; c->arena_host_ready = false;
     c->resv_active = false;            /* a reservation that was never submitted goes with its arena */
     c->fl_active = true;
     if (!rc) rc = build_tiles(c);

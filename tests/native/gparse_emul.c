@@ -50,24 +50,17 @@ static void flat_tail(GPic *g)
 
 /* mode 0: chains only (round 1's schedule); 1: flat path with the chains as fallback; 2: flat path, fail instead of
  * falling back (so that tests can tell which pictures the flat path serves) */
-int gparse_emul2(const uint8_t *pic, uint32_t len, int frame_type, int w, int h, int hs, int vs, int is15,
-                 uint8_t *blob, uint32_t cap, uint8_t *nest_out, HvqParseResult *res, int mode)
+/* One picture as the parse kernel sees it: the job record's own pointers (bitstream, blob, scratch, nest), nothing copied.  The fake device
+ * (tests/native/fake_kernels.cpp) runs the runtime's parse launches through this; gparse_emul2 below builds a job around private buffers.
+ * Returns 1 in mode 2 when the flat path hands the picture back (nothing is written to *res then), else 0. */
+int gparse_emul_job(const HvqParseJob *jobp, HvqParseResult *res, int mode)
 {
-    const uint32_t nd = (len + 3) / 4 + 8;
-    uint32_t *d = calloc(nd, 4);
-    uint8_t *scratch = calloc(gparse_emul_scratch_bytes(w, h, hs, vs) + 64, 1);
+    const HvqParseJob job = *jobp;
+    const int w = job.width, frame_type = job.frame_type;
     uint8_t *rowbuf = malloc(3 * (size_t)(w / 4 + 2));
     GPic *g = calloc(1, sizeof *g);
     GCode *codes = calloc(GC_COUNT, sizeof *codes);
-    if (!d || !scratch || !rowbuf || !g || !codes) return -1;
-    memcpy(d, pic, len);
-    HvqParseJob job;
-    memset(&job, 0, sizeof job);
-    job.pic = (uint64_t)(uintptr_t)d; job.blob = (uint64_t)(uintptr_t)blob; job.scratch = (uint64_t)(uintptr_t)scratch;
-    job.nest_out = (uint64_t)(uintptr_t)nest_out;
-    job.len = len; job.pic_dwords = nd; job.cap = cap;
-    job.width = (uint16_t)w; job.height = (uint16_t)h; job.frame_type = (uint8_t)frame_type;
-    job.h_samp = (uint8_t)hs; job.v_samp = (uint8_t)vs; job.is15 = (uint8_t)is15;
+    if (!rowbuf || !g || !codes) { free(rowbuf); free(g); free(codes); return -1; }
 
     uint32_t extra = 0, retried = 0;
     int flat = mode != 0;
@@ -121,7 +114,7 @@ again:
         }
         if (!g->retry) flat_tail(g);
         if (g->retry && !g->status) {
-            if (mode == 2) { free(d); free(scratch); free(rowbuf); free(g); free(codes); return 1; }
+            if (mode == 2) { free(rowbuf); free(g); free(codes); return 1; }
             flat = 0; retried = 1;
             goto again;
         }
@@ -159,8 +152,28 @@ again:
     for (int t = 0; t < NTHR; ++t) gp_reads_check(g, t, NTHR);
     gp_result(g, res, extra);
     res->pad[0] = retried;
-    free(d); free(scratch); free(rowbuf); free(g); free(codes);
+    free(rowbuf); free(g); free(codes);
     return 0;
+}
+
+int gparse_emul2(const uint8_t *pic, uint32_t len, int frame_type, int w, int h, int hs, int vs, int is15,
+                 uint8_t *blob, uint32_t cap, uint8_t *nest_out, HvqParseResult *res, int mode)
+{
+    const uint32_t nd = (len + 3) / 4 + 8;
+    uint32_t *d = calloc(nd, 4);
+    uint8_t *scratch = calloc(gparse_emul_scratch_bytes(w, h, hs, vs) + 64, 1);
+    if (!d || !scratch) { free(d); free(scratch); return -1; }
+    memcpy(d, pic, len);
+    HvqParseJob job;
+    memset(&job, 0, sizeof job);
+    job.pic = (uint64_t)(uintptr_t)d; job.blob = (uint64_t)(uintptr_t)blob; job.scratch = (uint64_t)(uintptr_t)scratch;
+    job.nest_out = (uint64_t)(uintptr_t)nest_out;
+    job.len = len; job.pic_dwords = nd; job.cap = cap;
+    job.width = (uint16_t)w; job.height = (uint16_t)h; job.frame_type = (uint8_t)frame_type;
+    job.h_samp = (uint8_t)hs; job.v_samp = (uint8_t)vs; job.is15 = (uint8_t)is15;
+    const int rc = gparse_emul_job(&job, res, mode);
+    free(d); free(scratch);
+    return rc;
 }
 
 int gparse_emul(const uint8_t *pic, uint32_t len, int frame_type, int w, int h, int hs, int vs, int is15,
