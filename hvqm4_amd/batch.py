@@ -234,6 +234,40 @@ class Context:
             check(lib().hvq_export_resampled(self._h, n, a_s, a_o, dtype, int(filt), (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
                                              C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
 
+    def picture_metrics(self, sids, ordinals, ref=None, out=None):
+        """hvq_picture_metrics: per plane (Y, U, V) the exact integers sum_a, sum_b, sum |a - b| and sum (a - b)^2 of resident
+        pictures a = (sids[i], ordinals[i]) against their references, in one launch on torch's current stream, without a host
+        synchronisation -> int64 CUDA tensor [n, 3, 4] (`out`, if given: such a tensor, contiguous; it is overwritten whole).
+        `ref`: None (every picture against zeros: sum, sum of squares -> mean and variance) or a list with one entry per picture:
+        None (zeros), (sid, ordinal) -- a resident picture of the same geometry, of any stream -- or a contiguous uint8 CUDA tensor of
+        pic_bytes(sid) elements laid out as the pictures are (Y | U | V; the caller keeps it alive until the work has run).
+        hvqm4_amd.metrics turns the records into PSNR, mean absolute difference, mean and variance.  Ordering and slot safety are
+        export()'s."""
+        import torch
+        from .export import check_one_hip_runtime
+        from .metrics import HvqMetricsRef, references
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
+        if out is None:
+            out = torch.empty((n, 3, 4), dtype=torch.int64, device="cuda")
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 3, 4) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 3, 4)")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_r = None if refs is None else C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
+        check(lib().hvq_picture_metrics(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
     def rgb_bench(self, reps: int):
         """-> (gpu_ms, bytes_per_rep, pictures): batched display epilogue over the newest picture of every stream"""
         ms, by, n = C.c_float(0), C.c_uint64(0), C.c_uint32(0)

@@ -253,5 +253,28 @@ _Static_assert(sizeof(HvqResampleJob) == 96, "HvqResampleJob must be 96 bytes");
 _Static_assert(sizeof(HvqResampleJob) % 16 == 0, "job tables are uploaded in 16-byte units");
 #endif
 
+/* one picture pair of the metrics launch (hvq_metrics_kernel, hvq_picture_metrics): picture `a` and its reference `b`, both Y|U|V tightly
+ * packed (a slot, or the caller's memory in a slot's layout), and the output record uint64 [3 planes][4] = { sum_a, sum_b, sad, sse }
+ * the launch adds into (zeroed in front of it).  b = 0: a reference of zeros, nothing is loaded for it.  A plane is units[p] 16-byte
+ * units long (widths and heights are multiples of 8: every plane starts on a 16-byte boundary and is a multiple of 16 bytes); a
+ * workgroup takes HVQ_MT_CHUNK consecutive units of ONE plane, wg_first[p] is the first workgroup of plane p (wg_first[0] = 0,
+ * wg_first[3] = the picture's workgroups: those past it leave).  Every member is a dword or a qword (scalar loads); 64 bytes. */
+#define HVQ_MT_LANES  256u          /* lanes of a workgroup */
+#define HVQ_MT_UNITS  4u            /* 16-byte units of a lane, HVQ_MT_LANES apart: 64 samples of a and of b */
+#define HVQ_MT_CHUNK  (HVQ_MT_LANES * HVQ_MT_UNITS)
+typedef struct HvqMetricsJob {
+    uint64_t a, b;                     /* device addresses, multiples of 16; b = 0: zeros */
+    uint64_t out;                      /* device address of the record, a multiple of 8 */
+    uint32_t plane_off[3];             /* byte offset of plane p inside a picture */
+    uint32_t units[3];                 /* 16-byte units of plane p */
+    uint32_t wg_first[4];
+} HvqMetricsJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqMetricsJob) == 64, "HvqMetricsJob must be 64 bytes");
+#else
+_Static_assert(sizeof(HvqMetricsJob) == 64, "HvqMetricsJob must be 64 bytes");
+#endif
+
 
 #endif

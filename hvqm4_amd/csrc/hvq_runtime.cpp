@@ -66,6 +66,8 @@ extern "C" void hvq_set_stamps(unsigned long long *p);
 extern "C" hipError_t hvq_launch_rgb(const void *jobs_dev, int njobs, int max_lanes, int wide, int format, hipStream_t stream);
 extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max_lanes, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
 extern "C" hipError_t hvq_launch_resample(const void *jobs_dev, int njobs, int max_wgs, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
+/* hvq_metrics.hip.  Weak: a build of the runtime without that unit links, and hvq_picture_metrics then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_metrics(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -2367,6 +2369,68 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
     }
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqRgbJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_rgb(tab, n, max_lanes, wide, format, st); });
+}
+
+/* Picture metrics (include/hvqm4_amd.h: the specification): a third member of the export chain.  The pictures of both sides are looked
+ * up, and the batch in flight ended, exactly as the exports do it; the memset of the records and the launch go behind the job table
+ * on the caller's stream (export_enqueue). */
+HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
+                                   uint64_t *out, void *hip_stream)
+{
+    static_assert(sizeof(HvqMetricsJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    /* both sides of every pair decide whether the batch in flight has to end */
+    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
+    for (int i = 0; ref && i < n; ++i)
+        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
+    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    std::vector<HvqMetricsJob> jobs((size_t)n);
+    uint32_t max_wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!a) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const uint8_t *b = nullptr;
+        if (ref && ref[i].stream >= 0) {
+            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
+            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
+            if (!b) return rc;
+            const Stream &r = c->streams[(size_t)ref[i].stream];
+            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
+                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
+                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
+        } else if (ref && ref[i].stream != -1) {
+            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory or zeros)", i, ref[i].stream);
+        } else if (ref && ref[i].ptr) {
+            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
+            b = (const uint8_t *)ref[i].ptr;
+        }
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
+        HvqMetricsJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
+        j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 12u);
+        const size_t len[3] = { ny, nc, nc };
+        size_t off = 0;
+        for (int p = 0; p < 3; ++p) {
+            j.plane_off[p] = (uint32_t)off;
+            j.units[p] = (uint32_t)(len[p] / 16u);
+            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_MT_CHUNK - 1u) / HVQ_MT_CHUNK;
+            off += len[p];
+        }
+        max_wgs = std::max(max_wgs, j.wg_first[3]);
+    }
+    if (!hvq_launch_metrics) return fail(HVQ_E_NOGPU, "this build of the library has no metrics kernel (hvq_metrics.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqMetricsJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) {
+                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 96u, st);       /* the launch adds into the records */
+                              return e != hipSuccess ? e : hvq_launch_metrics(tab, n, max_wgs, st);
+                          });
 }
 
 /* hvq_export_tensors' checks of one destination, for hvq_export_resampled: output size, crop, pitches, alignment (es = element size).

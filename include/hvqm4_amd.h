@@ -269,6 +269,31 @@ int  hvq_resample_table(int n_src, int n_out, int32_t *first, int32_t *count, fl
  * (upscales, identity, very large ratios).  The values do not depend on it. */
 int  hvq_resample_tile_rows(int crop_w, int crop_h, int out_w, int out_h);
 
+/* Metrics of resident pictures, computed where they lie: for `n` pairs (a_i, b_i), of any streams, sizes and samplings, in ONE kernel
+ * launch on the caller's HIP stream and without a host synchronisation, per plane p = Y, U, V over all samples of the plane
+ *       sum_a = sum a     sum_b = sum b     sad = sum |a - b|     sse = sum (a - b)^2
+ * as exact integers.  out: `n` records of uint64_t [3 planes Y, U, V][4] = { sum_a, sum_b, sad, sse }, 96 bytes each, dense, in call
+ * order, in DEVICE memory; the call writes all 96 * n bytes whatever they held before (the caller does not zero them).  Mean and
+ * variance of a plane, the mean absolute difference of two pictures (scene changes, near-duplicates) and PSNR follow from them.
+ *   a_i = picture (streams[i], ordinals[i]).  Its reference b_i:
+ *     ref[i].stream >= 0                 the resident picture (ref[i].stream, ref[i].ordinal), of any stream of the same width, height
+ *                                        and sampling as a_i; ref[i].ptr must be NULL.  A picture against itself: sad = sse = 0;
+ *     ref[i].stream == -1, ptr != NULL   the caller's device memory, laid out as hvq_picture_device_ptr lays a picture out (Y | U | V
+ *                                        tightly packed, hvq_stream_pic_bytes long); ptr must be a multiple of 16.  The library
+ *                                        cannot check its size; it is read when the work runs on `hip_stream`;
+ *     ref[i].stream == -1, ptr == NULL   a picture of zeros: sum_b = 0, sad = sum_a, sse = sum a^2 (mean and variance);
+ *     ref == NULL                        every picture against zeros.
+ *   Lookup, HVQ_E_STATE cases (a or b queued but not flushed, slot reused, dropped), ordering and slot safety are
+ *   hvq_export_pictures'; the batch in flight is ended only when an a_i or a resident b_i belongs to it; the call joins the same export
+ *   chain (it waits for the previous export of any kind, later slot writers wait for it).  HVQ_E_ARG for a bad stream or ordinal, a
+ *   geometry mismatch between a_i and b_i, ptr together with stream >= 0, a stream below -1, a ptr that is not a multiple of 16, a null
+ *   `out` or one that is not a multiple of 8, n above 65535.  Every argument is checked before anything is enqueued: a refused call
+ *   enqueues nothing and leaves `out` untouched.  HVQ_E_NOGPU (after those checks) from a build without the metrics kernel.
+ *   The sums do not depend on the order the GPU adds them in: the same call gives the same bits every time. */
+typedef struct HvqMetricsRef { int32_t stream, ordinal; const void *ptr; } HvqMetricsRef;
+int  hvq_picture_metrics(HvqContext *ctx, int n, const int *streams, const int *ordinals,
+                         const HvqMetricsRef *ref, uint64_t *out, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
