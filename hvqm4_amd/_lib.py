@@ -120,6 +120,9 @@ SYMBOLS = {
     "hvq_export_resampled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "hvq_picture_metrics": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_ssim_windows": (C.c_int, [C.c_int] * 4 + [C.c_void_p]),
+    "hvq_picture_ssim": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,
                                      C.POINTER(C.c_size_t)]),
     "hvq_resample_tile_rows": (C.c_int, [C.c_int] * 4),

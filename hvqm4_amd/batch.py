@@ -268,6 +268,67 @@ class Context:
         check(lib().hvq_picture_metrics(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def picture_ssim(self, sids, ordinals, ref, out=None, maps=False):
+        """hvq_picture_ssim: windowed SSIM (8 x 8 windows 4 samples apart, the arithmetic of x264 / ffmpeg's ssim filter, specified in
+        include/hvqm4_amd.h) of resident pictures a = (sids[i], ordinals[i]) against their references, in one launch on torch's
+        current stream, without a host synchronisation -> int64 CUDA tensor [n, 3, 2] = per plane (sum_f, windows) (`out`, if given:
+        such a tensor, contiguous; it is overwritten whole).  `ref` is required: a list with one entry per picture, (sid, ordinal)
+        -- a resident picture of the same geometry -- or a contiguous uint8 CUDA tensor of pic_bytes(sid) elements laid out as the
+        pictures are.  maps=True: -> (out, maps), maps a list of n triples of float32 CUDA tensors [rows_p, cols_p], the window
+        values of Y, U, V (views of one allocation per pair).  hvqm4_amd.metrics.ssim / ssim_all / ssim_db read the records.
+        Ordering and slot safety are export()'s."""
+        import torch
+        from .export import check_one_hip_runtime
+        from .metrics import HvqMetricsRef, references
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        if ref is None:
+            raise ValueError("picture_ssim needs a reference for every picture (SSIM against zeros means nothing)")
+        refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
+        for i, r in enumerate(refs):
+            if r[0] < 0 and r[2] is None:
+                raise ValueError(f"reference {i} is None: SSIM against zeros means nothing")
+        if out is None:
+            out = torch.empty((n, 3, 2), dtype=torch.int64, device="cuda")
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 3, 2) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 3, 2)")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        views, a_m = None, None
+        if maps:
+            views, ptrs = [], []
+            for s in sids:
+                dims = self._ssim_dims(s)
+                buf = torch.empty(sum(r * c for r, c in dims), dtype=torch.float32, device=out.device)
+                at, tri = 0, []
+                for r, c in dims:
+                    tri.append(buf[at:at + r * c].view(r, c))
+                    at += r * c
+                views.append(tuple(tri))
+                ptrs.append(buf.data_ptr())
+            a_m = C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_r = C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
+        check(lib().hvq_picture_ssim(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), a_m, C.c_void_p(stream)))
+        return (out, views) if maps else out
+
+    def _ssim_dims(self, sid):
+        """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
+        from .metrics import ssim_windows
+        w, h = self._geom[sid][:2]
+        y = w * h
+        c = (self.pic_bytes(sid) - y) // 2
+        hs, vs = {y // 4: (2, 2), y // 2: (2, 1), y: (1, 1)}[c]
+        return ssim_windows(w, h, hs, vs)
+
     def rgb_bench(self, reps: int):
         """-> (gpu_ms, bytes_per_rep, pictures): batched display epilogue over the newest picture of every stream"""
         ms, by, n = C.c_float(0), C.c_uint64(0), C.c_uint32(0)

@@ -276,5 +276,35 @@ static_assert(sizeof(HvqMetricsJob) == 64, "HvqMetricsJob must be 64 bytes");
 _Static_assert(sizeof(HvqMetricsJob) == 64, "HvqMetricsJob must be 64 bytes");
 #endif
 
+/* one picture pair of the SSIM launch (hvq_ssim_kernel, hvq_picture_ssim): picture `a` and its reference `b`, both Y|U|V tightly packed, the
+ * output record int64 [3 planes][2] = { sum_f, windows } the launch adds into (zeroed in front of it), and the pair's map of window values
+ * (0: none).  Plane p is bw[p] x bh[p] blocks of 4 x 4 samples, rows 4 * bw[p] bytes apart, and has (bh[p] - 1) x (bw[p] - 1) windows; its
+ * map starts map_off[p] floats into the pair's map.  A workgroup takes one tile of at most HVQ_SS_TR x HVQ_SS_TC windows of ONE plane, that
+ * is (HVQ_SS_TR + 1) x (HVQ_SS_TC + 1) blocks; plane p has tiles_x[p] tiles per tile row, wg_first[p] is its first workgroup (wg_first[0]
+ * = 0, wg_first[3] = the pair's workgroups: those past it leave).  A plane without a window (bw or bh below 2) has no workgroup.  Every
+ * member is a dword or a qword (scalar loads); 112 bytes. */
+#define HVQ_SS_LANES  256u          /* lanes of a workgroup */
+#define HVQ_SS_TR     15u           /* window rows of a tile: 16 block rows */
+#define HVQ_SS_TC     63u           /* window columns of a tile: 64 block columns */
+typedef struct HvqSsimJob {
+    uint64_t a, b;                     /* device addresses, multiples of 16 */
+    uint64_t out;                      /* device address of the record, a multiple of 8 */
+    uint64_t map;                      /* device address of the pair's map, a multiple of 4; 0: no map */
+    uint32_t plane_off[3];             /* byte offset of plane p inside a picture */
+    uint32_t map_off[3];               /* floats in front of plane p's windows inside the map */
+    uint32_t bw[3], bh[3];             /* blocks per row, block rows */
+    uint32_t tiles_x[3];
+    uint32_t wg_first[4];
+    uint32_t pad;
+} HvqSsimJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqSsimJob) == 112, "HvqSsimJob must be 112 bytes");
+static_assert(sizeof(HvqSsimJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+#else
+_Static_assert(sizeof(HvqSsimJob) == 112, "HvqSsimJob must be 112 bytes");
+_Static_assert(sizeof(HvqSsimJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

@@ -68,6 +68,8 @@ extern "C" hipError_t hvq_launch_tensor(const void *jobs_dev, int njobs, int max
 extern "C" hipError_t hvq_launch_resample(const void *jobs_dev, int njobs, int max_wgs, int dtype, const HvqTensorNorm *nm, hipStream_t stream);
 /* hvq_metrics.hip.  Weak: a build of the runtime without that unit links, and hvq_picture_metrics then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_metrics(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
+/* hvq_ssim.hip.  Weak for the same reason: hvq_picture_ssim then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_ssim(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -2430,6 +2432,92 @@ HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, con
                           [=](const void *tab, hipStream_t st) {
                               hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 96u, st);       /* the launch adds into the records */
                               return e != hipSuccess ? e : hvq_launch_metrics(tab, n, max_wgs, st);
+                          });
+}
+
+/* Windows of SSIM per plane (include/hvqm4_amd.h): host only */
+HVQ_EXPORT int hvq_ssim_windows(int width, int height, int h_samp, int v_samp, int32_t dims[3][2])
+{
+    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
+    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
+    hvq_parser_destroy(p);
+    const int cw = width >> (h_samp == 2), ch = height >> (v_samp == 2);
+    const int w[3] = { width, cw, cw }, h[3] = { height, ch, ch };
+    int total = 0;
+    for (int k = 0; k < 3; ++k) {
+        const int rows = std::max(h[k] / 4 - 1, 0), cols = std::max(w[k] / 4 - 1, 0);
+        if (dims) { dims[k][0] = rows; dims[k][1] = cols; }
+        total += rows * cols;
+    }
+    return total;
+}
+
+/* Windowed SSIM (include/hvqm4_amd.h: the specification): a fourth member of the export chain, hvq_picture_metrics' lookup, refusals and
+ * ordering; the memset of the records and the launch go behind the job table on the caller's stream (export_enqueue). */
+HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
+                                int64_t *out, float *const *maps, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    if (!ref) return fail(HVQ_E_ARG, "SSIM needs a reference for every picture (ref is NULL)");
+    for (int i = 0; maps && i < n; ++i)
+        if ((uintptr_t)maps[i] & 3u) return fail(HVQ_E_ARG, "map %d: the pointer must be a multiple of 4", i);
+    /* both sides of every pair decide whether the batch in flight has to end */
+    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
+    for (int i = 0; i < n; ++i)
+        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
+    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    std::vector<HvqSsimJob> jobs((size_t)n);
+    uint32_t max_wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!a) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const uint8_t *b = nullptr;
+        if (ref[i].stream >= 0) {
+            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
+            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
+            if (!b) return rc;
+            const Stream &r = c->streams[(size_t)ref[i].stream];
+            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
+                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
+                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
+        } else if (ref[i].stream != -1) {
+            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
+        } else if (ref[i].ptr) {
+            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
+            b = (const uint8_t *)ref[i].ptr;
+        } else {
+            return fail(HVQ_E_ARG, "reference %d: SSIM against a picture of zeros means nothing (stream -1 needs a pointer)", i);
+        }
+        const uint32_t cw = (uint32_t)(s.w >> s.wshift), ch = (uint32_t)(s.h >> s.hshift);
+        const uint32_t w[3] = { (uint32_t)s.w, cw, cw }, h[3] = { (uint32_t)s.h, ch, ch };
+        if (((uintptr_t)a | w[0] | w[1] | h[0] | h[1]) & 3u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 4 x 4 blocks", i, streams[i]);
+        HvqSsimJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
+        j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 6u);
+        j.map = (uint64_t)(uintptr_t)(maps ? maps[i] : nullptr);
+        uint32_t off = 0, moff = 0;
+        for (int p = 0; p < 3; ++p) {
+            j.plane_off[p] = off; j.map_off[p] = moff;
+            j.bw[p] = w[p] / 4u; j.bh[p] = h[p] / 4u;
+            const uint32_t rows = j.bh[p] ? j.bh[p] - 1u : 0u, cols = j.bw[p] ? j.bw[p] - 1u : 0u;
+            const uint32_t tiles_y = rows && cols ? (rows + HVQ_SS_TR - 1u) / HVQ_SS_TR : 0u;
+            j.tiles_x[p] = rows && cols ? (cols + HVQ_SS_TC - 1u) / HVQ_SS_TC : 1u;
+            j.wg_first[p + 1] = j.wg_first[p] + tiles_y * j.tiles_x[p];
+            off += w[p] * h[p]; moff += rows * cols;
+        }
+        max_wgs = std::max(max_wgs, j.wg_first[3]);
+    }
+    if (!hvq_launch_ssim) return fail(HVQ_E_NOGPU, "this build of the library has no SSIM kernel (hvq_ssim.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqSsimJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) {
+                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 48u, st);       /* the launch adds into the records */
+                              return e != hipSuccess ? e : hvq_launch_ssim(tab, n, max_wgs, st);
                           });
 }
 

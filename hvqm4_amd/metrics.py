@@ -2,6 +2,9 @@
 
 A record is int64 [3 planes Y, U, V][4] = (sum_a, sum_b, sad, sse).  The helpers below are pure torch, take CPU or CUDA tensors of
 shape [..., 3, 4] and never synchronise; torch is imported lazily, the rest of the package works without it.
+
+A record of hvq_picture_ssim / Context.picture_ssim is int64 [3 planes][2] = (sum_f, windows): the sum of the fixed-point window values
+(SSIM_ONE = 2^24 is 1.0) and the number of windows; ssim_windows, ssim, ssim_all and ssim_db belong to it.
 """
 from __future__ import annotations
 
@@ -9,6 +12,8 @@ import ctypes as C
 from typing import Callable, List, Optional, Tuple
 
 SUM_A, SUM_B, SAD, SSE = 0, 1, 2, 3
+SSIM_ONE = 1 << 24                  # HVQ_SSIM_ONE
+SUM_F, WINDOWS = 0, 1
 
 
 class HvqMetricsRef(C.Structure):
@@ -96,3 +101,43 @@ def mean_var(m, samples):
     mean = m[..., SUM_A].to(torch.float64) / cnt
     var = (m[..., SSE].to(torch.float64) / cnt - mean * mean).clamp_min(0.0)
     return mean, var
+
+
+def ssim_windows(width: int, height: int, h_samp: int = 2, v_samp: int = 2) -> Tuple[Tuple[int, int], Tuple[int, int], Tuple[int, int]]:
+    """(rows, cols) of the 8 x 8 SSIM windows, 4 samples apart, of the planes Y, U, V: hvq_ssim_windows.  A plane below 8 samples in a
+    direction has none: (0, cols) or (rows, 0)."""
+    y, c, _c = plane_samples(width, height, h_samp, v_samp)
+    cw = width >> (h_samp == 2)
+    dims = ((height, width), (c // cw if cw else 0, cw), (c // cw if cw else 0, cw))
+    return tuple((max(h // 4 - 1, 0), max(w // 4 - 1, 0)) for h, w in dims)
+
+
+def _ssim_parts(rec):
+    import torch
+    if rec.shape[-2:] != (3, 2):
+        raise ValueError(f"SSIM records have shape [..., 3, 2], not {tuple(rec.shape)}")
+    return rec[..., SUM_F].to(torch.float64), rec[..., WINDOWS].to(torch.float64)
+
+
+def ssim(rec):
+    """mean SSIM per plane, float64 [..., 3]: sum_f / (2^24 windows); NaN for a plane without a window"""
+    import torch
+    f, n = _ssim_parts(rec)
+    return torch.where(n == 0, torch.full_like(f, float("nan")), f / (SSIM_ONE * n.clamp_min(1.0)))
+
+
+def ssim_all(rec, samples):
+    """the mean over the planes weighted by their sample counts (what ffmpeg prints as "All"), float64 [...]; planes without a window
+    are left out of both sums.  `samples` = plane_samples(...), or anything that broadcasts against [..., 3]."""
+    import torch
+    f, n = _ssim_parts(rec)
+    cnt = torch.as_tensor(samples, dtype=torch.float64, device=rec.device) * (n > 0)
+    return ((f / (SSIM_ONE * n.clamp_min(1.0))) * cnt).sum(-1) / cnt.sum(-1)
+
+
+def ssim_db(x):
+    """-10 log10(1 - x), inf at 1"""
+    import torch
+    x = torch.as_tensor(x, dtype=torch.float64)
+    db = -10.0 * torch.log10((1.0 - x).clamp_min(1e-300))
+    return torch.where(x >= 1.0, torch.full_like(db, float("inf")), db)

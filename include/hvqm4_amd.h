@@ -294,6 +294,47 @@ typedef struct HvqMetricsRef { int32_t stream, ordinal; const void *ptr; } HvqMe
 int  hvq_picture_metrics(HvqContext *ctx, int n, const int *streams, const int *ordinals,
                          const HvqMetricsRef *ref, uint64_t *out, void *hip_stream);
 
+/* Windowed SSIM of resident pictures, computed where they lie: for `n` pairs (a_i, b_i), of any streams, sizes and samplings, in ONE kernel
+ * launch on the caller's HIP stream and without a host synchronisation, per plane the exact fixed-point sum of the window values and
+ * the number of windows, and on request the map of window values.  The per-window arithmetic is that of x264 / ffmpeg's `ssim` filter
+ * for 8-bit pictures; this text is the authority.
+ *   Per plane p = Y, U, V of W x H samples (the library's geometries make every W and H a multiple of 4):
+ *   Blocks and windows.  bw = W / 4, bh = H / 4.  Block (r, c), 0 <= r < bh, 0 <= c < bw, is the 4 x 4 samples at rows 4r .. 4r + 3,
+ *       columns 4c .. 4c + 3.  Window (i, j), 0 <= i < bh - 1, 0 <= j < bw - 1, is the 8 x 8 samples of blocks (i .. i + 1, j .. j + 1):
+ *       windows step 4 samples in both directions.  rows = max(bh - 1, 0), cols = max(bw - 1, 0), windows = rows * cols.  A plane
+ *       narrower or lower than 8 samples (the 4 x 4 chroma of an 8 x 8 4:2:0 picture) has no window: its record is { 0, 0 }, not an error.
+ *   Window integers.  Over the 64 samples of the window, a from picture a and b from picture b:
+ *       s1 = sum a     s2 = sum b     ss = sum (a^2 + b^2)     s12 = sum a b
+ *       vars = 64 ss - s1^2 - s2^2          covar = 64 s12 - s1 s2
+ *       A = 2 s1 s2 + 416     B = 2 covar + 235963     C = s1^2 + s2^2 + 416     D = vars + 235963
+ *       416 = (int)(.01^2 255^2 64 + .5), 235963 = (int)(.03^2 255^2 64 63 + .5).  All of these fit a signed 32-bit integer: s1, s2 <=
+ *       16320, ss <= 8 323 200, |A|, |B|, C, D < 2^30.  B is odd, so never 0; A, C and D are positive.
+ *   Window value, in float32, one rounding per operation, nothing fused:  q = ((float)A * (float)B) / ((float)C * (float)D); the
+ *       conversions round to nearest even, the division is the correctly rounded one.
+ *   Exact reduction.  f = (int)rint(q * 16777216.0f): the product is exact (a power of two), rint rounds half to even, and for |q| >= 0.5
+ *       the product is an integer already.  sum_f = sum of f over the plane's windows, a 64-bit integer: the record does not depend on
+ *       the order the GPU adds in.  The mean SSIM of the plane is sum_f / (HVQ_SSIM_ONE * windows).  Identical planes: f == HVQ_SSIM_ONE
+ *       in every window.
+ *   out: `n` records of int64_t [3 planes Y, U, V][2] = { sum_f, windows }, 48 bytes each, dense, in call order, in DEVICE memory, a
+ *       multiple of 8; the call writes all 48 * n bytes whatever they held before.  `windows` is counted by the kernel (every wave adds
+ *       the number of windows it evaluated) and equals rows * cols.
+ *   ref: HvqMetricsRef as for hvq_picture_metrics, its two non-trivial forms: stream >= 0 -- a resident picture of the same geometry, of
+ *       any stream, ptr NULL; stream == -1 with ptr -- the caller's device memory, Y | U | V tightly packed, a multiple of 16.  SSIM
+ *       against zeros means nothing: ref == NULL (with n > 0) and { -1, *, NULL } are HVQ_E_ARG.
+ *   maps: NULL, or `n` pointers, each NULL or a device pointer that is a multiple of 4 to hvq_ssim_windows(...) floats: the windows of Y,
+ *       then U, then V, each plane row-major rows x cols, dense.  Element (i, j) is the q of window (i, j), the bits of the float before
+ *       scaling.  Every element is written exactly once, nothing outside those floats is written.
+ *   Lookup, HVQ_E_STATE cases, n <= 65535, the checks of `ref`, "every argument is checked before anything is enqueued: a refused call
+ *   leaves `out` and every map untouched", ending the batch in flight only when a requested picture belongs to it, ordering on
+ *   `hip_stream`, membership of the export chain and slot safety are hvq_picture_metrics'.  A NULL context is HVQ_E_ARG.  HVQ_E_NOGPU
+ *   (after those checks) from a build without the SSIM kernel. */
+#define HVQ_SSIM_ONE 16777216
+/* host only: rows / cols of windows per plane, dims[p] = { rows, cols } (dims may be NULL); returns the total (>= 0), or HVQ_E_GEOMETRY
+ * for a geometry hvq_stream_open refuses */
+int  hvq_ssim_windows(int width, int height, int h_samp, int v_samp, int32_t dims[3][2]);
+int  hvq_picture_ssim(HvqContext *ctx, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
+                      int64_t *out, float *const *maps, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);

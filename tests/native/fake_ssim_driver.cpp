@@ -1,0 +1,343 @@
+/*
+ * tests/native/fake_ssim_driver.cpp -- TEST INFRASTRUCTURE: a stand-alone program that drives hvq_picture_ssim of the runtime
+ * (hvqm4_amd/csrc/hvq_runtime.cpp, linked unchanged against the CPU fake device and tests/native/fake_ssim.cpp) through
+ * include/hvqm4_amd.h.  It writes what it read back and judges nothing: tests/test_ssim_cpu.py compares with tests/ssim_ref.py on the
+ * oracle's pictures.
+ *
+ *   fake_ssim_driver <scenario> <outdir> <golden dir>
+ *
+ * results.txt, one fact per line:
+ *   W <label> <clip a> <ordinal a> <form> <clip b> <ordinal b> <6 numbers>     one record read back: [Y, U, V][sum_f, windows]
+ *       form: pic (a resident reference), inv (the caller's memory: picture b with every byte inverted, 255 - x)
+ *   Q <label> <clip a> <ordinal a> <form> <clip b> <ordinal b> <guard words intact> <guard words> <n> <n hex words>
+ *       the pair's map read back, the bits of its floats, and the sentinel words behind it
+ *   R <label> <return code>                                                    a return code the test wants to see
+ *   S <label> <bytes that still hold the sentinel> <bytes>                     an output buffer after refused calls
+ * Caller-side resources (a stream, output records, maps, reference memory) come from the fake's HIP calls, as a caller's would from HIP.
+ */
+#include "fake_device.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/hvqm4_amd.h"
+
+struct Pic { int type; const uint8_t *p; size_t len; };
+struct Clip {
+    std::string name;
+    std::vector<uint8_t> data;
+    HvqH4mInfo info;
+    std::vector<Pic> pics;
+};
+
+static std::string g_golden, g_out;
+static FILE *g_res;
+static std::map<std::string, Clip> g_clips;
+static const uint32_t GUARD = 0xA5A5A5A5u;
+static const size_t GUARD_WORDS = 16;
+
+#define CHECK(expr) do { const int rc_ = (expr); if (rc_ < 0) { fprintf(stderr, "fake_ssim_driver: %s = %d: %s\n", #expr, rc_, hvq_last_error_string()); exit(3); } } while (0)
+#define HIP(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "fake_ssim_driver: %s failed\n", #expr); exit(3); } } while (0)
+
+static const Clip &clip(const std::string &name)
+{
+    auto it = g_clips.find(name);
+    if (it != g_clips.end()) return it->second;
+    Clip &c = g_clips[name];
+    c.name = name;
+    const std::string path = g_golden + "/" + name + ".h4m";
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "fake_ssim_driver: cannot open %s\n", path.c_str()); exit(2); }
+    fseek(f, 0, SEEK_END);
+    c.data.resize((size_t)ftell(f));
+    fseek(f, 0, SEEK_SET);
+    if (fread(c.data.data(), 1, c.data.size(), f) != c.data.size()) exit(2);
+    fclose(f);
+    CHECK(hvq_h4m_header(c.data.data(), c.data.size(), &c.info));
+    HvqH4mIter it2;
+    hvq_h4m_begin(&it2);
+    int type; uint32_t disp; const uint8_t *p; size_t len;
+    while (hvq_h4m_next(c.data.data(), c.data.size(), &it2, &type, &disp, &p, &len) == 1) c.pics.push_back(Pic{ type, p, len });
+    return c;
+}
+
+static int decode(HvqContext *ctx, const Clip &c, int extra = 3)
+{
+    const int sid = hvq_stream_open(ctx, c.info.width, c.info.height, c.info.h_samp, c.info.v_samp, c.info.is_1_5, (int)c.pics.size() + extra);
+    CHECK(sid);
+    for (const Pic &p : c.pics) CHECK(hvq_stream_submit(ctx, sid, p.type, p.p, p.len));
+    CHECK(hvq_flush(ctx));
+    return sid;
+}
+
+static hipStream_t caller_stream()
+{
+    hipStream_t s = nullptr;
+    HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+}
+
+/* one pair of a call and what the test is told about it */
+struct Pair { int sid, k; HvqMetricsRef ref; std::string clip_a, form, clip_b; int kb; int windows; bool map; };
+
+static int windows_of(const Clip &c)
+{
+    const int n = hvq_ssim_windows(c.info.width, c.info.height, c.info.h_samp, c.info.v_samp, nullptr);
+    CHECK(n);
+    return n;
+}
+
+static Pair against_picture(int sid, const Clip &a, int k, int sid_b, const Clip &b, int kb, bool map)
+{
+    return Pair{ sid, k, HvqMetricsRef{ sid_b, kb, nullptr }, a.name, "pic", b.name, kb, windows_of(a), map };
+}
+
+/* the caller's memory: picture kb of stream sid_b read back, every byte inverted, in device memory at `offset` bytes into an allocation */
+static Pair against_memory(HvqContext *ctx, int sid, const Clip &a, int k, int sid_b, const Clip &b, int kb, size_t offset, bool map, std::vector<void *> *keep)
+{
+    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid_b);
+    std::vector<uint8_t> host(pb);
+    CHECK(hvq_read_picture(ctx, sid_b, kb, host.data(), host.size()));
+    for (uint8_t &x : host) x = (uint8_t)(255 - x);
+    void *d = nullptr;
+    HIP(hipMalloc(&d, pb + offset));
+    keep->push_back(d);
+    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
+    return Pair{ sid, k, HvqMetricsRef{ -1, 0, (uint8_t *)d + offset }, a.name, "inv", b.name, kb, windows_of(a), map };
+}
+
+struct Call { int64_t *out; std::vector<float *> maps; std::vector<Pair> pairs; std::string label; };
+
+/* queue one call on `caller`; out and the maps are filled with 0xFF bytes first (the call must replace every one of them), behind each
+ * map lie GUARD_WORDS sentinel words (the call must leave them) */
+static Call call_ssim(HvqContext *ctx, const std::vector<Pair> &pairs, hipStream_t caller, const char *label)
+{
+    const int n = (int)pairs.size();
+    std::vector<int> sids, ords;
+    std::vector<HvqMetricsRef> refs;
+    std::vector<float *> maps;
+    bool any = false;
+    for (const Pair &p : pairs) {
+        sids.push_back(p.sid); ords.push_back(p.k); refs.push_back(p.ref);
+        float *m = nullptr;
+        if (p.map) {
+            any = true;
+            std::vector<uint32_t> fill((size_t)p.windows + GUARD_WORDS, 0xFFFFFFFFu);
+            for (size_t g = 0; g < GUARD_WORDS; ++g) fill[(size_t)p.windows + g] = GUARD;
+            HIP(hipMalloc((void **)&m, fill.size() * 4u));
+            HIP(hipMemcpy(m, fill.data(), fill.size() * 4u, hipMemcpyHostToDevice));
+        }
+        maps.push_back(m);
+    }
+    void *out = nullptr;
+    HIP(hipMalloc(&out, (size_t)n * 48u));
+    std::vector<uint8_t> ff((size_t)n * 48u, 0xFF);
+    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    CHECK(hvq_picture_ssim(ctx, n, sids.data(), ords.data(), refs.data(), (int64_t *)out, any ? maps.data() : nullptr, caller));
+    return Call{ (int64_t *)out, maps, pairs, label };
+}
+
+/* after the caller's stream has been waited for */
+static void write_call(Call *c)
+{
+    std::vector<int64_t> host(c->pairs.size() * 6u);
+    HIP(hipMemcpy(host.data(), c->out, host.size() * 8u, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->pairs.size(); ++i) {
+        const Pair &p = c->pairs[i];
+        fprintf(g_res, "W %s %s %d %s %s %d", c->label.c_str(), p.clip_a.c_str(), p.k, p.form.c_str(), p.clip_b.c_str(), p.kb);
+        for (int v = 0; v < 6; ++v) fprintf(g_res, " %lld", (long long)host[i * 6u + (size_t)v]);
+        fprintf(g_res, "\n");
+        if (!c->maps[i]) continue;
+        std::vector<uint32_t> m((size_t)p.windows + GUARD_WORDS);
+        HIP(hipMemcpy(m.data(), c->maps[i], m.size() * 4u, hipMemcpyDeviceToHost));
+        size_t intact = 0;
+        for (size_t g = 0; g < GUARD_WORDS; ++g) intact += m[(size_t)p.windows + g] == GUARD;
+        fprintf(g_res, "Q %s %s %d %s %s %d %zu %zu %d", c->label.c_str(), p.clip_a.c_str(), p.k, p.form.c_str(), p.clip_b.c_str(), p.kb, intact, GUARD_WORDS, p.windows);
+        for (int v = 0; v < p.windows; ++v) fprintf(g_res, " %x", m[(size_t)v]);
+        fprintf(g_res, "\n");
+        HIP(hipFree(c->maps[i]));
+    }
+    HIP(hipFree(c->out));
+    c->out = nullptr;
+}
+
+static const char *SEVEN[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8", "i16" };
+
+/* seven clips of three samplings in one context: per clip one call of (k, k - 1), (k, k) and (k, inverted k) for every picture with a map
+ * for every pair, the same call without maps, then one call over all clips with the forms interleaved and a map for every other pair,
+ * and a call of one pair */
+static void scenario_goldens()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    std::vector<std::pair<int, const Clip *>> sc;
+    std::vector<Call> calls;
+    std::vector<void *> keep;
+    for (const char *nm : SEVEN) {
+        const Clip &c = clip(nm);
+        const int sid = decode(ctx, c);
+        sc.push_back({ sid, &c });
+        std::vector<Pair> pairs;
+        for (int k = 0; k < (int)c.pics.size(); ++k) {
+            if (k) pairs.push_back(against_picture(sid, c, k, sid, c, k - 1, true));
+            pairs.push_back(against_picture(sid, c, k, sid, c, k, true));
+            pairs.push_back(against_memory(ctx, sid, c, k, sid, c, k, k & 1 ? 16 : 0, true, &keep));
+        }
+        calls.push_back(call_ssim(ctx, pairs, caller, "goldens/maps"));
+        for (Pair &p : pairs) p.map = false;
+        calls.push_back(call_ssim(ctx, pairs, caller, "goldens/nomaps"));
+    }
+    std::vector<Pair> mixed;
+    int i = 0;
+    for (int round = 0; round < 2; ++round)
+        for (auto &s : sc) {
+            const int n = (int)s.second->pics.size(), k = (round * 3 + 1) % n;
+            const bool map = i & 1;
+            mixed.push_back(i % 3 == 0 ? against_picture(s.first, *s.second, k, s.first, *s.second, k ? k - 1 : n - 1, map)
+                          : i % 3 == 1 ? against_memory(ctx, s.first, *s.second, k, s.first, *s.second, k, 16, map, &keep)
+                                       : against_picture(s.first, *s.second, k, s.first, *s.second, k, map));
+            ++i;
+        }
+    calls.push_back(call_ssim(ctx, mixed, caller, "goldens/mixed"));
+    calls.push_back(call_ssim(ctx, { against_picture(sc[1].first, *sc[1].second, 1, sc[1].first, *sc[1].second, 0, true) }, caller, "goldens/one"));
+    HIP(hipStreamSynchronize(caller));
+    for (Call &c : calls) write_call(&c);
+    for (void *p : keep) HIP(hipFree(p));
+    for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
+ * the records are those of the pictures as they were; then a call destroyed with the context while still queued */
+static void scenario_reuse()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
+    const int n = (int)a.pics.size();
+    const int sa = decode(ctx, a), se = decode(ctx, e);
+    std::vector<Pair> pairs;
+    for (int k = 0; k < n; ++k) pairs.push_back(against_picture(sa, a, k, sa, a, (k + 1) % n, (k & 1) == 0));
+    Call c = call_ssim(ctx, pairs, caller, "reuse");
+    for (int pass = 0; pass < 2; ++pass) {                      /* 2 n later pictures into a ring of n + 4 slots: every slot of the first pass is rewritten */
+        for (const Pic &p : a.pics) CHECK(hvq_stream_submit(ctx, sa, p.type, p.p, p.len));
+        CHECK(hvq_flush(ctx));
+    }
+    const HvqMetricsRef self{ sa, 0, nullptr };
+    fprintf(g_res, "R reuse/evicted %d\n", hvq_picture_ssim(ctx, 1, &sa, &pairs[0].k, &self, c.out, nullptr, caller));
+    /* the newest pictures, with a call of another stream's pictures behind them in the chain; destroyed with that one still queued */
+    std::vector<Pair> late_call, late, other;
+    for (int k = 0; k < n; ++k) {
+        Pair p = against_picture(sa, a, 2 * n + k, sa, a, 2 * n + (k ? k - 1 : 0), true);
+        late_call.push_back(p);
+        p.k = k; p.kb = k ? k - 1 : 0;                          /* reported as the clip's pictures: the third pass decodes the same clip */
+        late.push_back(p);
+    }
+    Call d = call_ssim(ctx, late_call, caller, "reuse/late");
+    d.pairs = late;
+    for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(against_picture(se, e, k, se, e, k ? k - 1 : 0, true));
+    Call f = call_ssim(ctx, other, caller, "reuse/destroy");
+    hvq_context_destroy(ctx);
+    HIP(hipStreamSynchronize(caller));
+    write_call(&c);
+    write_call(&d);
+    write_call(&f);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* every refusal of the specification, into sentinel-filled buffers that must come back untouched */
+static void scenario_refused()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("gop64x48_15"), &b = clip("yuv422_64x48"), &d = a;
+    const int sa = decode(ctx, a), sb = decode(ctx, b);
+    /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
+    const int sd = hvq_stream_open(ctx, d.info.width, d.info.height, d.info.h_samp, d.info.v_samp, d.info.is_1_5, 3);
+    CHECK(sd);
+    for (const Pic &p : d.pics) CHECK(hvq_stream_submit(ctx, sd, p.type, p.p, p.len));
+    CHECK(hvq_flush(ctx));
+    const int last = (int)d.pics.size() - 1;
+    CHECK(hvq_stream_submit(ctx, sa, a.pics[0].type, a.pics[0].p, a.pics[0].len));      /* queued, not flushed: ordinal n of sa */
+    const int queued = (int)a.pics.size();
+
+    const size_t bytes = 8u + 2u * 48u + 8u, mbytes = ((size_t)windows_of(a) + 2u) * 4u;         /* sentinels on both sides of out; a map with room */
+    void *outbuf = nullptr, *mem = nullptr, *map0 = nullptr, *map1 = nullptr;
+    HIP(hipMalloc(&outbuf, bytes));
+    HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
+    HIP(hipMalloc(&map0, mbytes));
+    HIP(hipMalloc(&map1, mbytes));
+    std::vector<uint8_t> sent(bytes, 0xA5), msent(mbytes, 0xA5);
+    HIP(hipMemcpy(outbuf, sent.data(), sent.size(), hipMemcpyHostToDevice));
+    HIP(hipMemcpy(map0, msent.data(), msent.size(), hipMemcpyHostToDevice));
+    HIP(hipMemcpy(map1, msent.data(), msent.size(), hipMemcpyHostToDevice));
+    int64_t *o = (int64_t *)((uint8_t *)outbuf + 8);
+    float *good_maps[2] = { (float *)map0, (float *)map1 };
+    auto refuse = [&](const char *label, int n, std::vector<int> sids, std::vector<int> ords, std::vector<HvqMetricsRef> refs, int64_t *dst, float *const *maps) {
+        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_ssim(ctx, n, sids.data(), ords.data(), refs.empty() ? nullptr : refs.data(), dst, maps, caller));
+    };
+    const HvqMetricsRef S0{ sa, 0, nullptr }, S1{ sa, 1, nullptr };
+    refuse("geometry", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ sb, 1, nullptr } }, o, good_maps);
+    refuse("ptr_with_stream", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ sa, 0, mem } }, o, good_maps);
+    refuse("misaligned_ptr", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ -1, 0, (uint8_t *)mem + 8 } }, o, good_maps);
+    refuse("bad_stream", 2, { sa, 99 }, { 0, 0 }, { S1, S0 }, o, good_maps);
+    refuse("bad_ordinal", 2, { sa, sa }, { 0, 1000 }, { S1, S0 }, o, good_maps);
+    refuse("bad_ref_stream", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ 99, 0, nullptr } }, o, good_maps);
+    refuse("bad_ref_ordinal", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ sa, -1, nullptr } }, o, good_maps);
+    refuse("ref_stream_below_minus_one", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ -2, 0, nullptr } }, o, good_maps);
+    refuse("null_ref", 2, { sa, sa }, { 0, 1 }, {}, o, good_maps);
+    refuse("zeros_ref", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ -1, 0, nullptr } }, o, good_maps);
+    refuse("null_out", 2, { sa, sa }, { 0, 1 }, { S1, S0 }, nullptr, good_maps);
+    refuse("misaligned_out", 2, { sa, sa }, { 0, 1 }, { S1, S0 }, (int64_t *)((uint8_t *)o + 4), good_maps);
+    float *bad_maps[2] = { (float *)map0, (float *)((uint8_t *)map1 + 2) };
+    refuse("misaligned_map", 2, { sa, sa }, { 0, 1 }, { S1, S0 }, o, bad_maps);
+    refuse("too_many", 65536, { sa }, { 0 }, { S1 }, o, nullptr);
+    refuse("evicted", 2, { sd, sd }, { last, 0 }, { HvqMetricsRef{ sd, last, nullptr }, HvqMetricsRef{ sd, last, nullptr } }, o, good_maps);
+    refuse("evicted_ref", 2, { sd, sd }, { last, last }, { HvqMetricsRef{ sd, last, nullptr }, HvqMetricsRef{ sd, 0, nullptr } }, o, good_maps);
+    refuse("queued", 2, { sa, sa }, { 0, queued }, { S1, S0 }, o, good_maps);
+    fprintf(g_res, "R refused/null_context %d\n", hvq_picture_ssim(nullptr, 1, &sa, &last, &S0, o, nullptr, caller));
+    HIP(hipStreamSynchronize(caller));
+    size_t same = 0, total = 0;
+    for (void *buf : { outbuf, map0, map1 }) {
+        std::vector<uint8_t> back(buf == outbuf ? bytes : mbytes);
+        HIP(hipMemcpy(back.data(), buf, back.size(), hipMemcpyDeviceToHost));
+        for (uint8_t x : back) same += x == 0xA5;
+        total += back.size();
+    }
+    fprintf(g_res, "S refused %zu %zu\n", same, total);
+    /* the well-formed call right after them works */
+    CHECK(hvq_flush(ctx));
+    Call c = call_ssim(ctx, { against_picture(sa, a, 1, sa, a, 0, true), against_picture(sd, d, last, sd, d, last, false) }, caller, "refused/then_ok");
+    HIP(hipStreamSynchronize(caller));
+    write_call(&c);
+    HIP(hipFree(outbuf));
+    HIP(hipFree(mem));
+    HIP(hipFree(map0));
+    HIP(hipFree(map1));
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+int main(int argc, char **argv)
+{
+    if (argc < 4) { fprintf(stderr, "usage: fake_ssim_driver <scenario> <outdir> <golden dir>\n"); return 2; }
+    const std::string sc = argv[1];
+    g_out = argv[2]; g_golden = argv[3];
+    g_res = fopen((g_out + "/results.txt").c_str(), "w");
+    if (!g_res) { fprintf(stderr, "fake_ssim_driver: cannot write into %s\n", g_out.c_str()); return 2; }
+    if (sc == "goldens") scenario_goldens();
+    else if (sc == "reuse") scenario_reuse();
+    else if (sc == "refused") scenario_refused();
+    else { fprintf(stderr, "fake_ssim_driver: unknown scenario %s\n", sc.c_str()); return 2; }
+    fake_drain_all();
+    fclose(g_res);
+    return 0;
+}
