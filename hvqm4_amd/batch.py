@@ -320,6 +320,40 @@ class Context:
         check(lib().hvq_picture_ssim(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), a_m, C.c_void_p(stream)))
         return (out, views) if maps else out
 
+    def picture_checksums(self, sids, ordinals, src=None, out=None):
+        """hvq_picture_checksums: zlib's CRC-32 and Adler-32 of every plane and of the whole picture (the bytes read_picture returns)
+        of resident pictures (sids[i], ordinals[i]), computed on the device on torch's current stream, without a host
+        synchronisation and without moving a picture -> int64 CUDA tensor [n, 8] = (crc32 Y, U, V, picture, adler32 Y, U, V,
+        picture) (`out`, if given: such a tensor, contiguous; it is overwritten whole).  hvqm4_amd.checksums names the columns and
+        gives the expected values of pictures on the host.  `src`: None, or a list with one entry per picture: None (the resident
+        picture) or a contiguous uint8 CUDA tensor of pic_bytes(sid) elements laid out as the pictures of `sid` are (Y | U | V),
+        checksummed instead; its ordinal must be -1 and the caller keeps it alive until the work has run.  Ordering and slot safety
+        are export()'s."""
+        import torch
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 8) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 8)")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        check(lib().hvq_picture_checksums(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
         from .metrics import ssim_windows

@@ -33,6 +33,7 @@
 #ifndef HVQ_DESC_H
 #define HVQ_DESC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define HVQ_MAGIC        0x34515648u   /* "HVQ4" */
@@ -304,6 +305,40 @@ static_assert(sizeof(HvqSsimJob) % 16 == 0, "job tables are uploaded in 16-byte 
 #else
 _Static_assert(sizeof(HvqSsimJob) == 112, "HvqSsimJob must be 112 bytes");
 _Static_assert(sizeof(HvqSsimJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+#endif
+
+/* one picture of the checksum launch (hvq_checksum_kernel + hvq_checksum_finish_kernel, hvq_picture_checksums): picture `a`, Y|U|V tightly
+ * packed (a slot, or the caller's memory in a slot's layout), its accumulator `acc` in library-owned memory, uint64 [3 planes][4] =
+ * { R in the low dword, sum d, sum (len - i) d, unused } (hvq_checksum.h), zeroed in front of the launch, and the output record uint64 [8]
+ * the finishing launch writes.  A plane is units[p] 16-byte units long; a workgroup takes HVQ_CK_CHUNK consecutive units of ONE plane,
+ * counted from the plane's END (workgroup c of a plane has c whole chunks behind it; the one at the plane's start may be short: the units
+ * in front of the plane are zeros, which leave a CRC register of 0 as it is).  wg_first as in HvqMetricsJob.  xlen[p] = x^(8 * bytes of
+ * plane p) mod P, for the CRC's initial register and the picture value.  Every member is a dword or a qword (scalar loads); 80 bytes. */
+#define HVQ_CK_LANES  256u          /* lanes of a workgroup */
+#define HVQ_CK_UNITS  4u            /* 16-byte units of a lane, HVQ_CK_LANES apart */
+#define HVQ_CK_CHUNK  (HVQ_CK_LANES * HVQ_CK_UNITS)
+#define HVQ_CK_MAX_UNITS (1u << 22) /* 8192 x 8192 samples, the largest plane the library opens */
+typedef struct HvqChecksumJob {
+    uint64_t a;                        /* device address, a multiple of 16 */
+    uint64_t acc;                      /* device address of the accumulator, a multiple of 8 */
+    uint64_t out;                      /* device address of the record, a multiple of 8 */
+    uint32_t plane_off[3];             /* byte offset of plane p inside a picture */
+    uint32_t units[3];                 /* 16-byte units of plane p, at most HVQ_CK_MAX_UNITS */
+    uint32_t wg_first[4];
+    uint32_t xlen[3];
+    uint32_t pad;
+} HvqChecksumJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqChecksumJob) == 80, "HvqChecksumJob must be 80 bytes");
+static_assert(sizeof(HvqChecksumJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+static_assert(offsetof(HvqChecksumJob, acc) == 8 && offsetof(HvqChecksumJob, out) == 16 && offsetof(HvqChecksumJob, plane_off) == 24 &&
+              offsetof(HvqChecksumJob, units) == 36 && offsetof(HvqChecksumJob, wg_first) == 48 && offsetof(HvqChecksumJob, xlen) == 64,
+              "the members hvq_checksum_kernel reads");
+/* sum (len - i) d over a plane is at most 255 len (len + 1) / 2: an exact 64-bit integer for every plane the library opens */
+static_assert(255ull * (16ull * HVQ_CK_MAX_UNITS) * (16ull * HVQ_CK_MAX_UNITS + 1ull) / 2ull < (1ull << 63), "Adler's weighted sum must fit 64 bits");
+#else
+_Static_assert(sizeof(HvqChecksumJob) == 80, "HvqChecksumJob must be 80 bytes");
 #endif
 
 

@@ -38,6 +38,7 @@
 #include "hvq_desc.h"
 #include "hvq_parse.h"
 #include "hvq_gparse_core.h"
+#include "hvq_checksum.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -70,6 +71,8 @@ extern "C" hipError_t hvq_launch_resample(const void *jobs_dev, int njobs, int m
 extern "C" __attribute__((weak)) hipError_t hvq_launch_metrics(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 /* hvq_ssim.hip.  Weak for the same reason: hvq_picture_ssim then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_ssim(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
+/* hvq_checksum.hip.  Weak for the same reason: hvq_picture_checksums then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_checksums(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -345,6 +348,10 @@ struct HvqContext {
     struct ExportTab { uint8_t *host = nullptr; uint8_t *dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } ex[4];
     int ex_next = 0, ex_last = -1;     /* table of the next export; of the newest one (-1: none yet) */
     bool ex_unfenced = false;          /* an export was queued since c->stream last waited for one */
+    /* hvq_picture_checksums: the accumulators of one call's pictures, 96 bytes each.  One buffer serves every call: a call of the export
+     * chain runs behind the one before it, so the launch that zeroes and fills it comes after the launches that read it last */
+    uint8_t *ck_acc = nullptr;
+    size_t ck_cap = 0;
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
      * reads one set while the parse of batch k + 1 fills the other.  ps_live is the set the code below means by PS(c). */
@@ -647,6 +654,7 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     if (c->rb_tab_host) (void)hipHostFree(c->rb_tab_host);
     if (c->rgb_dev) (void)hipFree(c->rgb_dev);
     if (c->rgb_jobs_dev) (void)hipFree(c->rgb_jobs_dev);
+    if (c->ck_acc) (void)hipFree(c->ck_acc);
     for (auto &t : c->ex) {
         if (t.host) (void)hipHostFree(t.host);
         if (t.dev) (void)hipFree(t.dev);
@@ -2520,6 +2528,80 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
                               return e != hipSuccess ? e : hvq_launch_ssim(tab, n, max_wgs, st);
                           });
 }
+
+/* Checksums of resident pictures (include/hvqm4_amd.h: the specification): a fifth member of the export chain, hvq_picture_metrics' lookup,
+ * refusals and ordering.  The memset of the accumulators and the two launches go behind the job table on the caller's stream
+ * (export_enqueue); the accumulators are the context's own, reused by every call: the chain orders the calls. */
+HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                     uint64_t *out, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    std::vector<HvqChecksumJob> jobs((size_t)n);
+    uint32_t max_wgs = 0;
+    size_t known_len[2] = { 0, 0 };                                /* x^(8 len) of the last two plane lengths seen: streams share geometries */
+    uint32_t known_x[2] = { HVQ_CRC_ONE, HVQ_CRC_ONE };
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
+        if (ny / 16u > HVQ_CK_MAX_UNITS) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, streams[i], HVQ_CK_MAX_UNITS);
+        HvqChecksumJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a;
+        j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 8u);
+        const size_t len[3] = { ny, nc, nc };
+        size_t off = 0;
+        for (int p = 0; p < 3; ++p) {
+            j.plane_off[p] = (uint32_t)off;
+            j.units[p] = (uint32_t)(len[p] / 16u);
+            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_CK_CHUNK - 1u) / HVQ_CK_CHUNK;
+            const int slot = p != 0;
+            if (known_len[slot] != len[p]) { known_len[slot] = len[p]; known_x[slot] = hvq_gf_xpow8(len[p]); }
+            j.xlen[p] = known_x[slot];
+            off += len[p];
+        }
+        max_wgs = std::max(max_wgs, j.wg_first[3]);
+    }
+    if (!hvq_launch_checksums) return fail(HVQ_E_NOGPU, "this build of the library has no checksum kernel (hvq_checksum.hip is not linked)");
+    const size_t acc_bytes = (size_t)n * 96u;
+    if (acc_bytes > c->ck_cap) {
+        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
+        if (c->ck_acc) { HIPCHK(hipFree(c->ck_acc)); c->ck_acc = nullptr; c->ck_cap = 0; }
+        const size_t ncap = align_up(acc_bytes * 2, 4096);
+        HIPCHK(hipMalloc((void **)&c->ck_acc, ncap));
+        c->ck_cap = ncap;
+    }
+    uint8_t *acc = c->ck_acc;
+    for (int i = 0; i < n; ++i) jobs[(size_t)i].acc = (uint64_t)(uintptr_t)(acc + (size_t)i * 96u);
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqChecksumJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) {
+                              hipError_t e = hipMemsetAsync(acc, 0, acc_bytes, st);             /* the first launch xors and adds into them */
+                              return e != hipSuccess ? e : hvq_launch_checksums(tab, n, max_wgs, st);
+                          });
+}
+
+/* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */
+HVQ_EXPORT uint32_t hvq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return hvq_crc32_combine_x(crc_a, crc_b, hvq_gf_xpow8(len_b)); }
+HVQ_EXPORT uint32_t hvq_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b) { return hvq_adler32_combine_u(a, b, len_b); }
 
 /* hvq_export_tensors' checks of one destination, for hvq_export_resampled: output size, crop, pitches, alignment (es = element size).
  * The crop and the pitches in effect come back in *g; `bits` = pointer | pitches, for the alignment of the 16-byte stores. */

@@ -335,6 +335,44 @@ int  hvq_ssim_windows(int width, int height, int h_samp, int v_samp, int32_t dim
 int  hvq_picture_ssim(HvqContext *ctx, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                       int64_t *out, float *const *maps, void *hip_stream);
 
+/* Checksums of resident pictures, computed where they lie: for `n` pictures, of any streams, sizes and samplings, in one kernel launch and
+ * a tiny finishing launch behind it, on the caller's HIP stream and without a host synchronisation, zlib's CRC-32 and Adler-32 of every
+ * plane and of the whole picture.  "Is this picture bit for bit the expected one?" is answered by comparing 4-byte values; no picture
+ * crosses PCIe.  This text is the authority for the values; it makes no claim about the output of any muxer or tool.
+ *   A plane is its samples, rows tightly packed, exactly as they lie in the slot (the library's geometries make every plane a multiple of
+ *   16 bytes); `picture` is the bytes Y | U | V, what hvq_read_picture returns: crc32_picture == zlib's crc32 of that buffer.
+ *   CRC-32 of the bytes m_0 .. m_(L-1): r = 0xFFFFFFFF; per byte r ^= m_i, then eight times r = (r >> 1) ^ (0xEDB88320 & -(r & 1)); the value
+ *       is r ^ 0xFFFFFFFF (the reflected polynomial 0xEDB88320, initial register and final xor 0xFFFFFFFF: zlib's crc32(0, m, L)).
+ *   Adler-32: lo = (1 + sum m_i) mod 65521, hi = (L + sum (L - i) m_i) mod 65521, i from 0; the value is hi << 16 | lo (seed 1, modulus
+ *       65521: zlib's adler32(1, m, L)).
+ *   Both are computed exactly in parallel -- the CRC register is linear over GF(2), Adler's halves are integer sums reduced once at the
+ *   end -- so the values do not depend on the order the GPU combines partial results in: the same call gives the same bits every time.
+ *   out: `n` records of uint64_t [8] = { crc32_Y, crc32_U, crc32_V, crc32_picture, adler32_Y, adler32_U, adler32_V, adler32_picture }, 64
+ *       bytes each, dense, in call order, in DEVICE memory, a multiple of 8; every value lies in [0, 2^32); the call writes all 64 * n
+ *       bytes whatever they held before.
+ *   a_i = the resident picture (streams[i], ordinals[i]).  If src != NULL and src[i] != NULL, a_i is the caller's device memory instead,
+ *       laid out as a picture of streams[i] (Y | U | V tightly packed, hvq_stream_pic_bytes long): src[i] must be a multiple of 16 and
+ *       ordinals[i] must be -1; the library cannot check its size; it is read when the work runs on `hip_stream`.
+ *   Lookup, HVQ_E_STATE cases, n <= 65535, "every argument is checked before anything is enqueued: a refused call leaves `out`
+ *   untouched", ending the batch in flight only when a requested picture belongs to it, ordering on `hip_stream`, membership of the export
+ *   chain and slot safety are hvq_picture_metrics'.  HVQ_E_ARG for a NULL context, a bad stream or ordinal, a src[i] that is not a multiple
+ *   of 16 or comes with an ordinal other than -1, a null `out` or one that is not a multiple of 8.  n == 0 is HVQ_OK and does nothing.
+ *   HVQ_E_NOGPU (after those checks) from a build without the checksum kernel. */
+#define HVQ_CK_CRC32_Y 0
+#define HVQ_CK_CRC32_U 1
+#define HVQ_CK_CRC32_V 2
+#define HVQ_CK_CRC32_PICTURE 3
+#define HVQ_CK_ADLER32_Y 4
+#define HVQ_CK_ADLER32_U 5
+#define HVQ_CK_ADLER32_V 6
+#define HVQ_CK_ADLER32_PICTURE 7
+int  hvq_picture_checksums(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, uint64_t *out,
+                           void *hip_stream);
+/* Host only, no GPU needed, zlib's crc32_combine / adler32_combine: the checksum of A | B from the checksums of A and of B and the length
+ * of B in bytes -- a clip's running checksum from its pictures', a picture's from its planes'. */
+uint32_t hvq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+uint32_t hvq_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);

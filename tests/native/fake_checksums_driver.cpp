@@ -1,0 +1,330 @@
+/*
+ * tests/native/fake_checksums_driver.cpp -- TEST INFRASTRUCTURE: a stand-alone program that drives hvq_picture_checksums of the runtime
+ * (hvqm4_amd/csrc/hvq_runtime.cpp, linked unchanged against the CPU fake device and tests/native/fake_checksums.cpp) through
+ * include/hvqm4_amd.h.  It writes what it read back and judges nothing: tests/test_checksums_cpu.py compares with tests/checksums_ref.py
+ * on the oracle's pictures.
+ *
+ *   fake_checksums_driver <scenario> <outdir> <golden dir>
+ *
+ * results.txt, one fact per line:
+ *   C <label> <clip> <ordinal> <form> <8 numbers>     one record read back: crc32 Y, U, V, picture, adler32 Y, U, V, picture
+ *       form: pic (the resident picture), inv (the caller's memory: the picture with every byte inverted, 255 - x)
+ *   R <label> <return code>                           a return code the test wants to see
+ *   S <label> <bytes that still hold the sentinel> <bytes>     an output buffer after refused calls
+ * Caller-side resources (a stream, output records, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
+ */
+#include "fake_device.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/hvqm4_amd.h"
+
+struct Pic { int type; const uint8_t *p; size_t len; };
+struct Clip {
+    std::string name;
+    std::vector<uint8_t> data;
+    HvqH4mInfo info;
+    std::vector<Pic> pics;
+};
+
+static std::string g_golden, g_out;
+static FILE *g_res;
+static std::map<std::string, Clip> g_clips;
+
+#define CHECK(expr) do { const int rc_ = (expr); if (rc_ < 0) { fprintf(stderr, "fake_checksums_driver: %s = %d: %s\n", #expr, rc_, hvq_last_error_string()); exit(3); } } while (0)
+#define HIP(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "fake_checksums_driver: %s failed\n", #expr); exit(3); } } while (0)
+
+static const Clip &clip(const std::string &name)
+{
+    auto it = g_clips.find(name);
+    if (it != g_clips.end()) return it->second;
+    Clip &c = g_clips[name];
+    c.name = name;
+    const std::string path = g_golden + "/" + name + ".h4m";
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "fake_checksums_driver: cannot open %s\n", path.c_str()); exit(2); }
+    fseek(f, 0, SEEK_END);
+    c.data.resize((size_t)ftell(f));
+    fseek(f, 0, SEEK_SET);
+    if (fread(c.data.data(), 1, c.data.size(), f) != c.data.size()) exit(2);
+    fclose(f);
+    CHECK(hvq_h4m_header(c.data.data(), c.data.size(), &c.info));
+    HvqH4mIter it2;
+    hvq_h4m_begin(&it2);
+    int type; uint32_t disp; const uint8_t *p; size_t len;
+    while (hvq_h4m_next(c.data.data(), c.data.size(), &it2, &type, &disp, &p, &len) == 1) c.pics.push_back(Pic{ type, p, len });
+    return c;
+}
+
+static int decode(HvqContext *ctx, const Clip &c, int extra = 3)
+{
+    const int sid = hvq_stream_open(ctx, c.info.width, c.info.height, c.info.h_samp, c.info.v_samp, c.info.is_1_5, (int)c.pics.size() + extra);
+    CHECK(sid);
+    for (const Pic &p : c.pics) CHECK(hvq_stream_submit(ctx, sid, p.type, p.p, p.len));
+    CHECK(hvq_flush(ctx));
+    return sid;
+}
+
+static hipStream_t caller_stream()
+{
+    hipStream_t s = nullptr;
+    HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+}
+
+/* one picture of a call and what the test is told about it */
+struct Item { int sid, k; const void *src; std::string clip, form; int kk; };
+
+static Item resident(int sid, const Clip &c, int k) { return Item{ sid, k, nullptr, c.name, "pic", k }; }
+
+/* the caller's memory: picture k of stream sid read back, every byte inverted, in device memory at `offset` bytes into an allocation */
+static Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep)
+{
+    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
+    std::vector<uint8_t> host(pb);
+    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
+    for (uint8_t &x : host) x = (uint8_t)(255 - x);
+    void *d = nullptr;
+    HIP(hipMalloc(&d, pb + offset));
+    keep->push_back(d);
+    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
+    return Item{ sid, -1, (uint8_t *)d + offset, c.name, "inv", k };
+}
+
+struct Call { uint64_t *out; std::vector<Item> items; std::string label; };
+
+/* queue one call on `caller`; out is filled with 0xFF bytes first (the call must replace every one of them) */
+static Call call_checksums(HvqContext *ctx, const std::vector<Item> &items, bool null_src, hipStream_t caller, const char *label)
+{
+    const int n = (int)items.size();
+    std::vector<int> sids, ords;
+    std::vector<const void *> src;
+    for (const Item &p : items) { sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); }
+    void *out = nullptr;
+    HIP(hipMalloc(&out, (size_t)n * 64u));
+    std::vector<uint8_t> ff((size_t)n * 64u, 0xFF);
+    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    CHECK(hvq_picture_checksums(ctx, n, sids.data(), ords.data(), null_src ? nullptr : src.data(), (uint64_t *)out, caller));
+    return Call{ (uint64_t *)out, items, label };
+}
+
+/* after the caller's stream has been waited for */
+static void write_call(Call *c)
+{
+    std::vector<uint64_t> host(c->items.size() * 8u);
+    HIP(hipMemcpy(host.data(), c->out, host.size() * 8u, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->items.size(); ++i) {
+        const Item &p = c->items[i];
+        fprintf(g_res, "C %s %s %d %s", c->label.c_str(), p.clip.c_str(), p.kk, p.form.c_str());
+        for (int v = 0; v < 8; ++v) fprintf(g_res, " %llu", (unsigned long long)host[i * 8u + (size_t)v]);
+        fprintf(g_res, "\n");
+    }
+    HIP(hipFree(c->out));
+    c->out = nullptr;
+}
+
+static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8" };
+
+/* six clips of three samplings in one context: per clip one call over its pictures (src = NULL), then one call over all clips with the
+ * pictures interleaved, a call of one picture, and n == 0 */
+static void scenario_goldens()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    std::vector<std::pair<int, const Clip *>> sc;
+    std::vector<Call> calls;
+    for (const char *nm : SIX) {
+        const Clip &c = clip(nm);
+        const int sid = decode(ctx, c);
+        sc.push_back({ sid, &c });
+        std::vector<Item> items;
+        for (int k = 0; k < (int)c.pics.size(); ++k) items.push_back(resident(sid, c, k));
+        calls.push_back(call_checksums(ctx, items, true, caller, "goldens/clip"));
+    }
+    std::vector<Item> mixed;
+    for (int round = 0; round < 2; ++round)
+        for (auto &s : sc) mixed.push_back(resident(s.first, *s.second, (round * 3 + 1) % (int)s.second->pics.size()));
+    calls.push_back(call_checksums(ctx, mixed, false, caller, "goldens/mixed"));
+    calls.push_back(call_checksums(ctx, { resident(sc[1].first, *sc[1].second, 1) }, false, caller, "goldens/one"));
+    fprintf(g_res, "R goldens/n0 %d\n", hvq_picture_checksums(ctx, 0, nullptr, nullptr, nullptr, nullptr, caller));
+    HIP(hipStreamSynchronize(caller));
+    for (Call &c : calls) write_call(&c);
+    for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* pictures in the caller's memory, at the start of an allocation and 16 bytes into one, mixed with resident ones; on the caller's stream
+ * and on the null stream */
+static void scenario_memory()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
+    const int sa = decode(ctx, a), sb = decode(ctx, b);
+    std::vector<void *> keep;
+    std::vector<Item> items;
+    for (int k = 0; k < (int)a.pics.size(); ++k) {
+        items.push_back(in_memory(ctx, sa, a, k, k & 1 ? 16 : 0, &keep));
+        items.push_back(resident(sa, a, k));
+    }
+    items.push_back(in_memory(ctx, sb, b, 1, 16, &keep));
+    items.push_back(resident(sb, b, 1));
+    Call c = call_checksums(ctx, items, false, caller, "memory");
+    Call d = call_checksums(ctx, items, false, nullptr, "memory/nullstream");
+    HIP(hipStreamSynchronize(caller));
+    HIP(hipStreamSynchronize(nullptr));
+    write_call(&c);
+    write_call(&d);
+    for (void *p : keep) HIP(hipFree(p));
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
+ * the records are those of the pictures as they were */
+static void scenario_reuse()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
+    const int n = (int)a.pics.size();
+    const int sa = decode(ctx, a), se = decode(ctx, e);
+    std::vector<Item> items;
+    for (int k = 0; k < n; ++k) items.push_back(resident(sa, a, k));
+    Call c = call_checksums(ctx, items, false, caller, "reuse");
+    for (int pass = 0; pass < 2; ++pass) {                      /* 2 n later pictures into a ring of n + 3 slots: every slot of the first pass is rewritten */
+        for (const Pic &p : a.pics) CHECK(hvq_stream_submit(ctx, sa, p.type, p.p, p.len));
+        CHECK(hvq_flush(ctx));
+    }
+    fprintf(g_res, "R reuse/evicted %d\n", hvq_picture_checksums(ctx, 1, &sa, &items[0].k, nullptr, c.out, caller));
+    /* the newest pictures, with a call of another stream's pictures behind them in the chain; destroyed with that one still queued */
+    std::vector<Item> late_call, late, other;
+    for (int k = 0; k < n; ++k) {
+        Item p = resident(sa, a, 2 * n + k);
+        late_call.push_back(p);
+        p.kk = k;                                               /* reported as the clip's pictures: the third pass decodes the same clip */
+        late.push_back(p);
+    }
+    Call d = call_checksums(ctx, late_call, false, caller, "reuse/late");
+    d.items = late;
+    for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(resident(se, e, k));
+    Call f = call_checksums(ctx, other, false, caller, "reuse/destroy");
+    hvq_context_destroy(ctx);
+    HIP(hipStreamSynchronize(caller));
+    write_call(&c);
+    write_call(&d);
+    write_call(&f);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* two calls back to back on one stream, nothing waited for in between: they share the context's accumulators.  A small call, then a
+ * larger one (the accumulators grow with the first still queued), then the small one again */
+static void scenario_backtoback()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("wide296x160"), &b = clip("gop64x48_15");
+    const int sa = decode(ctx, a), sb = decode(ctx, b);
+    std::vector<Item> small, large;
+    for (int k = 0; k < 2; ++k) small.push_back(resident(sa, a, k));
+    for (int rep = 0; rep < 6; ++rep) {
+        for (int k = 0; k < (int)b.pics.size(); ++k) large.push_back(resident(sb, b, k));
+        for (int k = 0; k < (int)a.pics.size(); ++k) large.push_back(resident(sa, a, k));
+    }
+    Call c = call_checksums(ctx, small, false, caller, "backtoback/small");
+    Call d = call_checksums(ctx, large, false, caller, "backtoback/large");
+    Call e = call_checksums(ctx, small, false, caller, "backtoback/again");
+    Call f = call_checksums(ctx, large, false, caller, "backtoback/large2");
+    HIP(hipStreamSynchronize(caller));
+    write_call(&c);
+    write_call(&d);
+    write_call(&e);
+    write_call(&f);
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* every refusal of the specification, into one sentinel-filled buffer that must come back untouched */
+static void scenario_refused()
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    const Clip &a = clip("gop64x48_15"), &d = a;
+    const int sa = decode(ctx, a);
+    /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
+    const int sd = hvq_stream_open(ctx, d.info.width, d.info.height, d.info.h_samp, d.info.v_samp, d.info.is_1_5, 3);
+    CHECK(sd);
+    for (const Pic &p : d.pics) CHECK(hvq_stream_submit(ctx, sd, p.type, p.p, p.len));
+    CHECK(hvq_flush(ctx));
+    const int last = (int)d.pics.size() - 1;
+    CHECK(hvq_stream_submit(ctx, sa, a.pics[0].type, a.pics[0].p, a.pics[0].len));      /* queued, not flushed: ordinal n of sa */
+    const int queued = (int)a.pics.size();
+
+    const size_t bytes = 2u * 64u;
+    void *out = nullptr, *mem = nullptr;
+    HIP(hipMalloc(&out, bytes + 8u));
+    HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
+    std::vector<uint8_t> sent(bytes + 8u, 0xA5);
+    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
+    uint64_t *o = (uint64_t *)out;
+    auto refuse = [&](const char *label, HvqContext *cx, int n, std::vector<int> sids, std::vector<int> ords, std::vector<const void *> src, uint64_t *dst) {
+        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_checksums(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), dst, caller));
+    };
+    refuse("null_context", nullptr, 2, { sa, sa }, { 0, 1 }, {}, o);
+    refuse("bad_stream", ctx, 2, { sa, 99 }, { 0, 0 }, {}, o);
+    refuse("bad_ordinal", ctx, 2, { sa, sa }, { 0, 1000 }, {}, o);
+    refuse("misaligned_src", ctx, 2, { sa, sa }, { 0, -1 }, { nullptr, (uint8_t *)mem + 8 }, o);
+    refuse("src_with_ordinal", ctx, 2, { sa, sa }, { 0, 1 }, { nullptr, mem }, o);
+    refuse("src_with_bad_stream", ctx, 2, { sa, 99 }, { 0, -1 }, { nullptr, mem }, o);
+    refuse("minus_one_without_src", ctx, 2, { sa, sa }, { 0, -1 }, { nullptr, nullptr }, o);
+    refuse("null_out", ctx, 2, { sa, sa }, { 0, 1 }, {}, nullptr);
+    refuse("misaligned_out", ctx, 2, { sa, sa }, { 0, 1 }, {}, (uint64_t *)((uint8_t *)out + 4));
+    refuse("too_many", ctx, 65536, { sa }, { 0 }, {}, o);
+    refuse("evicted", ctx, 2, { sd, sd }, { last, 0 }, {}, o);
+    refuse("queued", ctx, 2, { sa, sa }, { 0, queued }, {}, o);
+    fprintf(g_res, "R refused/n0 %d\n", hvq_picture_checksums(ctx, 0, nullptr, nullptr, nullptr, nullptr, caller));
+    HIP(hipStreamSynchronize(caller));
+    std::vector<uint8_t> back(sent.size());
+    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
+    size_t same = 0;
+    for (uint8_t x : back) same += x == 0xA5;
+    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    /* the well-formed call right after them works */
+    CHECK(hvq_flush(ctx));
+    Call c = call_checksums(ctx, { resident(sa, a, 1), resident(sd, d, last) }, false, caller, "refused/then_ok");
+    HIP(hipStreamSynchronize(caller));
+    write_call(&c);
+    HIP(hipFree(out));
+    HIP(hipFree(mem));
+    hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+int main(int argc, char **argv)
+{
+    if (argc < 4) { fprintf(stderr, "usage: fake_checksums_driver <scenario> <outdir> <golden dir>\n"); return 2; }
+    const std::string sc = argv[1];
+    g_out = argv[2]; g_golden = argv[3];
+    g_res = fopen((g_out + "/results.txt").c_str(), "w");
+    if (!g_res) { fprintf(stderr, "fake_checksums_driver: cannot write into %s\n", g_out.c_str()); return 2; }
+    if (sc == "goldens") scenario_goldens();
+    else if (sc == "memory") scenario_memory();
+    else if (sc == "reuse") scenario_reuse();
+    else if (sc == "backtoback") scenario_backtoback();
+    else if (sc == "refused") scenario_refused();
+    else { fprintf(stderr, "fake_checksums_driver: unknown scenario %s\n", sc.c_str()); return 2; }
+    fake_drain_all();
+    fclose(g_res);
+    return 0;
+}
