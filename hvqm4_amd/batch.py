@@ -354,6 +354,48 @@ class Context:
         check(lib().hvq_picture_checksums(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def picture_histograms(self, sids, ordinals, ref=None, src=None, out=None):
+        """hvq_picture_histograms: per plane (Y, U, V) the 256-bin histogram of resident pictures a = (sids[i], ordinals[i]), in one
+        launch on torch's current stream, without a host synchronisation -> int32 CUDA tensor [n, 3, 256] (`out`, if given: such a
+        tensor, contiguous; it is overwritten whole).  `ref` None: bin v counts the samples equal to v (HVQ_HIST_VALUES).  `ref` a
+        list with one entry per picture, (sid, ordinal) -- a resident picture of the same geometry, of any stream -- or a contiguous
+        uint8 CUDA tensor of pic_bytes(sid) elements laid out as the pictures are: bin d counts the positions where |a - b| equals d
+        (HVQ_HIST_ABSDIFF); an entry None is refused.  `src` as in picture_checksums: None, or per picture None (the resident
+        picture) or a uint8 CUDA tensor counted instead, with ordinal -1.  hvqm4_amd.histograms reads the records (percentiles,
+        Otsu, equalisation, histogram distances, maximum error).  Ordering and slot safety are export()'s."""
+        import torch
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        from .histograms import BINS, HIST_ABSDIFF, HIST_VALUES
+        from .metrics import HvqMetricsRef, references
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
+        for i, r in enumerate(refs or ()):
+            if r[0] < 0 and r[2] is None:
+                raise ValueError(f"reference {i} is None: |a - 0| is a itself, ref=None gives its histogram")
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        if out is None:
+            out = torch.empty((n, 3, BINS), dtype=torch.int32, device="cuda")
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (n, 3, BINS) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int32 tensor of shape ({n}, 3, {BINS})")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_r = None if refs is None else C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
+        check(lib().hvq_picture_histograms(self._h, n, a_s, a_o, a_p, HIST_VALUES if refs is None else HIST_ABSDIFF, a_r,
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
         from .metrics import ssim_windows

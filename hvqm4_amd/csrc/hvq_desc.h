@@ -341,5 +341,35 @@ static_assert(255ull * (16ull * HVQ_CK_MAX_UNITS) * (16ull * HVQ_CK_MAX_UNITS + 
 _Static_assert(sizeof(HvqChecksumJob) == 80, "HvqChecksumJob must be 80 bytes");
 #endif
 
+/* one picture of the histogram launch (hvq_histogram_kernel, hvq_picture_histograms): picture `a` and, in HVQ_HIST_ABSDIFF, its reference
+ * `b`, both Y|U|V tightly packed (a slot, or the caller's memory in a slot's layout), and the output record uint32 [3 planes][256] the
+ * launch adds into (zeroed in front of it).  b = 0: HVQ_HIST_VALUES, bin v counts the samples of a equal to v; otherwise bin d counts
+ * the positions where |a - b| = d.  A plane is units[p] 16-byte units long; a workgroup takes HVQ_HG_CHUNK consecutive units of ONE plane,
+ * counts them in LDS and flushes its 256 bins once (1, 2, 4 and 8 chunks per workgroup were measured); wg_first as in HvqMetricsJob.
+ * Every member is a dword or a qword (scalar loads); 64 bytes. */
+#define HVQ_HG_BINS   256u          /* HVQ_HIST_BINS */
+#define HVQ_HG_LANES  256u          /* lanes of a workgroup */
+#define HVQ_HG_UNITS  4u            /* 16-byte units of a lane, HVQ_HG_LANES apart */
+#define HVQ_HG_CHUNK  (HVQ_HG_LANES * HVQ_HG_UNITS)
+#define HVQ_HG_MAX_UNITS (1u << 22) /* 8192 x 8192 samples, the largest plane the library opens */
+typedef struct HvqHistogramJob {
+    uint64_t a, b;                     /* device addresses, multiples of 16; b = 0: values of a */
+    uint64_t out;                      /* device address of the record, a multiple of 4 */
+    uint32_t plane_off[3];             /* byte offset of plane p inside a picture */
+    uint32_t units[3];                 /* 16-byte units of plane p, at most HVQ_HG_MAX_UNITS */
+    uint32_t wg_first[4];
+} HvqHistogramJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqHistogramJob) == 64, "HvqHistogramJob must be 64 bytes");
+static_assert(sizeof(HvqHistogramJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+static_assert(offsetof(HvqHistogramJob, b) == 8 && offsetof(HvqHistogramJob, out) == 16 && offsetof(HvqHistogramJob, plane_off) == 24 &&
+              offsetof(HvqHistogramJob, units) == 36 && offsetof(HvqHistogramJob, wg_first) == 48, "the members hvq_histogram_kernel reads");
+/* a bin holds at most the samples of its plane: 32 bits hold every count, in the record and (a workgroup's share) in LDS */
+static_assert(16ull * HVQ_HG_MAX_UNITS == (1ull << 26) && 16ull * HVQ_HG_MAX_UNITS < (1ull << 32), "a 32-bit bin must hold the samples of the largest plane");
+#else
+_Static_assert(sizeof(HvqHistogramJob) == 64, "HvqHistogramJob must be 64 bytes");
+#endif
+
 
 #endif

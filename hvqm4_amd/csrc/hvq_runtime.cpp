@@ -73,6 +73,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_metrics(const void *jobs_
 extern "C" __attribute__((weak)) hipError_t hvq_launch_ssim(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 /* hvq_checksum.hip.  Weak for the same reason: hvq_picture_checksums then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_checksums(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
+/* hvq_histogram.hip.  Weak for the same reason: hvq_picture_histograms then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_histograms(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -2596,6 +2598,85 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
                           [=](const void *tab, hipStream_t st) {
                               hipError_t e = hipMemsetAsync(acc, 0, acc_bytes, st);             /* the first launch xors and adds into them */
                               return e != hipSuccess ? e : hvq_launch_checksums(tab, n, max_wgs, st);
+                          });
+}
+
+/* Histograms of resident pictures (include/hvqm4_amd.h: the specification): a sixth member of the export chain, hvq_picture_metrics' lookup,
+ * refusals and ordering, hvq_picture_checksums' `src`.  The memset of the records and the launch go behind the job table on the caller's
+ * stream (export_enqueue). */
+HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, int mode,
+                                      const HvqMetricsRef *ref, uint32_t *out, void *hip_stream)
+{
+    static_assert(HVQ_HIST_BINS == HVQ_HG_BINS, "the kernel's bins are the header's");
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (mode != HVQ_HIST_VALUES && mode != HVQ_HIST_ABSDIFF) return fail(HVQ_E_ARG, "bad mode %d", mode);
+    if (mode == HVQ_HIST_VALUES && ref) return fail(HVQ_E_ARG, "HVQ_HIST_VALUES takes no reference (ref must be NULL)");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out || ((uintptr_t)out & 3u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 4");
+    if (mode == HVQ_HIST_ABSDIFF && !ref) return fail(HVQ_E_ARG, "HVQ_HIST_ABSDIFF needs a reference for every picture (ref is NULL)");
+    /* the resident pictures of both sides decide whether the batch in flight has to end; the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i) {
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+        if (ref && ref[i].stream >= 0) { res_s.push_back(ref[i].stream); res_o.push_back(ref[i].ordinal); }
+    }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    std::vector<HvqHistogramJob> jobs((size_t)n);
+    uint32_t max_wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const uint8_t *b = nullptr;
+        if (ref && ref[i].stream >= 0) {
+            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
+            int rc = HVQ_OK;
+            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
+            if (!b) return rc;
+            const Stream &r = c->streams[(size_t)ref[i].stream];
+            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
+                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
+                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
+        } else if (ref && ref[i].stream != -1) {
+            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
+        } else if (ref && ref[i].ptr) {
+            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
+            b = (const uint8_t *)ref[i].ptr;
+        } else if (ref) {
+            return fail(HVQ_E_ARG, "reference %d: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)", i);
+        }
+        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
+        if (ny / 16u > HVQ_HG_MAX_UNITS) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, streams[i], HVQ_HG_MAX_UNITS);
+        HvqHistogramJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
+        j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 3u * HVQ_HIST_BINS);
+        const size_t len[3] = { ny, nc, nc };
+        size_t off = 0;
+        for (int p = 0; p < 3; ++p) {
+            j.plane_off[p] = (uint32_t)off;
+            j.units[p] = (uint32_t)(len[p] / 16u);
+            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_HG_CHUNK - 1u) / HVQ_HG_CHUNK;
+            off += len[p];
+        }
+        max_wgs = std::max(max_wgs, j.wg_first[3]);
+    }
+    if (!hvq_launch_histograms) return fail(HVQ_E_NOGPU, "this build of the library has no histogram kernel (hvq_histogram.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqHistogramJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) {
+                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 3u * HVQ_HIST_BINS * sizeof(uint32_t), st);   /* the launch adds into the records */
+                              return e != hipSuccess ? e : hvq_launch_histograms(tab, n, max_wgs, st);
                           });
 }
 

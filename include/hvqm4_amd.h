@@ -373,6 +373,42 @@ int  hvq_picture_checksums(HvqContext *ctx, int n, const int *streams, const int
 uint32_t hvq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 uint32_t hvq_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
 
+/* Histograms of resident pictures, computed where they lie: for `n` pictures, of any streams, sizes and samplings, in ONE kernel launch on
+ * the caller's HIP stream and without a host synchronisation, per plane p = Y, U, V the 256-bin histogram of its samples as exact
+ * integers.  The distribution is what the sums of hvq_picture_metrics average away: median and percentiles, exposure and black-frame
+ * checks, Otsu thresholds, equalisation tables, scene cuts by histogram distance; and, of a picture against its reference, the maximum
+ * absolute error and the error percentiles.
+ *   mode HVQ_HIST_VALUES    out[p][v] = the number of samples of plane p of a_i that equal v.  ref must be NULL.
+ *   mode HVQ_HIST_ABSDIFF   out[p][d] = the number of positions of plane p where |a_i - b_i| equals d.  ref gives b_i.
+ *   Identities, in every mode:    sum over v of out[p][v] = the samples of plane p;
+ *       in HVQ_HIST_VALUES:       sum v out[p][v] = sum_a of hvq_picture_metrics;
+ *       in HVQ_HIST_ABSDIFF:      sum d out[p][d] = sad and sum d^2 out[p][d] = sse of hvq_picture_metrics for the same pair; a picture
+ *                                 against itself has every position in bin 0.
+ *   The counts are integers added with integer atomics: the record does not depend on the order the GPU adds in, the same call gives the
+ *   same bits every time.
+ *   out: `n` records of uint32_t [3 planes Y, U, V][HVQ_HIST_BINS], 3072 bytes each, dense, in call order, in DEVICE memory, a non-null
+ *       multiple of 4; the call writes all 3072 * n bytes whatever they held before (the caller does not zero them).  32 bits hold every
+ *       count: the largest plane the library opens is 8192 x 8192 = 2^26 samples.
+ *   a_i = the resident picture (streams[i], ordinals[i]).  If src != NULL and src[i] != NULL, a_i is the caller's device memory instead,
+ *       laid out as a picture of streams[i] (Y | U | V tightly packed, hvq_stream_pic_bytes long): src[i] must be a multiple of 16 and
+ *       ordinals[i] must be -1; the library cannot check its size; it is read when the work runs on `hip_stream`
+ *       (hvq_picture_checksums' src).
+ *   ref: HvqMetricsRef as for hvq_picture_ssim, its two non-trivial forms: stream >= 0 -- a resident picture of the same width, height and
+ *       sampling as streams[i], of any stream, ptr NULL; stream == -1 with ptr -- the caller's device memory, Y | U | V tightly packed, a
+ *       multiple of 16.  |a - 0| is a: in HVQ_HIST_ABSDIFF ref == NULL (with n > 0) and an entry { -1, *, NULL } are HVQ_E_ARG.
+ *   Lookup, HVQ_E_STATE cases (a or b queued but not flushed, slot reused, dropped), ordering on `hip_stream`, membership of the export
+ *   chain and slot safety are hvq_picture_metrics'; the batch in flight is ended only when a resident a_i or a resident b_i belongs to
+ *   it.  HVQ_E_ARG for a NULL context, a bad mode, a ref in HVQ_HIST_VALUES, a bad stream or ordinal, a src[i] that is not a multiple of 16
+ *   or comes with an ordinal other than -1, the refusals of `ref` above and of hvq_picture_metrics (geometry mismatch, ptr together with
+ *   stream >= 0, a stream below -1, a ptr that is not a multiple of 16), a null `out` or one that is not a multiple of 4, n above 65535.
+ *   n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a refused call enqueues nothing and
+ *   leaves `out` untouched.  HVQ_E_NOGPU (after those checks) from a build without the histogram kernel. */
+#define HVQ_HIST_BINS     256
+#define HVQ_HIST_VALUES   0      /* bin v counts the samples of a equal to v            */
+#define HVQ_HIST_ABSDIFF  1      /* bin d counts the positions where |a - b| equals d   */
+int  hvq_picture_histograms(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, int mode,
+                            const HvqMetricsRef *ref, uint32_t *out, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
