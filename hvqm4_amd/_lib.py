@@ -126,6 +126,9 @@ SYMBOLS = {
     "hvq_picture_checksums": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_picture_histograms": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "hvq_motion_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "hvq_picture_motion": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

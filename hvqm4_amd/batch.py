@@ -396,6 +396,54 @@ class Context:
                                            C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def picture_motion(self, sids, ordinals, ref, block=16, radius=8, out=None):
+        """hvq_picture_motion: the block-matching motion field (full search on luma, specified in include/hvqm4_amd.h) of resident
+        pictures a = (sids[i], ordinals[i]) against their references, in one launch on torch's current stream, without a host
+        synchronisation -> a list of n int32 CUDA tensors [rows, cols, 4] = per block (dy, dx, cost, cost_zero): the block looks like
+        the reference at (y + dy, x + dx) (`out`, if given: such a list, every tensor contiguous; they are overwritten whole).  `ref`
+        is required: a list with one entry per picture, (sid, ordinal) -- a resident picture of the same geometry -- or a contiguous
+        uint8 CUDA tensor of pic_bytes(sid) elements laid out as the pictures are.  `block` is 8 or 16 (16 only on streams whose width
+        and height are multiples of 16), `radius` 0 .. 15.  hvqm4_amd.motion reads the fields on the host.  Ordering and slot safety
+        are export()'s."""
+        import torch
+        from .export import check_one_hip_runtime
+        from .metrics import HvqMetricsRef, references
+        from .motion import MAX_RADIUS, blocks
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_RADIUS:
+            raise ValueError(f"radius {radius!r}: an integer in [0, {MAX_RADIUS}]")
+        dims = [blocks(self._geom[s][0], self._geom[s][1], block) for s in sids]
+        if ref is None:
+            raise ValueError("picture_motion needs a reference for every picture (motion against zeros means nothing)")
+        refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
+        for i, r in enumerate(refs):
+            if r[0] < 0 and r[2] is None:
+                raise ValueError(f"reference {i} is None: motion against zeros means nothing")
+        if out is None:
+            out = [torch.empty((r, c, 4), dtype=torch.int32, device="cuda") for r, c in dims]
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors")
+            for i, (t, (r, c)) in enumerate(zip(out, dims)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (r, c, 4) or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous int32 tensor of shape ({r}, {c}, 4)")
+                if t.device.type != "cuda":
+                    raise ValueError(f"out[{i}] is on {t.device}, not a GPU")
+            out = list(out)
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out[0].device).cuda_stream if n else None
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_r = C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
+        a_f = C.cast((C.c_void_p * n)(*[t.data_ptr() for t in out]), C.c_void_p)
+        check(lib().hvq_picture_motion(self._h, n, a_s, a_o, a_r, block, radius, a_f, C.c_void_p(stream)))
+        return out
+
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
         from .metrics import ssim_windows

@@ -371,5 +371,36 @@ static_assert(16ull * HVQ_HG_MAX_UNITS == (1ull << 26) && 16ull * HVQ_HG_MAX_UNI
 _Static_assert(sizeof(HvqHistogramJob) == 64, "HvqHistogramJob must be 64 bytes");
 #endif
 
+/* one picture of the motion launch (hvq_motion_kernel, hvq_picture_motion): the luma planes of picture `a` and of its reference `b`, both
+ * w x h bytes with pitch w, and the field int32 [rows][cols][4] = { dy, dx, cost, cost_zero } the launch writes, every record once with
+ * one 16-byte store.  Block size and radius are those of the call (launch arguments).  A workgroup of HVQ_MV_LANES lanes takes one tile of
+ * HVQ_MV_TILE x HVQ_MV_TILE samples of a, tiles_x tiles a row, tiles in all; it stages the tile's window of b, HVQ_MV_MAX_RADIUS at most
+ * wider on every side, into LDS, and each of its waves searches blocks of the tile.  A candidate's key is
+ * cost << 15 | (|dy| + |dx|) << 10 | (dy + R) << 5 | (dx + R): the smallest key is the winner of include/hvqm4_amd.h.
+ * Every member is a dword or a qword (scalar loads); 48 bytes. */
+#define HVQ_MV_LANES       256u     /* lanes of a workgroup */
+#define HVQ_MV_TILE        64u      /* samples of a tile's side: a multiple of both block sizes */
+#define HVQ_MV_MAX_RADIUS  15u      /* HVQ_MOTION_MAX_RADIUS */
+#define HVQ_MV_MAX_SIDE    32768u   /* w and h stay below this: byte offsets inside a plane fit 30 bits */
+typedef struct HvqMotionJob {
+    uint64_t a, b;                     /* device addresses of the luma planes, multiples of 16 */
+    uint64_t out;                      /* device address of the field, a multiple of 16 */
+    uint32_t w, h;                     /* luma samples, multiples of the block */
+    uint32_t rows, cols;               /* h / block, w / block */
+    uint32_t tiles_x, tiles;           /* ceil(w / HVQ_MV_TILE), tiles_x * ceil(h / HVQ_MV_TILE) */
+} HvqMotionJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqMotionJob) == 48, "HvqMotionJob must be 48 bytes");
+static_assert(sizeof(HvqMotionJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+static_assert(offsetof(HvqMotionJob, b) == 8 && offsetof(HvqMotionJob, out) == 16 && offsetof(HvqMotionJob, w) == 24 && offsetof(HvqMotionJob, rows) == 32 &&
+              offsetof(HvqMotionJob, tiles_x) == 40, "the members hvq_motion_kernel reads");
+static_assert(HVQ_MV_TILE % 16u == 0 && HVQ_MV_TILE % 8u == 0, "a tile is made of whole blocks of either size");
+/* the largest cost, 16 x 16 x 255, fits the 16 bits the key gives it, and the 16-bit lanes of v_qsad_pk_u16_u8 */
+static_assert(16u * 16u * 255u < (1u << 16) && 2u * HVQ_MV_MAX_RADIUS < (1u << 5), "the key's fields hold their values");
+#else
+_Static_assert(sizeof(HvqMotionJob) == 48, "HvqMotionJob must be 48 bytes");
+#endif
+
 
 #endif

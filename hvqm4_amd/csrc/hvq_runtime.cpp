@@ -75,6 +75,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_ssim(const void *jobs_dev
 extern "C" __attribute__((weak)) hipError_t hvq_launch_checksums(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 /* hvq_histogram.hip.  Weak for the same reason: hvq_picture_histograms then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_histograms(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
+/* hvq_motion.hip.  Weak for the same reason: hvq_picture_motion then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_motion(const void *jobs_dev, int njobs, uint32_t max_tiles, int block, int radius, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -2678,6 +2680,81 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
                               hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 3u * HVQ_HIST_BINS * sizeof(uint32_t), st);   /* the launch adds into the records */
                               return e != hipSuccess ? e : hvq_launch_histograms(tab, n, max_wgs, st);
                           });
+}
+
+/* Blocks of a motion field (include/hvqm4_amd.h): host only */
+HVQ_EXPORT int hvq_motion_blocks(int width, int height, int h_samp, int v_samp, int block, int32_t dims[2])
+{
+    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
+    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
+    hvq_parser_destroy(p);
+    if (block != 8 && block != 16) return fail(HVQ_E_ARG, "block %d (8 or 16)", block);
+    if (width % block || height % block) return fail(HVQ_E_ARG, "blocks of %d do not tile a %d x %d picture", block, width, height);
+    if (dims) { dims[0] = height / block; dims[1] = width / block; }
+    return (height / block) * (width / block);
+}
+
+/* Motion fields between resident pictures (include/hvqm4_amd.h: the specification): a seventh member of the export chain,
+ * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_ssim's references.  Only the launch goes behind the job table on the
+ * caller's stream (export_enqueue): it writes every record, nothing is zeroed in front of it. */
+HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
+                                  int block, int radius, int32_t *const *out, void *hip_stream)
+{
+    static_assert(HVQ_MOTION_MAX_RADIUS == HVQ_MV_MAX_RADIUS, "the kernel's largest radius is the header's");
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (block != 8 && block != 16) return fail(HVQ_E_ARG, "block %d (8 or 16)", block);
+    if (radius < 0 || radius > HVQ_MOTION_MAX_RADIUS) return fail(HVQ_E_ARG, "radius %d outside [0, %d]", radius, HVQ_MOTION_MAX_RADIUS);
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out) return fail(HVQ_E_ARG, "out is NULL");
+    if (!ref) return fail(HVQ_E_ARG, "motion needs a reference for every picture (ref is NULL)");
+    for (int i = 0; i < n; ++i)
+        if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "field %d: the pointer must be a non-null multiple of 16", i);
+    /* both sides of every pair decide whether the batch in flight has to end */
+    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
+    for (int i = 0; i < n; ++i)
+        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
+    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    std::vector<HvqMotionJob> jobs((size_t)n);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = HVQ_OK;
+        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
+        if (!a) return rc;
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const uint8_t *b = nullptr;
+        if (ref[i].stream >= 0) {
+            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
+            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
+            if (!b) return rc;
+            const Stream &r = c->streams[(size_t)ref[i].stream];
+            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
+                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
+                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
+        } else if (ref[i].stream != -1) {
+            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
+        } else if (ref[i].ptr) {
+            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
+            b = (const uint8_t *)ref[i].ptr;
+        } else {
+            return fail(HVQ_E_ARG, "reference %d: motion against a picture of zeros means nothing (stream -1 needs a pointer)", i);
+        }
+        if (s.w % block || s.h % block) return fail(HVQ_E_ARG, "picture %d: blocks of %d do not tile stream %d (%d x %d)", i, block, streams[i], s.w, s.h);
+        if ((uintptr_t)a & 15u || s.w >= (int)HVQ_MV_MAX_SIDE || s.h >= (int)HVQ_MV_MAX_SIDE)
+            return fail(HVQ_E_ARG, "picture %d: stream %d (%d x %d) is beyond what the motion kernel addresses", i, streams[i], s.w, s.h);
+        HvqMotionJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
+        j.out = (uint64_t)(uintptr_t)out[i];
+        j.w = (uint32_t)s.w; j.h = (uint32_t)s.h;
+        j.rows = j.h / (uint32_t)block; j.cols = j.w / (uint32_t)block;
+        j.tiles_x = (j.w + HVQ_MV_TILE - 1u) / HVQ_MV_TILE;
+        j.tiles = j.tiles_x * ((j.h + HVQ_MV_TILE - 1u) / HVQ_MV_TILE);
+        max_tiles = std::max(max_tiles, j.tiles);
+    }
+    if (!hvq_launch_motion) return fail(HVQ_E_NOGPU, "this build of the library has no motion kernel (hvq_motion.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqMotionJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_motion(tab, n, max_tiles, block, radius, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -409,6 +409,45 @@ uint32_t hvq_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
 int  hvq_picture_histograms(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, int mode,
                             const HvqMetricsRef *ref, uint32_t *out, void *hip_stream);
 
+/* Block-matching motion fields between resident pictures, computed where they lie: for `n` pictures, of any streams and sizes, in ONE
+ * kernel launch on the caller's HIP stream and without a host synchronisation, per block of picture a_i the displacement at which the
+ * reference b_i looks most like it.  Full search on the LUMA plane only; a is W x H luma samples, b has the same geometry.
+ *   Blocks.      block B is 8 or 16; rows = H / B, cols = W / B; block (r, c) is the B x B samples of a whose top-left corner is
+ *                (y0, x0) = (B r, B c).  Widths and heights are multiples of 8: B = 8 always tiles.  B = 16 on a stream whose width or
+ *                height is not a multiple of 16 is HVQ_E_ARG for the whole call: no sample is silently left out.
+ *   Candidates.  radius R, 0 <= R <= HVQ_MOTION_MAX_RADIUS.  The candidates of a block are the displacements (dy, dx) with |dy| <= R and
+ *                |dx| <= R whose displaced block lies wholly inside the picture: 0 <= y0 + dy, y0 + dy + B <= H, 0 <= x0 + dx,
+ *                x0 + dx + B <= W.  No padding; nothing outside plane Y of b is read.  (0, 0) is always a candidate.
+ *   Cost.        cost(dy, dx) = sum over 0 <= i, j < B of |a[y0 + i][x0 + j] - b[y0 + dy + i][x0 + dx + j]|, at most 65280.
+ *   Winner.      the candidate with the smallest tuple (cost, |dy| + |dx|, dy, dx) in lexicographic order, dy and dx compared as signed
+ *                integers: among equal costs the zero vector wins, then the shortest vector in L1, then the one furthest up, then the
+ *                one furthest left.  The rule does not depend on the order in which candidates are evaluated: the same call gives the
+ *                same bits every time.  (R <= 15 lets the tuple pack into 31 bits -- 16 of cost, 5 of L1, 5 of dy + R, 5 of dx + R.)
+ *   Sign.        block (r, c) of a looks like b at (y0 + dy, x0 + dx): with b the earlier picture, that is where the block came from.
+ *   Record.      per block int32_t [4] = { dy, dx, cost, cost_zero }, cost_zero = cost(0, 0); 16 bytes, written exactly once.  The
+ *                field of a picture is int32_t [rows][cols][4], row-major and dense.  The sum of cost_zero over the field is the Y sad
+ *                of hvq_picture_metrics for the same pair when B tiles the picture.
+ * hvq_motion_blocks (host only) returns rows * cols of a width x height picture and fills dims = { rows, cols } (dims may be NULL):
+ *   HVQ_E_GEOMETRY for a geometry hvq_stream_open refuses, HVQ_E_ARG for a block other than 8 or 16 and for B = 16 on a picture that is
+ *   not a multiple of 16 in both directions.
+ * hvq_picture_motion:
+ *   out[i]: a non-null DEVICE pointer, a multiple of 16, to the field of picture i (16 * hvq_motion_blocks bytes); every record of it is
+ *       written whatever was there before (no memset, no atomics); nothing outside it is written.
+ *   a_i = the resident picture (streams[i], ordinals[i]).  ref: HvqMetricsRef, its two non-trivial forms as for hvq_picture_ssim:
+ *       stream >= 0 -- a resident picture of the same width, height and sampling, of any stream, ptr NULL; stream == -1 with ptr -- the
+ *       caller's device memory in slot layout (Y first), a multiple of 16.  Motion against zeros means nothing: ref == NULL (with n > 0)
+ *       and an entry { -1, *, NULL } are HVQ_E_ARG.
+ *   Lookup, HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain and slot safety are hvq_picture_metrics'; the
+ *   batch in flight is ended only when a requested picture (a or b) belongs to it.  HVQ_E_ARG for a NULL context, a block other than 8 or
+ *   16, B = 16 on a stream it does not tile, a radius outside [0, HVQ_MOTION_MAX_RADIUS], a bad stream or ordinal, the refusals of `ref`
+ *   above and of hvq_picture_metrics, a null `out`, an out[i] that is null or not a multiple of 16, n above 65535.  n == 0 is HVQ_OK and
+ *   does nothing.  Every argument is checked before anything is enqueued: a refused call enqueues nothing and leaves every field
+ *   untouched.  HVQ_E_NOGPU (after those checks) from a build without the motion kernel. */
+#define HVQ_MOTION_MAX_RADIUS 15
+int  hvq_motion_blocks(int width, int height, int h_samp, int v_samp, int block, int32_t dims[2]);
+int  hvq_picture_motion(HvqContext *ctx, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
+                        int block, int radius, int32_t *const *out, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
