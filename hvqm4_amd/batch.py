@@ -444,6 +444,59 @@ class Context:
         check(lib().hvq_picture_motion(self._h, n, a_s, a_o, a_r, block, radius, a_f, C.c_void_p(stream)))
         return out
 
+    def encode_jpeg(self, sids, ordinals, quality=90, src=None, out=None, lengths=None):
+        """hvq_encode_jpeg: each picture (sids[i], ordinals[i]) as one complete baseline JPEG (JFIF) file (specified byte for byte in
+        include/hvqm4_amd.h) in device memory, on torch's current stream, without a host synchronisation -> (buffers, lengths): n uint8
+        CUDA tensors, file i at the start of buffers[i], and an int64 CUDA tensor [n] of the files' lengths.  A length larger than its
+        buffer says that the file did not fit (nothing of it was written): call again with that much room.  hvqm4_amd.jpeg.files turns the
+        pair into bytes on the host.  `out`, if given: a list of n contiguous uint8 CUDA tensors whose data pointers are multiples of 16,
+        of 631 elements at least (default: 2 * pic_bytes(sid) + 1024 each); `lengths`: a contiguous int64 CUDA tensor [n].  `src`, if
+        given: a list with one entry per picture, None or a contiguous uint8 CUDA tensor of pic_bytes(sid) elements laid out as the
+        pictures are; that memory is encoded in the picture's place and ordinals[i] must be -1.  Ordering and slot safety are export()'s."""
+        import torch
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+            raise ValueError(f"quality {quality!r}: an integer in [1, 100]")
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        if out is None:
+            out = [torch.empty(2 * self.pic_bytes(s) + 1024, dtype=torch.uint8, device="cuda") for s in sids]
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors")
+            for i, t in enumerate(out):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.numel() < 631:
+                    raise ValueError(f"out[{i}] must be a contiguous one-dimensional uint8 tensor of 631 elements at least")
+                if t.data_ptr() % 16:
+                    raise ValueError(f"out[{i}]: the data pointer must be a multiple of 16")
+                if t.device.type != "cuda":
+                    raise ValueError(f"out[{i}] is on {t.device}, not a GPU")
+            out = list(out)
+        if lengths is None:
+            lengths = torch.empty(n, dtype=torch.int64, device="cuda")
+        else:
+            if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int64 or tuple(lengths.shape) != (n,) or not lengths.is_contiguous():
+                raise ValueError(f"lengths must be a contiguous int64 tensor of shape ({n},)")
+            if lengths.device.type != "cuda":
+                raise ValueError(f"lengths is on {lengths.device}, not a GPU")
+        if not n:
+            return out, lengths
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(lengths.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_f = C.cast((C.c_void_p * n)(*[t.data_ptr() for t in out]), C.c_void_p)
+        a_c = C.cast((C.c_uint64 * n)(*[t.numel() for t in out]), C.c_void_p)
+        check(lib().hvq_encode_jpeg(self._h, n, a_s, a_o, a_p, quality, a_f, a_c, C.c_void_p(lengths.data_ptr()), C.c_void_p(stream)))
+        return out, lengths
+
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
         from .metrics import ssim_windows

@@ -402,5 +402,38 @@ static_assert(16u * 16u * 255u < (1u << 16) && 2u * HVQ_MV_MAX_RADIUS < (1u << 5
 _Static_assert(sizeof(HvqMotionJob) == 48, "HvqMotionJob must be 48 bytes");
 #endif
 
+/* one picture of the three JPEG launches (hvq_jpeg.hip, hvq_encode_jpeg): the picture in slot layout (Y | U | V), the file's destination
+ * with its capacity, where its length goes, and the picture's entries of the context's scratch: scr[scr_first] = 1 when the file fits its
+ * capacity (written by the layout launch), scr[scr_first + 1 + j] = the stuffed byte length of restart interval j (written by the measure
+ * launch), replaced by the interval's offset inside the file (layout launch), read by the emit launch.  A workgroup of HVQ_JP_LANES lanes
+ * takes one restart interval (one MCU row: mw MCUs of hs * vs + 2 blocks), one lane a block, HVQ_JP_LANES / (hs * vs + 2) whole MCUs a
+ * chunk.  The table is followed in the same upload by the quantisers of the call (HvqJpegQuant) and one header per distinct geometry
+ * (HVQ_JPEG_HEADER_SLOT bytes each); hdr_off is the byte offset of this picture's header from the start of the table.
+ * Every member is a dword or a qword (scalar loads); 64 bytes. */
+#define HVQ_JP_LANES     128u       /* lanes of a workgroup of the measure and emit launches: blocks of a chunk */
+#define HVQ_JP_MAX_SIDE  32768u     /* w and h stay below this */
+typedef struct HvqJpegJob {
+    uint64_t src;                      /* device address of the picture, a multiple of 16 */
+    uint64_t out;                      /* device address of the file, a multiple of 16 */
+    uint64_t cap;                      /* bytes at out */
+    uint64_t len;                      /* device address of lengths[i], a multiple of 8 */
+    uint32_t w, h;                     /* luma samples */
+    uint32_t hs, vs;                   /* sampling factors of luma, 1 or 2 */
+    uint32_t mw, mh;                   /* MCUs of a row, MCU rows = restart intervals */
+    uint32_t scr_first;                /* first of the picture's mh + 1 dwords of scratch */
+    uint32_t hdr_off;                  /* the picture's header, bytes from the start of the table */
+} HvqJpegJob;
+
+/* the quantisers of a call, hvq_jpeg_qpack of hvq_jpeg.h, [0] luminance and [1] chrominance, natural order */
+typedef struct HvqJpegQuant { uint32_t q[2][64]; } HvqJpegQuant;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqJpegJob) == 64 && sizeof(HvqJpegQuant) == 512, "HvqJpegJob must be 64 bytes, HvqJpegQuant 512");
+static_assert(offsetof(HvqJpegJob, out) == 8 && offsetof(HvqJpegJob, cap) == 16 && offsetof(HvqJpegJob, len) == 24 && offsetof(HvqJpegJob, w) == 32 &&
+              offsetof(HvqJpegJob, hs) == 40 && offsetof(HvqJpegJob, mw) == 48 && offsetof(HvqJpegJob, scr_first) == 56, "the members the JPEG kernels read");
+#else
+_Static_assert(sizeof(HvqJpegJob) == 64, "HvqJpegJob must be 64 bytes");
+#endif
+
 
 #endif

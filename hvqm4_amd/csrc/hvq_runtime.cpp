@@ -39,6 +39,7 @@
 #include "hvq_parse.h"
 #include "hvq_gparse_core.h"
 #include "hvq_checksum.h"
+#include "hvq_jpeg.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -77,6 +78,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_checksums(const void *job
 extern "C" __attribute__((weak)) hipError_t hvq_launch_histograms(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 /* hvq_motion.hip.  Weak for the same reason: hvq_picture_motion then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_motion(const void *jobs_dev, int njobs, uint32_t max_tiles, int block, int radius, hipStream_t stream);
+/* hvq_jpeg.hip.  Weak for the same reason: hvq_encode_jpeg then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_jpeg(const void *jobs_dev, int njobs, uint32_t max_mh, uint32_t quant_off, void *scratch, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -356,6 +359,9 @@ struct HvqContext {
      * chain runs behind the one before it, so the launch that zeroes and fills it comes after the launches that read it last */
     uint8_t *ck_acc = nullptr;
     size_t ck_cap = 0;
+    /* hvq_encode_jpeg: per picture of one call one dword and one per restart interval (HvqJpegJob).  One buffer serves every call, as ck_acc */
+    uint32_t *jp_scr = nullptr;
+    size_t jp_cap = 0;                 /* dwords */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
      * reads one set while the parse of batch k + 1 fills the other.  ps_live is the set the code below means by PS(c). */
@@ -659,6 +665,7 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     if (c->rgb_dev) (void)hipFree(c->rgb_dev);
     if (c->rgb_jobs_dev) (void)hipFree(c->rgb_jobs_dev);
     if (c->ck_acc) (void)hipFree(c->ck_acc);
+    if (c->jp_scr) (void)hipFree(c->jp_scr);
     for (auto &t : c->ex) {
         if (t.host) (void)hipHostFree(t.host);
         if (t.dev) (void)hipFree(t.dev);
@@ -2755,6 +2762,117 @@ HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, cons
     if (!hvq_launch_motion) return fail(HVQ_E_NOGPU, "this build of the library has no motion kernel (hvq_motion.hip is not linked)");
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqMotionJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_motion(tab, n, max_tiles, block, radius, st); });
+}
+
+/* The header and the bound of a JPEG file (include/hvqm4_amd.h): host only */
+static int jpeg_geometry(int width, int height, int h_samp, int v_samp)
+{
+    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
+    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
+    hvq_parser_destroy(p);
+    if (width >= (int)HVQ_JP_MAX_SIDE || height >= (int)HVQ_JP_MAX_SIDE || hvq_jpeg_bound_of((uint32_t)width, (uint32_t)height, (uint32_t)h_samp, (uint32_t)v_samp) >> 32)
+        return fail(HVQ_E_GEOMETRY, "%d x %d is beyond what a JPEG file of this library holds", width, height);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_jpeg_header(int width, int height, int h_samp, int v_samp, int quality, uint8_t *dst, size_t cap, size_t *len)
+{
+    { int rc = jpeg_geometry(width, height, h_samp, v_samp); if (rc) return rc; }
+    if (quality < 1 || quality > 100) return fail(HVQ_E_ARG, "quality %d outside [1, 100]", quality);
+    if (len) *len = HVQ_JPEG_HEADER_BYTES;
+    if (!dst || cap < HVQ_JPEG_HEADER_BYTES) return fail(HVQ_E_ARG, "the header takes %u bytes", HVQ_JPEG_HEADER_BYTES);
+    uint8_t buf[HVQ_JPEG_HEADER_SLOT];
+    if (hvq_jpeg_write_header((uint32_t)width, (uint32_t)height, (uint32_t)h_samp, (uint32_t)v_samp, quality, buf) != HVQ_JPEG_HEADER_BYTES)
+        return fail(HVQ_E_ARG, "internal: the header is not %u bytes", HVQ_JPEG_HEADER_BYTES);
+    memcpy(dst, buf, HVQ_JPEG_HEADER_BYTES);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT size_t hvq_jpeg_bound(int width, int height, int h_samp, int v_samp)
+{
+    if (jpeg_geometry(width, height, h_samp, v_samp)) return 0;
+    return (size_t)hvq_jpeg_bound_of((uint32_t)width, (uint32_t)height, (uint32_t)h_samp, (uint32_t)v_samp);
+}
+
+/* Baseline JPEG files of resident pictures (include/hvqm4_amd.h: the specification): an eighth member of the export chain,
+ * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_checksums' `src`.  The three launches go behind the job table on the
+ * caller's stream (export_enqueue); the table carries the call's quantisers and one header per distinct geometry behind the jobs; the
+ * scratch is the context's own, reused by every call: the chain orders the calls. */
+HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, int quality,
+                               void *const *out, const uint64_t *cap, uint64_t *lengths, void *hip_stream)
+{
+    static_assert(HVQ_JPEG_HEADER == HVQ_JPEG_HEADER_BYTES, "the kernel's header length is the header's");
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (quality < 1 || quality > 100) return fail(HVQ_E_ARG, "quality %d outside [1, 100]", quality);
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    if (!n) return HVQ_OK;
+    if (!out || !cap) return fail(HVQ_E_ARG, "out or cap is NULL");
+    if (!lengths || ((uintptr_t)lengths & 7u)) return fail(HVQ_E_ARG, "lengths must be a non-null multiple of 8");
+    for (int i = 0; i < n; ++i) {
+        if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "file %d: the pointer must be a non-null multiple of 16", i);
+        if (cap[i] < HVQ_JPEG_HEADER_BYTES + 2u) return fail(HVQ_E_ARG, "file %d: %llu bytes hold not even the header and EOI (%u)", i, (unsigned long long)cap[i], HVQ_JPEG_HEADER_BYTES + 2u);
+    }
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    const size_t quant_off = (size_t)n * sizeof(HvqJpegJob), hdr0 = quant_off + sizeof(HvqJpegQuant);
+    std::vector<uint8_t> table(hdr0);
+    std::vector<uint32_t> geoms;                                        /* w, h, hs << 4 | vs of every header in the table */
+    uint32_t max_mh = 0;
+    size_t scr_dwords = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const uint32_t hs = 1u << s.wshift, vs = 1u << s.hshift;
+        if (((uintptr_t)a & 15u) || s.w % 8 || s.h % 8 || s.w >= (int)HVQ_JP_MAX_SIDE || s.h >= (int)HVQ_JP_MAX_SIDE || hs > 2u || vs > 2u ||
+            hvq_jpeg_bound_of((uint32_t)s.w, (uint32_t)s.h, hs, vs) >> 32)
+            return fail(HVQ_E_ARG, "picture %d: stream %d (%d x %d) is beyond what the JPEG kernels address", i, streams[i], s.w, s.h);
+        HvqJpegJob j;
+        memset(&j, 0, sizeof j);
+        j.src = (uint64_t)(uintptr_t)a; j.out = (uint64_t)(uintptr_t)out[i]; j.cap = cap[i]; j.len = (uint64_t)(uintptr_t)(lengths + i);
+        j.w = (uint32_t)s.w; j.h = (uint32_t)s.h; j.hs = hs; j.vs = vs;
+        j.mw = hvq_jpeg_mw(j.w, hs); j.mh = hvq_jpeg_mh(j.h, vs);
+        j.scr_first = (uint32_t)scr_dwords;
+        scr_dwords += (size_t)j.mh + 1u;
+        if (scr_dwords >> 31) return fail(HVQ_E_ARG, "%d pictures have more restart intervals than one call takes", n);
+        max_mh = std::max(max_mh, j.mh);
+        size_t g = 0;
+        while (g < geoms.size() && !(geoms[g] == j.w && geoms[g + 1] == j.h && geoms[g + 2] == (hs << 4 | vs))) g += 3;
+        if (g == geoms.size()) {
+            geoms.insert(geoms.end(), { j.w, j.h, hs << 4 | vs });
+            table.resize(table.size() + HVQ_JPEG_HEADER_SLOT);
+            hvq_jpeg_write_header(j.w, j.h, hs, vs, quality, table.data() + table.size() - HVQ_JPEG_HEADER_SLOT);
+        }
+        j.hdr_off = (uint32_t)(hdr0 + g / 3u * HVQ_JPEG_HEADER_SLOT);
+        memcpy(table.data() + (size_t)i * sizeof j, &j, sizeof j);
+    }
+    HvqJpegQuant qt;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) qt.q[t][k] = hvq_jpeg_qpack(hvq_jpeg_q(HVQ_JPEG_QBASE[t][k], quality));
+    memcpy(table.data() + quant_off, &qt, sizeof qt);
+    if (!hvq_launch_jpeg) return fail(HVQ_E_NOGPU, "this build of the library has no JPEG kernels (hvq_jpeg.hip is not linked)");
+    if (scr_dwords > c->jp_cap) {
+        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
+        if (c->jp_scr) { HIPCHK(hipFree(c->jp_scr)); c->jp_scr = nullptr; c->jp_cap = 0; }
+        const size_t ncap = align_up(scr_dwords * 2, 1024);
+        HIPCHK(hipMalloc((void **)&c->jp_scr, ncap * sizeof(uint32_t)));
+        c->jp_cap = ncap;
+    }
+    uint32_t *scr = c->jp_scr;
+    return export_enqueue(c, table.data(), table.size(), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_jpeg(tab, n, max_mh, (uint32_t)quant_off, scr, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

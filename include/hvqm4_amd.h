@@ -448,6 +448,65 @@ int  hvq_motion_blocks(int width, int height, int h_samp, int v_samp, int block,
 int  hvq_picture_motion(HvqContext *ctx, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                         int block, int radius, int32_t *const *out, void *hip_stream);
 
+/* Baseline JPEG (JFIF) files of resident pictures, written where the pictures lie: for `n` pictures, of any streams, sizes and samplings,
+ * each becomes one complete file in the caller's DEVICE memory, on the caller's HIP stream and without a host synchronisation; the file
+ * lengths are left in device memory.  The codec's display arithmetic is JFIF's full-range Y / Cb / Cr and its samplings are JPEG's, so a
+ * file needs no colour conversion and no resampling and decodes to what the player shows.  The bytes are specified exactly:
+ *   Geometry.    W x H luma samples (multiples of 8), chroma planes (W / h_samp) x (H / v_samp).  An MCU is 8 h_samp x 8 v_samp luma samples;
+ *                mw = ceil(W / (8 h_samp)), mh = ceil(H / (8 v_samp)).  Every plane is extended to whole blocks by repeating its last column,
+ *                then its last row.  Blocks of an MCU: the Y blocks in raster order (v_samp rows of h_samp), then Cb (= U), then Cr (= V).
+ *   Transform.   Integers only.  x = sample - 128.  C[k][n] = floor(s_k cos((2 n + 1) k pi / 16) 8192 + 0.5), s_0 = sqrt(1 / 8), s_k = 1 / 2
+ *                otherwise, for n < 4; C[k][7 - n] = C[k][n] for even k, -C[k][n] for odd k.  Rows k = 0 .. 7, n = 0 .. 3:
+ *                    2896 2896 2896 2896 / 4017 3406 2276 799 / 3784 1567 -1567 -3784 / 3406 -799 -4017 -2276 /
+ *                    2896 -2896 -2896 2896 / 2276 -4017 799 3406 / 1567 -3784 3784 -1567 / 799 -2276 3406 -4017
+ *                Rows first: r[y][k] = (sum_n C[k][n] x[y][n] + 1024) >> 11; then columns: F[k][l] = (sum_y C[k][y] r[y][l] + 16384) >> 15,
+ *                both shifts arithmetic.  The sums are exact in 32 bits (below 2^23 and 2^27).  Any evaluation order or even/odd
+ *                factorisation that yields the same integers is allowed; no other intermediate rounding is.
+ *   Range.       With A = sum |C[k][y] C[l][n]| <= 23168^2 (rows 0 and 4 have the largest absolute sum, 8 x 2896): an AC basis has as much
+ *                positive as negative weight (every row k > 0 sums to 0), samples lie in [-128, 127], so the unrounded AC value is at most
+ *                255 A / 2 / 2^26 < 1019.9; the row rounding adds at most 23168 / 2 / 2^15 < 0.36 and the last rounding 0.5: |AC| <= 1020.
+ *                The unrounded DC lies in [-128, 127] A / 2^26 = [-1023.8, 1015.8]: -1024 <= DC <= 1016, differences below 2048.  So AC
+ *                sizes never exceed 10 and DC difference sizes never exceed 11: what the tables below code.
+ *   Quantising.  Base tables: ITU-T T.81 Annex K.1 (luminance) and K.2 (chrominance).  Quality q in 1 .. 100 scales them as the IJG
+ *                library does: s = 5000 / q (integer division) for q < 50, else 200 - 2 q; Q[i] = clamp((base[i] s + 50) / 100, 1, 255).
+ *                Coefficient = sign(F) ((|F| + (Q >> 1)) / Q), integer division.
+ *   Coding.      Baseline Huffman with the tables of Annex K.3 - K.6 (K.3 / K.5 for Y, K.4 / K.6 for Cb and Cr), zigzag order, DC
+ *                differences per component, (run, size) symbols, ZRL = 0xF0, EOB = 0x00 unless coefficient 63 is non-zero; a negative
+ *                value v of size s is written as v + 2^s - 1.  Restart interval = one MCU row (Ri = mw): every interval starts with the
+ *                three DC predictors at 0 and is padded with 1-bits to a byte; inside entropy data every 0xFF is followed by 0x00; interval
+ *                j < mh - 1 is followed by the marker FF D0 + (j mod 8).  Every MCU row is thus an independent, byte-aligned piece.
+ *   Segments.    In this order, HVQ_JPEG_HEADER (629) bytes up to the entropy data for every geometry and quality: SOI; APP0 "JFIF\0",
+ *                version 1.01, units 0, density 1 x 1, no thumbnail; DQT table 0 (8-bit, zigzag order); DQT table 1; SOF0, precision 8, H,
+ *                W, 3 components: id 1 sampling h_samp << 4 | v_samp table 0, id 2 0x11 table 1, id 3 0x11 table 1; DHT DC0, DHT AC0, DHT
+ *                DC1, DHT AC1, one segment each; DRI = mw; SOS, 3 components, table selectors 0x00 / 0x11 / 0x11, Ss 0, Se 63, Ah / Al 0;
+ *                the entropy data; EOI.
+ * hvq_jpeg_header (host only) writes those HVQ_JPEG_HEADER bytes to dst (cap bytes) and their count to *len (len may be NULL):
+ *   HVQ_E_GEOMETRY for a geometry hvq_stream_open refuses, HVQ_E_ARG for a quality outside 1 .. 100, a null dst or a cap below the count.
+ * hvq_jpeg_bound (host only): a length no file of this geometry exceeds at any quality, 0 for a refused geometry:
+ *   629 + 2 + 2 (mh - 1) + 2 mh ceil(mw (h_samp v_samp + 2) 64 x 26 / 8) -- header, EOI, the RST markers, and per interval its blocks at 26
+ *   bits a coefficient (the longest AC code, 16, with 10 value bits; a DC difference takes 11 + 11 at most; a ZRL stands for 16
+ *   coefficients in 11 bits), rounded up to a byte, every byte stuffed.
+ * hvq_encode_jpeg:
+ *   a_i = the resident picture (streams[i], ordinals[i]); with src != NULL, src[i] != NULL and ordinals[i] == -1 it is the caller's device
+ *       memory in slot layout (Y | U | V of stream streams[i]'s geometry, a multiple of 16), exactly as hvq_picture_checksums' src.
+ *   out[i]: a non-null DEVICE pointer, a multiple of 16, with cap[i] bytes (cap: host memory).  The file starts at out[i]; nothing at or
+ *       beyond out[i] + cap[i] is ever written.
+ *   lengths: a DEVICE pointer, a multiple of 8, to n values.  lengths[i] is always written and is the length of the complete file,
+ *       whether or not it fitted.  When lengths[i] <= cap[i] the bytes [0, lengths[i]) are the file, each written once, and the bytes
+ *       after them are untouched.  When it is larger the contents of out[i] within cap[i] are unspecified (this build writes none): call
+ *       again with more room.
+ *   Lookup, HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain and slot safety are hvq_picture_metrics'; the
+ *   batch in flight is ended only when a requested picture belongs to it.  HVQ_E_ARG for a NULL context, a quality outside 1 .. 100, a
+ *   bad stream or ordinal, a null `out`, `cap` or `lengths`, an out[i] that is null or not a multiple of 16, a `lengths` that is not a
+ *   multiple of 8, a cap[i] below HVQ_JPEG_HEADER + 2, a src[i] with an ordinal other than -1 or not a multiple of 16, n above 65535.
+ *   n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a refused call enqueues nothing and
+ *   leaves every destination and `lengths` untouched.  HVQ_E_NOGPU (after those checks) from a build without the JPEG kernels. */
+#define HVQ_JPEG_HEADER 629
+int    hvq_jpeg_header(int width, int height, int h_samp, int v_samp, int quality, uint8_t *dst, size_t cap, size_t *len);
+size_t hvq_jpeg_bound(int width, int height, int h_samp, int v_samp);
+int    hvq_encode_jpeg(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, int quality,
+                       void *const *out, const uint64_t *cap, uint64_t *lengths, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);

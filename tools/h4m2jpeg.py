@@ -1,0 +1,62 @@
+"""The pictures of an .h4m clip as JPEG files: demux, decode and encode on the device, one .jpg per picture in decode order
+(hvq_encode_jpeg: baseline JFIF, the clip's own Y / Cb / Cr and sampling, no colour conversion, no resampling).  What crosses PCIe is the
+bitstream one way and the compressed files the other; no decoded picture is read back.
+
+    python tools/h4m2jpeg.py clip.h4m outdir [--quality Q]
+
+writes outdir/<clip name>_<ordinal, 5 digits><frame type>.jpg.  torch is imported before the library, so both share one HIP runtime."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FRAME_TYPES = {0x10: "I", 0x20: "P", 0x30: "B"}
+
+
+def file_name(stem, k, ftype):
+    return f"{stem}_{k:05d}{FRAME_TYPES.get(ftype, 'X')}.jpg"
+
+
+def clip_files(ctx, data, quality):
+    """-> (frame types, files as bytes) of one clip: its pictures decoded into a stream of their own and encoded in one call"""
+    from hvqm4_amd import jpeg
+    from hvqm4_amd.container import parse_header, video_pictures
+    hdr = parse_header(data)
+    pics = [(ft, bytes(p)) for ft, _d, p in video_pictures(data)]
+    n = len(pics)
+    sid = ctx.open_stream(hdr.width, hdr.height, hdr.h_samp, hdr.v_samp, hdr.is15, n + 3)
+    for ft, p in pics:
+        ctx.submit(sid, ft, p)
+    ctx.flush()
+    buffers, lengths = ctx.encode_jpeg([sid] * n, list(range(n)), quality=quality)
+    files = jpeg.files(buffers, lengths)
+    ctx.close_stream(sid)
+    return [ft for ft, _p in pics], files
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("clip", help="an .h4m file")
+    ap.add_argument("outdir")
+    ap.add_argument("--quality", type=int, default=90, help="1 .. 100, scaled as the IJG library does")
+    args = ap.parse_args()
+    if not 1 <= args.quality <= 100:
+        ap.error("--quality takes 1 .. 100")
+    import torch
+    torch.cuda.init()
+    from hvqm4_amd import batch
+    os.makedirs(args.outdir, exist_ok=True)
+    stem = os.path.splitext(os.path.basename(args.clip))[0]
+    ctx = batch.Context(0)
+    types, files = clip_files(ctx, open(args.clip, "rb").read(), args.quality)
+    ctx.close()
+    for k, (ft, f) in enumerate(zip(types, files)):
+        with open(os.path.join(args.outdir, file_name(stem, k, ft)), "wb") as out:
+            out.write(f)
+    print(f"{len(files)} files, {sum(len(f) for f in files)} bytes, quality {args.quality} -> {args.outdir}")
+
+
+if __name__ == "__main__":
+    main()
