@@ -133,6 +133,9 @@ SYMBOLS = {
     "hvq_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hvq_encode_jpeg": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "hvq_picture_hashes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_hash_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

@@ -354,6 +354,70 @@ class Context:
         check(lib().hvq_picture_checksums(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def picture_hashes(self, sids, ordinals, src=None, out=None):
+        """hvq_picture_hashes: three 64-bit perceptual hashes of the luma plane of resident pictures (sids[i], ordinals[i]) -- aHash,
+        dHash and pHash as include/hvqm4_amd.h specifies them, exact integers -- and the sum of the luma samples, computed on the
+        device on torch's current stream, without a host synchronisation and without moving a picture -> int64 CUDA tensor [n, 4] =
+        (ahash, dhash, phash, sum_y) holding the bit patterns (`out`, if given: such a tensor, contiguous; it is overwritten whole).
+        hvqm4_amd.phash names the columns, gives the expected values of pictures on the host and the Hamming distances; hash_nearest
+        searches the records where they lie.  `src` as in picture_checksums: None, or per picture None (the resident picture) or a
+        contiguous uint8 CUDA tensor of pic_bytes(sid) elements hashed instead, with ordinal -1.  Ordering and slot safety are
+        export()'s."""
+        import torch
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        for s in sids:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 4)")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        check(lib().hvq_picture_hashes(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def hash_nearest(self, queries, database=None, self_offset=-1, threshold=10, out=None):
+        """hvq_hash_nearest: for every query hash the nearest database hash by Hamming distance, how many lie within `threshold` bits
+        and the first such, on torch's current stream, without a host synchronisation -> int32 CUDA tensor [nq, 4] = (nearest,
+        distance, within, first_within) (`out`, if given: such a tensor, contiguous, 16-byte aligned).  `queries`, `database`: int64
+        CUDA tensors [n], or [n, k] of which column 0 counts; the stride is the tensor's own, so records[:, phash.PHASH] searches one
+        column of picture_hashes' records where it lies.  self_offset < 0: every database hash is a candidate; otherwise query i sees
+        candidates j < self_offset + i ("earlier than me").  database None: the queries themselves with self_offset 0, which is
+        de-duplication of a sequence -- column first_within is then hvqm4_amd.phash.duplicates.  A query without a candidate gets
+        (-1, 65, 0, -1)."""
+        import torch
+        from .export import check_one_hip_runtime
+        from .phash import hash_views
+        if not 0 <= threshold <= 64:
+            raise ValueError(f"threshold {threshold} outside [0, 64]")
+        (qp, nq, qs), (dp, ndb, ds), off = hash_views(queries, database, self_offset)
+        if out is None:
+            out = torch.empty((nq, 4), dtype=torch.int32, device=queries.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (nq, 4) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous int32 tensor of shape ({nq}, 4)")
+            if out.data_ptr() & 15:
+                raise ValueError(f"out: pointer {out.data_ptr():#x} must be a multiple of 16")
+            if out.device.type != "cuda":
+                raise ValueError(f"out is on {out.device}, not a GPU")
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().hvq_hash_nearest(self._h, C.c_void_p(qp), nq, qs, C.c_void_p(dp) if ndb else None, ndb, ds, off, threshold,
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
     def picture_histograms(self, sids, ordinals, ref=None, src=None, out=None):
         """hvq_picture_histograms: per plane (Y, U, V) the 256-bin histogram of resident pictures a = (sids[i], ordinals[i]), in one
         launch on torch's current stream, without a host synchronisation -> int32 CUDA tensor [n, 3, 256] (`out`, if given: such a

@@ -435,5 +435,52 @@ static_assert(offsetof(HvqJpegJob, out) == 8 && offsetof(HvqJpegJob, cap) == 16 
 _Static_assert(sizeof(HvqJpegJob) == 64, "HvqJpegJob must be 64 bytes");
 #endif
 
+/* one picture of the two hash launches (hvq_phash.hip, hvq_picture_hashes): the luma plane `a` (w x h bytes, pitch w: the start of a slot,
+ * or of the caller's memory in a slot's layout), the picture's cells `acc` in library-owned memory, uint64 [HVQ_PH_ROWS][HVQ_PH_COLS],
+ * zeroed in front of the first launch, and the record uint64 [4] the finishing launch writes.  Cell (r, c) of acc is cell (r, c) of the
+ * 32 x 32 grid for c < 32 and cell (r, c - 32) of the 32-row x 9-column grid for c >= 32 (include/hvqm4_amd.h: S8 and D follow from them).
+ * A lane takes `cols` adjacent samples of a row (16, or 8 when w is no multiple of 16): a row has units = w / cols of them.  A workgroup of
+ * HVQ_PH_LANES lanes takes cells_pw = 1, 2, 4 or 8 consecutive row cells, HVQ_PH_LANES / cells_pw = sub_lanes lanes each (a power of two:
+ * lane l works on row cell l >> sub_shift of the workgroup's), and of every row HVQ_PH_LANES at most of its units: within a row cell lanes_x =
+ * min(units, HVQ_PH_LANES) lanes stand side by side and rows_pp = sub_lanes / lanes_x rows deep (at least 1: cells_pw is 1 when a row fills the
+ * workgroup).  Row cell r has the sample rows [h r / 32, ceil(h (r + 1) / 32)).  xchunks = ceil(units / HVQ_PH_LANES); workgroup g of the
+ * picture has the row cells (g % (32 / cells_pw)) * cells_pw .. and chunk g / (32 / cells_pw); wgs = 32 / cells_pw * xchunks, those past it
+ * leave.  Every member is a dword or a qword (scalar loads); 64 bytes. */
+#define HVQ_PH_LANES  256u          /* lanes of a workgroup, of both launches */
+#define HVQ_PH_ROWS   32u           /* row cells */
+#define HVQ_PH_COLS   41u           /* column cells: 32 + 9 */
+#define HVQ_PH_CELLS  (HVQ_PH_ROWS * HVQ_PH_COLS)
+#define HVQ_PH_MAX_CPW 8u           /* most row cells of a workgroup */
+#define HVQ_PH_MAX_SIDE 8192u       /* w and h stay at or below this: the widths of the accumulators (hvq_phash.hip) */
+#define HVQ_PH_BATCH  4096u         /* pictures of one launch pair: the runtime cuts a larger call, its cells stay below 42 MiB */
+typedef struct HvqHashJob {
+    uint64_t a;                        /* device address of the luma plane, a multiple of 16 */
+    uint64_t acc;                      /* device address of the cells, a multiple of 8 */
+    uint64_t out;                      /* device address of the record, a multiple of 8 */
+    uint32_t w, h;                     /* luma samples, multiples of 8 */
+    uint32_t units, lanes_x;
+    uint32_t rows_pp, wgs;
+    uint32_t cells_pw, sub_shift;      /* row cells of a workgroup; log2 of the lanes of one */
+    uint32_t pad[2];
+} HvqHashJob;
+
+/* hvq_hash_nearest: a workgroup of HVQ_HN_LANES lanes takes HVQ_HN_LANES queries, one a lane, and walks the database in tiles of HVQ_HN_TILE
+ * hashes staged in LDS */
+#define HVQ_HN_LANES  256u
+#define HVQ_HN_TILE   1024u
+#define HVQ_HN_MAX    (1u << 24)    /* HVQ_HASH_NEAREST_MAX: an index fits the low 24 bits of the key d << 24 | j */
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqHashJob) == 64, "HvqHashJob must be 64 bytes");
+static_assert(sizeof(HvqHashJob) % 16 == 0, "job tables are uploaded in 16-byte units");
+static_assert(offsetof(HvqHashJob, acc) == 8 && offsetof(HvqHashJob, out) == 16 && offsetof(HvqHashJob, w) == 24 && offsetof(HvqHashJob, units) == 32 &&
+              offsetof(HvqHashJob, rows_pp) == 40 && offsetof(HvqHashJob, cells_pw) == 48, "the members the hash kernels read");
+/* a cell is at most 255 w h: 64 bits hold it, 32 do not */
+static_assert(255ull * HVQ_PH_MAX_SIDE * HVQ_PH_MAX_SIDE < (1ull << 34) && 255ull * HVQ_PH_MAX_SIDE * HVQ_PH_MAX_SIDE > (1ull << 32), "a cell needs 64 bits");
+static_assert(HVQ_HN_TILE % HVQ_HN_LANES == 0, "every lane stages the same number of hashes of a tile");
+#else
+_Static_assert(sizeof(HvqHashJob) == 64, "HvqHashJob must be 64 bytes");
+#endif
+
 
 #endif

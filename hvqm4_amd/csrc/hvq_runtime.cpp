@@ -40,6 +40,7 @@
 #include "hvq_gparse_core.h"
 #include "hvq_checksum.h"
 #include "hvq_jpeg.h"
+#include "hvq_phash.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -80,6 +81,10 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_histograms(const void *jo
 extern "C" __attribute__((weak)) hipError_t hvq_launch_motion(const void *jobs_dev, int njobs, uint32_t max_tiles, int block, int radius, hipStream_t stream);
 /* hvq_jpeg.hip.  Weak for the same reason: hvq_encode_jpeg then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_jpeg(const void *jobs_dev, int njobs, uint32_t max_mh, uint32_t quant_off, void *scratch, hipStream_t stream);
+/* hvq_phash.hip.  Weak for the same reason: hvq_picture_hashes and hvq_hash_nearest then refuse with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_hashes(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_hash_nearest(const uint64_t *q, uint32_t nq, uint32_t q_stride, const uint64_t *db, uint32_t ndb, uint32_t db_stride,
+                                                                    int64_t self_offset, uint32_t threshold, int32_t *out, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -362,6 +367,10 @@ struct HvqContext {
     /* hvq_encode_jpeg: per picture of one call one dword and one per restart interval (HvqJpegJob).  One buffer serves every call, as ck_acc */
     uint32_t *jp_scr = nullptr;
     size_t jp_cap = 0;                 /* dwords */
+    /* hvq_picture_hashes: the cells of one launch pair's pictures, HVQ_PH_CELLS qwords each, HVQ_PH_BATCH pictures at the most.  One buffer
+     * serves every launch pair and every call, as ck_acc */
+    uint8_t *ph_acc = nullptr;
+    size_t ph_cap = 0;
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
      * reads one set while the parse of batch k + 1 fills the other.  ps_live is the set the code below means by PS(c). */
@@ -666,6 +675,7 @@ HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
     if (c->rgb_jobs_dev) (void)hipFree(c->rgb_jobs_dev);
     if (c->ck_acc) (void)hipFree(c->ck_acc);
     if (c->jp_scr) (void)hipFree(c->jp_scr);
+    if (c->ph_acc) (void)hipFree(c->ph_acc);
     for (auto &t : c->ex) {
         if (t.host) (void)hipHostFree(t.host);
         if (t.dev) (void)hipFree(t.dev);
@@ -2873,6 +2883,105 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
     uint32_t *scr = c->jp_scr;
     return export_enqueue(c, table.data(), table.size(), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_jpeg(tab, n, max_mh, (uint32_t)quant_off, scr, st); });
+}
+
+/* Perceptual hashes of resident pictures (include/hvqm4_amd.h: the specification): a ninth member of the export chain,
+ * hvq_picture_checksums' lookup, refusals, `src` and ordering.  The memset of the cells and the two launches go behind the job table on
+ * the caller's stream (export_enqueue), HVQ_PH_BATCH pictures a launch pair: the cells are the context's own, reused by every pair and
+ * every call -- the stream orders the pairs, the chain the calls. */
+#ifndef HVQ_PH_CPW
+#define HVQ_PH_CPW HVQ_PH_MAX_CPW      /* most row cells of a workgroup (measurements: 1, 2, 4) */
+#endif
+HVQ_EXPORT int hvq_picture_hashes(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                  uint64_t *out, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    std::vector<HvqHashJob> jobs((size_t)n);
+    uint32_t max_wgs = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        if (((uintptr_t)a & 15u) || (s.w & 7) || (s.h & 7) || s.w < 8 || s.h < 8 || s.w > (int)HVQ_PH_MAX_SIDE || s.h > (int)HVQ_PH_MAX_SIDE)
+            return fail(HVQ_E_ARG, "picture %d: stream %d (%d x %d) is beyond what the hash kernels address", i, streams[i], s.w, s.h);
+        HvqHashJob &j = jobs[(size_t)i];
+        memset(&j, 0, sizeof j);
+        j.a = (uint64_t)(uintptr_t)a;
+        j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 4u);
+        j.w = (uint32_t)s.w; j.h = (uint32_t)s.h;
+        j.units = j.w / ((j.w & 8u) ? 8u : 16u);
+        j.lanes_x = std::min(j.units, HVQ_PH_LANES);
+        /* as many row cells a workgroup as leave every cell a whole row of lanes: the work a lane does once per row cell (the column
+         * weights) is then shared by more rows (1, 2, 4 and 8 were measured) */
+        j.cells_pw = 1; j.sub_shift = 8;
+        while (j.cells_pw < HVQ_PH_CPW && (HVQ_PH_LANES >> 1 >> (8u - j.sub_shift)) >= j.lanes_x) { j.cells_pw *= 2u; --j.sub_shift; }
+        j.rows_pp = (HVQ_PH_LANES / j.cells_pw) / j.lanes_x;
+        j.wgs = HVQ_PH_ROWS / j.cells_pw * ((j.units + HVQ_PH_LANES - 1u) / HVQ_PH_LANES);
+        max_wgs = std::max(max_wgs, j.wgs);
+    }
+    if (!hvq_launch_hashes) return fail(HVQ_E_NOGPU, "this build of the library has no hash kernels (hvq_phash.hip is not linked)");
+    const size_t cell_bytes = (size_t)HVQ_PH_CELLS * 8u;
+    const size_t acc_bytes = (size_t)std::min(n, (int)HVQ_PH_BATCH) * cell_bytes;
+    if (acc_bytes > c->ph_cap) {
+        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
+        if (c->ph_acc) { HIPCHK(hipFree(c->ph_acc)); c->ph_acc = nullptr; c->ph_cap = 0; }
+        const size_t ncap = std::min(align_up(acc_bytes * 2, 4096), align_up((size_t)HVQ_PH_BATCH * cell_bytes, 4096));
+        HIPCHK(hipMalloc((void **)&c->ph_acc, ncap));
+        c->ph_cap = ncap;
+    }
+    uint8_t *acc = c->ph_acc;
+    for (int i = 0; i < n; ++i) jobs[(size_t)i].acc = (uint64_t)(uintptr_t)(acc + (size_t)(i % (int)HVQ_PH_BATCH) * cell_bytes);
+    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqHashJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) {
+                              for (int at = 0; at < n; at += (int)HVQ_PH_BATCH) {
+                                  const int cnt = std::min(n - at, (int)HVQ_PH_BATCH);
+                                  hipError_t e = hipMemsetAsync(acc, 0, (size_t)cnt * cell_bytes, st);    /* the first launch adds into them */
+                                  if (e == hipSuccess) e = hvq_launch_hashes((const HvqHashJob *)tab + at, cnt, max_wgs, st);
+                                  if (e != hipSuccess) return e;
+                              }
+                              return hipSuccess;
+                          });
+}
+
+/* Nearest hashes (include/hvqm4_amd.h: the specification).  The call reads no resident picture: no member of the export chain, one launch
+ * on the caller's stream. */
+HVQ_EXPORT int hvq_hash_nearest(HvqContext *c, const uint64_t *q, int nq, int q_stride, const uint64_t *db, int ndb, int db_stride,
+                                int64_t self_offset, int threshold, int32_t *out, void *hip_stream)
+{
+    static_assert(HVQ_HASH_NEAREST_MAX == HVQ_HN_MAX, "the kernel's key holds the header's counts");
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    if (nq < 0 || nq > HVQ_HASH_NEAREST_MAX || ndb < 0 || ndb > HVQ_HASH_NEAREST_MAX)
+        return fail(HVQ_E_ARG, "%d queries against %d hashes: each count lies in [0, %d]", nq, ndb, HVQ_HASH_NEAREST_MAX);
+    if (q_stride < 1 || db_stride < 1) return fail(HVQ_E_ARG, "strides %d and %d: a stride counts 64-bit words and is at least 1", q_stride, db_stride);
+    if (threshold < 0 || threshold > 64) return fail(HVQ_E_ARG, "threshold %d outside [0, 64]", threshold);
+    if (!nq) return HVQ_OK;
+    if (!q || ((uintptr_t)q & 7u)) return fail(HVQ_E_ARG, "q must be a non-null multiple of 8");
+    if (ndb && (!db || ((uintptr_t)db & 7u))) return fail(HVQ_E_ARG, "db must be a non-null multiple of 8");
+    if (!out || ((uintptr_t)out & 15u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 16");
+    if (!hvq_launch_hash_nearest) return fail(HVQ_E_NOGPU, "this build of the library has no hash kernels (hvq_phash.hip is not linked)");
+    HIPCHK(hipSetDevice(c->device));
+    /* an offset that admits every candidate for every query is "all" */
+    const int64_t off = self_offset < 0 || self_offset >= (int64_t)ndb ? -1 : self_offset;
+    HIPCHK(hvq_launch_hash_nearest(q, (uint32_t)nq, (uint32_t)q_stride, db, (uint32_t)ndb, (uint32_t)db_stride, off, (uint32_t)threshold, out,
+                                   (hipStream_t)hip_stream));
+    return HVQ_OK;
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

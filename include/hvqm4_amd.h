@@ -507,6 +507,82 @@ size_t hvq_jpeg_bound(int width, int height, int h_samp, int v_samp);
 int    hvq_encode_jpeg(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, int quality,
                        void *const *out, const uint64_t *cap, uint64_t *lengths, void *hip_stream);
 
+/* Perceptual hashes of resident pictures, computed where they lie: for `n` pictures, of any streams, sizes and samplings, in one kernel
+ * launch and a small finishing launch behind it, on the caller's HIP stream and without a host synchronisation, three 64-bit hashes of
+ * the luma plane.  "Have I seen this picture before?" is then a matter of Hamming distances between 8-byte values (hvq_hash_nearest);
+ * no picture moves.  The values are specified as exact integers: this text is the authority for them.  It is a construction of the same
+ * kind as the well-known aHash, dHash and pHash and makes no claim to equal the output of any library (those shrink pictures with float
+ * filters).
+ *   Plane.       Everything works on the luma plane only: a[y][x], W x H samples of 8 bits, W and H multiples of 8 up to 8192 (what
+ *                hvq_stream_open accepts).  Chroma and sampling only matter for locating plane Y in the slot.
+ *   Area grids.  A grid of gy rows x gx columns divides the plane into equal rectangles with rational edges.  In integers:
+ *                wy(r, y) = max(0, min(gy y + gy, H r + H) - max(gy y, H r)) for 0 <= r < gy, 0 <= y < H; wx(c, x) the same with gx and W.
+ *                Cell sum S[r][c] = sum over y, x of wy(r, y) wx(c, x) a[y][x].  Every cell has total weight W H (sum_r wy = gy,
+ *                sum_y wy(r, y) = H); S <= 255 W H < 2^34: a cell is a 64-bit integer (a 32-bit cell is wrong from W H = 16 843 010
+ *                samples on).  Nothing is rounded.  A plane narrower or lower than the grid spreads a sample over several cells; the
+ *                formula is unchanged.  Three grids are used: S32 (32 x 32), S8 (8 x 8) and D (8 rows x 9 columns).  Two identities
+ *                hold, and an implementation may rely on them: 16 S8[r][c] = the sum of the 4 x 4 block of S32 at (4 r, 4 c);
+ *                4 D[r][c] = the sum of rows 4 r .. 4 r + 3 of the 32-row x 9-column grid.
+ *   Bit order.   A hash is 64 bits taken row-major from an 8 x 8 array of booleans: element (r, c) is bit 63 - (8 r + c).  Printed as 16 hex
+ *                digits it reads left to right, top to bottom.
+ *   aHash.       T = sum of all S8 (= 64 sum a).  bit(r, c) = 64 S8[r][c] > T.
+ *   dHash.       bit(r, c) = D[r][c + 1] > D[r][c], 0 <= c < 8.
+ *   pHash.       m[r][c] = (16 S32[r][c] + (W H >> 1)) / (W H), integer division: the cell mean in sixteenths, 0 .. 4080.
+ *                F[k][l] = sum over r, c of C[k][r] C[l][c] m[r][c] for 0 <= k, l < 8, exact, |F| < 2^46 (the pass over c fits 32 bits,
+ *                the pass over r needs 64).  Sort the 64 values, f_0 <= ... <= f_63: bit(k, l) = 2 F[k][l] > f_31 + f_32 -- "above the
+ *                median", the even-count median without its division.
+ *                C[k][n] = floor(4096 cos((2 n + 1) k pi / 64) + 0.5): the unnormalised DCT-II.  C[0][n] = 4096 and
+ *                C[k][31 - n] = (-1)^k C[k][n].  The table is committed as constants (hvq_phash.h); rows k = 1 .. 7, n = 0 .. 15:
+ *                    4091 4052 3973 3857 3703 3513 3290 3035 2751 2440 2106 1751 1380 995 601 201
+ *                    4076 3920 3612 3166 2598 1931 1189 401 -401 -1189 -1931 -2598 -3166 -3612 -3920 -4076
+ *                    4052 3703 3035 2106 995 -201 -1380 -2440 -3290 -3857 -4091 -3973 -3513 -2751 -1751 -601
+ *                    4017 3406 2276 799 -799 -2276 -3406 -4017 -4017 -3406 -2276 -799 799 2276 3406 4017
+ *                    3973 3035 1380 -601 -2440 -3703 -4091 -3513 -2106 -201 1751 3290 4052 3857 2751 995
+ *                    3920 2598 401 -1931 -3612 -4076 -3166 -1189 1189 3166 4076 3612 1931 -401 -2598 -3920
+ *                    3857 2106 -601 -3035 -4091 -3290 -995 1751 3703 3973 2440 -201 -2751 -4052 -3513 -1380
+ *                No entry is within 0.02 of a rounding tie.  Every row k > 0 sums to exactly 0: a constant added to the picture changes
+ *                only F[0][0].
+ *   Known answers.  A flat picture of value v > 0, any size: { 0, 0, 0x8000000000000000, v W H }; of value 0: { 0, 0, 0, 0 } (all F are
+ *                0, none is above the median).  64 x 64 with columns 0 .. 31 = 255 and the rest 0: ahash 0xF0F0F0F0F0F0F0F0, dhash 0; its
+ *                mirror: ahash 0x0F0F0F0F0F0F0F0F, dhash 0x1818181818181818 (column 4 of the 9-column grid is half covered).  ahash
+ *                and dhash are invariant under a + c without clipping; phash too while F[0][0] stays above f_32.
+ *   out: `n` records of uint64_t [4] = { ahash, dhash, phash, sum_y } (HVQ_HASH_*), 32 bytes each, dense, in call order, in DEVICE memory, a
+ *       multiple of 8.  sum_y = T / 64, the plain sum of the luma samples (sum_a of plane Y of hvq_picture_metrics).  The call writes all
+ *       32 n bytes whatever they held before.  All sums are integer sums: the record does not depend on the order the GPU adds in.
+ *   a_i, `src`, lookup, HVQ_E_STATE and HVQ_E_ARG cases, n <= 65535, ordering on `hip_stream`, membership of the export chain, slot safety
+ *   and ending the batch in flight only when a requested picture belongs to it are hvq_picture_checksums', word for word.  n == 0 is
+ *   HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a refused call leaves `out` untouched.  HVQ_E_NOGPU
+ *   (after those checks) from a build without the hash kernels. */
+#define HVQ_HASH_AHASH 0
+#define HVQ_HASH_DHASH 1
+#define HVQ_HASH_PHASH 2
+#define HVQ_HASH_SUM_Y 3
+int  hvq_picture_hashes(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src, uint64_t *out,
+                        void *hip_stream);
+
+/* Nearest hashes by Hamming distance, on hashes that lie in DEVICE memory: one launch on `hip_stream`, no host synchronisation.
+ *   q, db: device pointers, multiples of 8.  Query i is q[i * q_stride], candidate j is db[j * db_stride]; the strides count uint64_t and
+ *       are at least 1 (a stride of 4 walks one column of hvq_picture_hashes' records).  q and db may overlap or be equal.
+ *   d(i, j) = popcount(q_i ^ db_j).  The candidates of query i are all 0 <= j < ndb when self_offset < 0, otherwise those with
+ *       j < self_offset + i ("earlier than me": q == db with offset 0 is de-duplication in place; a block of queries starting at k uses
+ *       offset k).
+ *   out: `nq` records of int32_t [4] = { nearest, distance, within, first_within } (HVQ_NEAR_*), 16 bytes each, dense, in DEVICE memory, a
+ *       multiple of 16.  nearest is the candidate with the smallest (d, j), distance its d; within is the number of candidates with
+ *       d <= threshold, first_within the smallest such j or -1.  A query without candidates has { -1, 65, 0, -1 }.  Every record is
+ *       written exactly once (one 16-byte store) and does not depend on the order of evaluation.
+ *   0 <= threshold <= 64; 0 <= nq, ndb <= HVQ_HASH_NEAREST_MAX (2^24).  nq == 0 does nothing; ndb == 0 writes the empty records.
+ *   The call reads no resident picture and is no member of the export chain: it is just a launch on `hip_stream`, ordered by that
+ *   stream behind the work that produced the hashes.  HVQ_E_ARG for a NULL context, a NULL or misaligned q, db (with ndb > 0) or out, a
+ *   stride below 1, a threshold outside 0 .. 64, a count out of range; a refused call leaves `out` untouched.  HVQ_E_NOGPU (after those
+ *   checks) from a build without the hash kernels. */
+#define HVQ_NEAR_NEAREST 0
+#define HVQ_NEAR_DISTANCE 1
+#define HVQ_NEAR_WITHIN 2
+#define HVQ_NEAR_FIRST_WITHIN 3
+#define HVQ_HASH_NEAREST_MAX (1 << 24)
+int  hvq_hash_nearest(HvqContext *ctx, const uint64_t *q, int nq, int q_stride, const uint64_t *db, int ndb, int db_stride,
+                      int64_t self_offset, int threshold, int32_t *out, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
