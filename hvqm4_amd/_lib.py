@@ -64,6 +64,10 @@ class HvqStats(C.Structure):
                 ("launch_queues", C.c_uint32), ("queue_bytes", C.c_uint64), ("copy_bytes", C.c_uint64), ("copy_seconds", C.c_double)]
 
 
+class HvqScaleDst(C.Structure):                 # include/hvqm4_amd.h: a destination of hvq_scale_pictures
+    _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "crop_x", "crop_y", "crop_w", "crop_h")]
+
+
 # every symbol include/hvqm4.h and include/hvqm4_amd.h declare: (restype, argtypes)
 SYMBOLS = {
     "HVQM4InitDecoder": (None, []),
@@ -136,6 +140,10 @@ SYMBOLS = {
     "hvq_picture_hashes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_hash_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p,
                                    C.c_void_p]),
+    "hvq_scale_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_scale_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hvq_scale_body": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hvq_scale_force_direct": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

@@ -7,13 +7,18 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import HVQ_E_ARG, HvqError, HvqStats, check, lib
+from ._lib import HVQ_E_ARG, HvqError, HvqScaleDst, HvqStats, check, lib
+
+# HvqScaleDst as a numpy record: a pointer and eight int32 (width, height, h_samp, v_samp, crop_x, crop_y, crop_w, crop_h)
+_SCALE_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (8,))])
+assert _SCALE_DST.itemsize == C.sizeof(HvqScaleDst)
 
 
 class Context:
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
         self._geom = {}                                    # stream id -> (width, height), for export()
+        self._geom4 = {}                                   # stream id -> (width, height, h_samp, v_samp), filled by _geometry
         check(lib().hvq_context_create(device, C.byref(self._h)))
 
     def set_launch_queues(self, n: int) -> None:
@@ -29,6 +34,7 @@ class Context:
     def close_stream(self, sid: int) -> None:
         check(lib().hvq_stream_close(self._h, sid))
         self._geom.pop(sid, None)
+        self._geom4.pop(sid, None)
 
     def set_parse_threads(self, sid: int, threads: int) -> int:
         """host threads that share the parse of ONE picture of this stream (hvq_stream_set_parse_threads); returns the count in effect"""
@@ -560,6 +566,102 @@ class Context:
         a_c = C.cast((C.c_uint64 * n)(*[t.numel() for t in out]), C.c_void_p)
         check(lib().hvq_encode_jpeg(self._h, n, a_s, a_o, a_p, quality, a_f, a_c, C.c_void_p(lengths.data_ptr()), C.c_void_p(stream)))
         return out, lengths
+
+    def _geometry(self, sid):
+        """(width, height, h_samp, v_samp) of an open stream"""
+        g = self._geom4.get(sid)
+        if g is None:
+            w, h = self._geom[sid][:2]
+            y = w * h
+            c = (self.pic_bytes(sid) - y) // 2
+            g = self._geom4[sid] = (w, h) + {y // 4: (2, 2), y // 2: (2, 1), y: (1, 1)}[c]
+        return g
+
+    def scale_force_direct(self, on: bool) -> bool:
+        """hvq_scale_force_direct: every later scale_pictures of this context takes the direct body of the kernel (False: the chosen
+        one again) -> the setting before.  The values do not depend on it: for tests that compare the two with =="""
+        return bool(check(lib().hvq_scale_force_direct(self._h, int(bool(on)))))
+
+    def scale_pictures(self, sids, ordinals, size, sampling=None, crop=None, src=None, out=None):
+        """hvq_scale_pictures: resident pictures (sids[i], ordinals[i]) resampled plane by plane with the area filter (exact integers,
+        one rounding: include/hvqm4_amd.h) into uint8 pictures of another geometry IN SLOT LAYOUT (Y | U | V), on torch's current
+        stream, without a host synchronisation and without moving a picture.  `size`: (w, h), or one such pair per picture;
+        `sampling`: None (the source's), (h_samp, v_samp), or one per picture (None entries: the source's); `crop`: None (the whole
+        picture), (x, y, w, h) in luma samples, or one per picture.  -> when every target geometry is the same one uint8 CUDA tensor
+        [n, bytes], otherwise a list of n 1-D uint8 CUDA tensors (`out`, if given: of that same form, contiguous, rows 16-byte
+        aligned; it is overwritten whole).  Whatever takes src= or ref.ptr takes a row of the result, with an open stream of the
+        target geometry to carry it.  hvqm4_amd.scale gives the expected bytes (of_picture), the plane views and the target sizes
+        (fit, pyramid).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
+        import torch
+        from . import scale as sc
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        if n > 65535:
+            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        streams = set(sids)
+        for s in streams:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        sizes, one_size = sc.per_picture(size, n, 2, "size")
+        if n and (sizes[0] is None if one_size else any(v is None for v in sizes)):
+            raise ValueError("size: every picture needs a target size")
+        samplings, one_sampling = sc.per_picture(sampling, n, 2, "sampling")
+        crops, one_crop = sc.per_picture(crop, n, 4, "crop")
+        # a call usually repeats few shapes: each distinct (source geometry, size, sampling, crop) is looked at once
+        geoms = {s: self._geometry(s) for s in streams}
+        if n and one_size and one_sampling and one_crop and len(set(geoms.values())) == 1:
+            keys = [(geoms[sids[0]], sizes[0], samplings[0], crops[0])] * n
+            distinct = keys[:1]
+        else:
+            keys = list(zip(map(geoms.__getitem__, sids), sizes, samplings, crops))
+            distinct = set(keys)
+        shapes = {}
+        for key in distinct:
+            g, sz, sm, cr = key
+            dst = sz + (sm or g[2:])
+            sc.plane_sizes(g, dst, cr)                                    # ValueError beyond the library's limits
+            shapes[key] = (dst, sc.nbytes(*dst), dst + (cr or (0, 0, 0, 0)))
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        dst_geoms = {v[0] for v in shapes.values()}
+        uniform = len(dst_geoms) == 1
+        nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
+        if out is None:
+            out = torch.empty((n, nb[0]), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
+        if uniform:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0]) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0]})")
+            device = out.device
+            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0]) + np.uint64(out.data_ptr())       # rows of a multiple of 16 bytes
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors (the target geometries differ)")
+            for i, t in enumerate(out):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
+            device = out[0].device if n else torch.device("cuda")
+            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
+            if len({t.get_device() for t in out}) > 1:
+                raise ValueError("out: the tensors lie on different devices")
+        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
+            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
+            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
+        if device.type != "cuda":
+            raise ValueError(f"out is on {device}, not a GPU")
+        if not n:
+            return out
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_d = np.empty(n, dtype=_SCALE_DST)                                  # HvqScaleDst[n]
+        a_d["ptr"] = where
+        a_d["rest"] = shapes[keys[0]][2] if len(shapes) == 1 else [shapes[k][2] for k in keys]
+        check(lib().hvq_scale_pictures(self._h, n, a_s, a_o, a_p, C.c_void_p(a_d.ctypes.data), C.c_void_p(stream)))
+        return out
 
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""

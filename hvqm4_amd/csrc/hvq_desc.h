@@ -483,4 +483,56 @@ _Static_assert(sizeof(HvqHashJob) == 64, "HvqHashJob must be 64 bytes");
 #endif
 
 
+/* one plane of one picture of the scale launch (hvq_scale.hip, hvq_scale_pictures): three jobs a picture, Y, U, V.  `src` is the first
+ * sample of the crop's part of the source plane (any byte address inside the picture: the picture itself starts and ends on a multiple of
+ * 16, and pitch is a multiple of 4, so the dwords around a row of the crop lie inside the picture), ny rows of nx samples, `pitch` bytes
+ * from row to row; `dst` is the target plane, my rows of mx samples, dense (pitch mx: a multiple of 4, as dst is).  The values are
+ * include/hvqm4_amd.h's: out = (S + (D >> 1)) / D with D = nx ny, as the high 64 bits of (S + (D >> 1)) * magic, magic = ceil(2^64 / D)
+ * (hvq_scale.h: why that is exact).  Grid row = picture, its three jobs one behind the other; a workgroup of HVQ_SC_LANES lanes takes a
+ * tile of one plane -- HVQ_SC_TW x HVQ_SC_TH target samples in the tiled body, HVQ_SC_DTW x HVQ_SC_DTH in the direct one: tiles_x tiles
+ * side by side, `tiles` in all; the workgroups of a grid row walk the tiles of Y, then U, then V, those past them leave.  body
+ * HVQ_SC_DIRECT: a lane computes four adjacent samples in each of four rows from global memory (at most 2 x 2 taps each when chosen).  body HVQ_SC_TILED: the tile's source rows go through LDS, `chunk` rows at a
+ * time, `row_dwords` dwords a row (the most a tile of this plane needs); horizontal sums of a chunk once (32 bits: at most 255 nx <
+ * 2^21), then the vertical pass into cells of 32 bits when 255 nx ny < 2^32 and of 64 bits (HVQ_SC_WIDE) otherwise.  The first and last
+ * source of a target, floor(n r / m) and ceil(n (r + 1) / m), are a multiplication and a shift with mul_x / mul_y.  Every member is a dword
+ * or a qword (scalar loads); 80 bytes. */
+#define HVQ_SC_LANES  256u
+#define HVQ_SC_TW     64u           /* target samples a tile is wide: 16 dwords, one store a lane and row */
+#define HVQ_SC_TH     16u           /* target rows of a tile */
+#define HVQ_SC_DTW    256u          /* the direct body's tile: a wave stores 256 adjacent bytes of a row, a lane four rows 4 apart */
+#define HVQ_SC_DTH    16u
+#define HVQ_SC_RAW_DWORDS 4096u     /* LDS of the staged source rows of a chunk */
+#define HVQ_SC_MAX_CHUNK 32u        /* most source rows of a chunk */
+#define HVQ_SC_MAX_RATIO 32u        /* n <= 32 m per plane and axis */
+#define HVQ_SC_DIRECT 0u
+#define HVQ_SC_TILED  1u
+#define HVQ_SC_WIDE   2u
+typedef struct HvqScaleJob {
+    uint64_t src;                      /* device address of the first sample of the crop in the source plane */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint64_t magic;                    /* ceil(2^64 / (nx ny)) */
+    uint32_t pitch;                    /* bytes between source rows, a multiple of 4 */
+    uint32_t nx, ny;                   /* source samples of the crop */
+    uint32_t mx, my;                   /* target samples: mx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t body;                     /* HVQ_SC_DIRECT or HVQ_SC_TILED, | HVQ_SC_WIDE: cells of 64 bits */
+    uint32_t chunk, row_dwords;        /* the tiled body's: chunk * row_dwords <= HVQ_SC_RAW_DWORDS, 1 <= chunk <= HVQ_SC_MAX_CHUNK */
+    uint32_t mul_x, shift_x;           /* v / mx = v * mul_x >> shift_x for v < 2^27 (hvq_scale.h): no lane divides */
+    uint32_t mul_y, shift_y;           /* likewise by my */
+} HvqScaleJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqScaleJob) == 80 && sizeof(HvqScaleJob) % 16 == 0, "HvqScaleJob must be 80 bytes: job tables are uploaded in 16-byte units");
+static_assert(offsetof(HvqScaleJob, dst) == 8 && offsetof(HvqScaleJob, magic) == 16 && offsetof(HvqScaleJob, pitch) == 24 && offsetof(HvqScaleJob, tiles_x) == 44 &&
+              offsetof(HvqScaleJob, body) == 52 && offsetof(HvqScaleJob, chunk) == 56 && offsetof(HvqScaleJob, mul_x) == 64 && offsetof(HvqScaleJob, mul_y) == 72, "the members the scale kernel reads");
+static_assert(HVQ_SC_TW * HVQ_SC_TH == HVQ_SC_LANES * 4u, "a lane stores one dword of the tile");
+static_assert(HVQ_SC_DTW == 64u * 4u && HVQ_SC_DTH * 64u == HVQ_SC_LANES * 4u, "the direct body: 64 lanes side by side, four waves, four rows a lane");
+static_assert(HVQ_SC_MAX_CHUNK == 32u, "a wave stages eight rows of a chunk, all loads issued before the first is used");
+/* the widest row of a tile: 64 targets at 32 sources each, one more at each edge, three bytes of alignment in front, rounded up */
+static_assert((HVQ_SC_TW * HVQ_SC_MAX_RATIO + 2u + 3u + 3u) / 4u <= HVQ_SC_RAW_DWORDS, "a chunk holds one row at least");
+#else
+_Static_assert(sizeof(HvqScaleJob) == 80, "HvqScaleJob must be 80 bytes");
+#endif
+
+
 #endif

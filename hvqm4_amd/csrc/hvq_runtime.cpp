@@ -41,6 +41,7 @@
 #include "hvq_checksum.h"
 #include "hvq_jpeg.h"
 #include "hvq_phash.h"
+#include "hvq_scale.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -85,6 +86,9 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_jpeg(const void *jobs_dev
 extern "C" __attribute__((weak)) hipError_t hvq_launch_hashes(const void *jobs_dev, int njobs, uint32_t max_wgs, hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_hash_nearest(const uint64_t *q, uint32_t nq, uint32_t q_stride, const uint64_t *db, uint32_t ndb, uint32_t db_stride,
                                                                     int64_t self_offset, uint32_t threshold, int32_t *out, hipStream_t stream);
+
+/* hvq_scale.hip.  Weak for the same reason: hvq_scale_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -371,6 +375,7 @@ struct HvqContext {
      * serves every launch pair and every call, as ck_acc */
     uint8_t *ph_acc = nullptr;
     size_t ph_cap = 0;
+    bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
      * reads one set while the parse of batch k + 1 fills the other.  ps_live is the set the code below means by PS(c). */
@@ -2982,6 +2987,119 @@ HVQ_EXPORT int hvq_hash_nearest(HvqContext *c, const uint64_t *q, int nq, int q_
     HIPCHK(hvq_launch_hash_nearest(q, (uint32_t)nq, (uint32_t)q_stride, db, (uint32_t)ndb, (uint32_t)db_stride, off, (uint32_t)threshold, out,
                                    (hipStream_t)hip_stream));
     return HVQ_OK;
+}
+
+/* Scaled copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a tenth member of the export chain,
+ * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_checksums' `src`.  Three jobs a picture, one per plane; one launch
+ * behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no
+ * memset. */
+static int scale_geometry(int width, int height, int h_samp, int v_samp)
+{
+    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
+    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
+    hvq_parser_destroy(p);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int64_t hvq_scale_bytes(int width, int height, int h_samp, int v_samp)
+{
+    { int rc = scale_geometry(width, height, h_samp, v_samp); if (rc) return rc; }
+    return (int64_t)width * height + 2 * (int64_t)(width >> (h_samp == 2)) * (height >> (v_samp == 2));
+}
+
+HVQ_EXPORT int hvq_scale_body(int nx, int ny, int mx, int my)
+{
+    if (nx < 1 || ny < 1 || mx < 1 || my < 1 || nx > 8192 || ny > 8192 || mx > 8192 || my > 8192)
+        return fail(HVQ_E_ARG, "%d x %d -> %d x %d: a plane has 1 .. 8192 samples a side", nx, ny, mx, my);
+    if (nx > (int)HVQ_SC_MAX_RATIO * mx || ny > (int)HVQ_SC_MAX_RATIO * my)
+        return fail(HVQ_E_ARG, "%d x %d -> %d x %d: a reduction beyond %u is refused", nx, ny, mx, my, HVQ_SC_MAX_RATIO);
+    return (int)hvq_sc_body((uint32_t)nx, (uint32_t)ny, (uint32_t)mx, (uint32_t)my);
+}
+
+HVQ_EXPORT int hvq_scale_force_direct(HvqContext *c, int on)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = c->sc_force_direct ? 1 : 0;
+    c->sc_force_direct = on != 0;
+    return was;
+}
+
+HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                  const HvqScaleDst *dst, void *hip_stream)
+{
+    static_assert(HVQ_SCALE_DIRECT == (int)HVQ_SC_DIRECT && HVQ_SCALE_TILED == (int)HVQ_SC_TILED && HVQ_SCALE_MAX_RATIO == (int)HVQ_SC_MAX_RATIO,
+                  "the header's names are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    std::vector<HvqScaleJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    /* a call usually repeats few shapes: the geometry check (a parser's tables) and the multipliers of a plane are kept from the picture before */
+    HvqScaleDst seen{};
+    HvqScaleJob last[3];
+    memset(last, 0, sizeof last);
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const HvqScaleDst &d = dst[i];
+        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
+            int rc = scale_geometry(d.width, d.height, d.h_samp, d.v_samp);
+            if (rc) return rc;
+            seen = d;
+        }
+        int cx = d.crop_x, cy = d.crop_y, cw = d.crop_w, ch = d.crop_h;
+        if (cw == 0) {
+            if (cx || cy || ch) return fail(HVQ_E_ARG, "destination %d: crop_w == 0 means the whole picture and takes the other three as 0", i);
+            cw = s.w; ch = s.h;
+        }
+        if (cx < 0 || cy < 0 || cw <= 0 || ch <= 0 || cx > s.w - cw || cy > s.h - ch)
+            return fail(HVQ_E_ARG, "destination %d: the crop %d, %d, %d x %d is empty or leaves the %d x %d picture", i, cx, cy, cw, ch, s.w, s.h);
+        if (((cx | cw) & ((1 << s.wshift) - 1)) || ((cy | ch) & ((1 << s.hshift) - 1)))
+            return fail(HVQ_E_ARG, "destination %d: the crop %d, %d, %d x %d does not lie on the chroma samples of stream %d", i, cx, cy, cw, ch, streams[i]);
+        if (cw < 8 || ch < 8) return fail(HVQ_E_ARG, "destination %d: a cropped source of %d x %d is below 8 x 8", i, cw, ch);
+        const int dws = d.h_samp == 2, dhs = d.v_samp == 2;
+        const uint8_t *sp = a;
+        uint8_t *dp = (uint8_t *)d.ptr;
+        for (int p = 0; p < 3; ++p) {
+            const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0;
+            const uint32_t pitch = (uint32_t)(s.w >> xs);
+            const uint32_t nx = (uint32_t)(cw >> xs), ny = (uint32_t)(ch >> ys);
+            const uint32_t mx = (uint32_t)(d.width >> (p ? dws : 0)), my = (uint32_t)(d.height >> (p ? dhs : 0));
+            if (nx > HVQ_SC_MAX_RATIO * mx || ny > HVQ_SC_MAX_RATIO * my)
+                return fail(HVQ_E_ARG, "destination %d, plane %d: %u x %u -> %u x %u is a reduction beyond %u", i, p, nx, ny, mx, my, HVQ_SC_MAX_RATIO);
+            HvqScaleJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            const uint64_t from = (uint64_t)(uintptr_t)(sp + (size_t)(cy >> ys) * pitch + (size_t)(cx >> xs));
+            HvqScaleJob &l = last[p];
+            if (l.nx == nx && l.ny == ny && l.mx == mx && l.my == my && ((l.body & HVQ_SC_TILED) == 0) == (c->sc_force_direct || hvq_sc_body(nx, ny, mx, my) == HVQ_SC_DIRECT)) {
+                j = l;
+                j.src = from; j.dst = (uint64_t)(uintptr_t)dp; j.pitch = pitch;
+            } else {
+                j = l = hvq_sc_job(from, pitch, nx, ny, (uint64_t)(uintptr_t)dp, mx, my, c->sc_force_direct);
+            }
+            sp += (size_t)pitch * (size_t)(s.h >> ys);
+            dp += (size_t)mx * my;
+        }
+        max_tiles = std::max(max_tiles, jobs[(size_t)i * 3u].tiles + jobs[(size_t)i * 3u + 1u].tiles + jobs[(size_t)i * 3u + 2u].tiles);
+    }
+    if (!hvq_launch_scale) return fail(HVQ_E_NOGPU, "this build of the library has no scale kernel (hvq_scale.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqScaleJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_scale(tab, n, max_tiles, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -583,6 +583,61 @@ int  hvq_picture_hashes(HvqContext *ctx, int n, const int *streams, const int *o
 int  hvq_hash_nearest(HvqContext *ctx, const uint64_t *q, int nq, int q_stride, const uint64_t *db, int ndb, int db_stride,
                       int64_t self_offset, int threshold, int32_t *out, void *hip_stream);
 
+/* Resident pictures resampled into uint8 pictures of ANOTHER geometry in slot layout, where they lie: for `n` pictures, of any streams,
+ * sizes and samplings, in one kernel launch on the caller's HIP stream and without a host synchronisation, each picture's three planes
+ * through the area (box) filter with rational cell edges -- the construction of hvq_picture_hashes' grids -- into DEVICE memory laid
+ * out as a slot of the target geometry is.  Whatever takes "the caller's device memory in slot layout" (`src` of hvq_picture_checksums,
+ * hvq_picture_histograms, hvq_encode_jpeg, hvq_picture_hashes; `ref.ptr` of hvq_picture_metrics, hvq_picture_ssim, hvq_picture_motion)
+ * takes the result, given an open stream of the target geometry to carry it (nothing need ever be submitted to that stream).  The values
+ * are specified as exact integers: this text is the authority for them.
+ *   Planes.    Each of the three planes is resampled on its own.  The source plane is the crop's part of plane p, Ny rows x Nx samples:
+ *              for Y the crop itself, for U and V the crop's edges divided by the SOURCE sampling.  The target plane has My x Mx
+ *              samples, from the target geometry; its sampling may differ from the source's (4:4:4 -> 4:2:0, 4:2:2 -> 4:2:0 and the
+ *              reverse): chroma is simply another plane with its own N and M.
+ *   Values.    wy(r, y) = max(0, min(My (y + 1), Ny (r + 1)) - max(My y, Ny r))   0 <= r < My, 0 <= y < Ny   (sum over y = Ny)
+ *              wx(c, x) likewise with Mx, Nx
+ *              S[r][c]  = sum over y, x of wy(r, y) wx(c, x) a[y][x]              exact; S <= 255 Nx Ny < 2^34: 64 bits
+ *              D        = Nx Ny
+ *              out[r][c] = (S[r][c] + (D >> 1)) / D                               integer division: round half up, ONE rounding
+ *              Any evaluation order, separable or not, that yields these integers is allowed; no intermediate rounding is.  The
+ *              horizontal partial sums (sum over x of wx a) fit 21 bits.  32-bit cells serve a plane only when 255 Nx Ny < 2^32
+ *              (hvq_picture_hashes' threshold); beyond it a cell is 64 bits.
+ *   Known answers.  M == N is the identity.  An integer reduction k is the k x k box mean rounded half up: the 2 x 2 block {0, 0, 0, 2}
+ *              gives 1 and {0, 0, 0, 1} gives 0.  An integer enlargement replicates samples.  A flat picture stays flat at any ratio.
+ *   dst[i]:    ptr: a non-null DEVICE pointer, a multiple of 16: Y | U | V tightly packed, the target geometry's slot layout,
+ *              hvq_scale_bytes(width, height, h_samp, v_samp) bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics on the output).
+ *              width, height, h_samp, v_samp: the target geometry, one that hvq_stream_open accepts (else HVQ_E_GEOMETRY).
+ *              crop_x, crop_y, crop_w, crop_h: the source crop in luma samples; crop_w == 0 (then all four are 0): the whole picture.
+ *   hvq_scale_bytes (host only): bytes of a picture of that geometry, or HVQ_E_GEOMETRY.
+ *   hvq_scale_body (host only): the body of the kernel a plane of nx x ny samples takes on its way to mx x my: HVQ_SCALE_DIRECT (no
+ *              sample has more than 2 x 2 taps: identity and enlargement) or HVQ_SCALE_TILED (the source rows of a tile of targets go
+ *              through LDS, horizontal sums once, then the vertical pass); HVQ_E_ARG beyond the limits below.  The values do not depend
+ *              on it.  hvq_scale_force_direct(ctx, 1) makes every later call of the context take the direct body (0: the chosen one
+ *              again) and returns the setting before: for tests that compare the two with ==.
+ *   HVQ_E_ARG for the whole call: for any plane and axis N > 32 M (a reduction beyond 32 is refused rather than done badly;
+ *              enlargement is unlimited, it has at most two taps per axis); a crop that is empty or leaves the picture; a crop whose x
+ *              values are no multiples of the source h_samp or whose y values are no multiples of the source v_samp; a cropped source
+ *              narrower or lower than 8 luma samples; a null or misaligned ptr; n above 65535; a bad stream or ordinal; a src[i] with an
+ *              ordinal other than -1 or that is no multiple of 16; a NULL context.  n == 0 is HVQ_OK and does nothing.  Every
+ *              argument is checked before anything is enqueued: a refused call leaves every destination untouched.  HVQ_E_NOGPU (after
+ *              those checks) from a build without the scale kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_picture_metrics'. */
+typedef struct HvqScaleDst {
+    void   *ptr;                                  /* device, multiple of 16: Y | U | V tightly packed, the target geometry's slot layout */
+    int32_t width, height, h_samp, v_samp;        /* target geometry: one that hvq_stream_open accepts */
+    int32_t crop_x, crop_y, crop_w, crop_h;       /* source crop in luma samples; crop_w == 0 (all four 0): the whole picture */
+} HvqScaleDst;
+#define HVQ_SCALE_DIRECT 0
+#define HVQ_SCALE_TILED  1
+#define HVQ_SCALE_MAX_RATIO 32
+int     hvq_scale_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                           const HvqScaleDst *dst, void *hip_stream);
+int64_t hvq_scale_bytes(int width, int height, int h_samp, int v_samp);
+int     hvq_scale_body(int nx, int ny, int mx, int my);
+int     hvq_scale_force_direct(HvqContext *ctx, int on);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);

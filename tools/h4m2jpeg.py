@@ -2,9 +2,13 @@
 (hvq_encode_jpeg: baseline JFIF, the clip's own Y / Cb / Cr and sampling, no colour conversion, no resampling).  What crosses PCIe is the
 bitstream one way and the compressed files the other; no decoded picture is read back.
 
-    python tools/h4m2jpeg.py clip.h4m outdir [--quality Q]
+    python tools/h4m2jpeg.py clip.h4m outdir [--quality Q] [--size WxH | --fit N]
 
-writes outdir/<clip name>_<ordinal, 5 digits><frame type>.jpg.  torch is imported before the library, so both share one HIP runtime."""
+writes outdir/<clip name>_<ordinal, 5 digits><frame type>.jpg.  --size WxH (multiples of 8) and --fit N (the largest size of the clip's
+aspect inside N x N, hvqm4_amd.scale.fit) make thumbnails: the pictures are resampled where they lie (hvq_scale_pictures, the area
+filter) and the scaled pictures encoded from there (encode_jpeg(src=...)); a stream of the thumbnails' geometry that nothing is submitted
+to carries them.  Without these options the files are what they always were.  torch is imported before the library, so both share one HIP
+runtime."""
 import argparse
 import os
 import sys
@@ -19,8 +23,9 @@ def file_name(stem, k, ftype):
     return f"{stem}_{k:05d}{FRAME_TYPES.get(ftype, 'X')}.jpg"
 
 
-def clip_files(ctx, data, quality):
-    """-> (frame types, files as bytes) of one clip: its pictures decoded into a stream of their own and encoded in one call"""
+def clip_files(ctx, data, quality, size=None):
+    """-> (frame types, files as bytes) of one clip: its pictures decoded into a stream of their own and encoded in one call; size =
+    (w, h): scaled to that size first, on the device"""
     from hvqm4_amd import jpeg
     from hvqm4_amd.container import parse_header, video_pictures
     hdr = parse_header(data)
@@ -30,10 +35,40 @@ def clip_files(ctx, data, quality):
     for ft, p in pics:
         ctx.submit(sid, ft, p)
     ctx.flush()
-    buffers, lengths = ctx.encode_jpeg([sid] * n, list(range(n)), quality=quality)
-    files = jpeg.files(buffers, lengths)
+    if size is None:
+        buffers, lengths = ctx.encode_jpeg([sid] * n, list(range(n)), quality=quality)
+        files = jpeg.files(buffers, lengths)
+    else:
+        scaled = ctx.scale_pictures([sid] * n, list(range(n)), size)
+        carrier = ctx.open_stream(size[0], size[1], hdr.h_samp, hdr.v_samp, hdr.is15, 3)       # never submitted to: it names the geometry of src=
+        buffers, lengths = ctx.encode_jpeg([carrier] * n, [-1] * n, quality=quality, src=[scaled[i] for i in range(n)])
+        files = jpeg.files(buffers, lengths)
+        ctx.close_stream(carrier)
     ctx.close_stream(sid)
     return [ft for ft, _p in pics], files
+
+
+def target_size(data, size, fit, error):
+    """(w, h) of the thumbnails, or None without --size / --fit; error(message) on what the library would refuse"""
+    from hvqm4_amd import scale
+    from hvqm4_amd.container import parse_header
+    if not size and fit is None:
+        return None
+    hdr = parse_header(data)
+    if size:
+        try:
+            w, h = (int(v) for v in size.lower().split("x"))
+        except ValueError:
+            error("--size takes WxH")
+    else:
+        if fit < 8:
+            error("--fit takes 8 at least")
+        w, h = scale.fit(hdr.width, hdr.height, fit, fit)
+    try:
+        scale.plane_sizes((hdr.width, hdr.height, hdr.h_samp, hdr.v_samp), (w, h, hdr.h_samp, hdr.v_samp))
+    except ValueError as e:
+        error(str(e))
+    return w, h
 
 
 def main():
@@ -41,16 +76,22 @@ def main():
     ap.add_argument("clip", help="an .h4m file")
     ap.add_argument("outdir")
     ap.add_argument("--quality", type=int, default=90, help="1 .. 100, scaled as the IJG library does")
+    ap.add_argument("--size", default=None, metavar="WxH", help="thumbnails of this size (multiples of 8)")
+    ap.add_argument("--fit", type=int, default=None, metavar="N", help="thumbnails of the clip's aspect inside N x N")
     args = ap.parse_args()
     if not 1 <= args.quality <= 100:
         ap.error("--quality takes 1 .. 100")
+    if args.size and args.fit:
+        ap.error("--size and --fit exclude each other")
+    data = open(args.clip, "rb").read()
+    size = target_size(data, args.size, args.fit, ap.error)
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
     os.makedirs(args.outdir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(args.clip))[0]
     ctx = batch.Context(0)
-    types, files = clip_files(ctx, open(args.clip, "rb").read(), args.quality)
+    types, files = clip_files(ctx, data, args.quality, size)
     ctx.close()
     for k, (ft, f) in enumerate(zip(types, files)):
         with open(os.path.join(args.outdir, file_name(stem, k, ft)), "wb") as out:
