@@ -68,6 +68,18 @@ class HvqScaleDst(C.Structure):                 # include/hvqm4_amd.h: a destina
     _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "crop_x", "crop_y", "crop_w", "crop_h")]
 
 
+class HvqFilterTerm(C.Structure):               # include/hvqm4_amd.h: one separable kernel of a plane's filter
+    _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("wx", C.c_int16 * 31), ("wy", C.c_int16 * 31)]
+
+
+class HvqPlaneFilter(C.Structure):
+    _fields_ = [("terms", C.c_int32), ("combine", C.c_int32), ("shift", C.c_int32), ("bias", C.c_int32), ("term", HvqFilterTerm * 2)]
+
+
+class HvqFilter(C.Structure):                   # a filter of hvq_filter_pictures: luma for Y, chroma for U and V
+    _fields_ = [("luma", HvqPlaneFilter), ("chroma", HvqPlaneFilter)]
+
+
 # every symbol include/hvqm4.h and include/hvqm4_amd.h declare: (restype, argtypes)
 SYMBOLS = {
     "HVQM4InitDecoder": (None, []),
@@ -144,6 +156,10 @@ SYMBOLS = {
     "hvq_scale_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hvq_scale_body": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hvq_scale_force_direct": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_filter_check": (C.c_int, [C.c_void_p]),
+    "hvq_filter_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "hvq_filter_force_filter": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

@@ -663,6 +663,91 @@ class Context:
         check(lib().hvq_scale_pictures(self._h, n, a_s, a_o, a_p, C.c_void_p(a_d.ctypes.data), C.c_void_p(stream)))
         return out
 
+    def filter_force_filter(self, on: bool) -> bool:
+        """hvq_filter_force_filter: every later filter_pictures of this context runs identity planes through the filter body of the
+        kernel instead of the copy body (False: the chosen one again) -> the setting before.  The values do not depend on it: for
+        tests that compare the two with =="""
+        return bool(check(lib().hvq_filter_force_filter(self._h, int(bool(on)))))
+
+    def filter_pictures(self, sids, ordinals, filt, src=None, out=None):
+        """hvq_filter_pictures: resident pictures (sids[i], ordinals[i]) through separable integer filters (exact integers, one
+        rounding: include/hvqm4_amd.h) into uint8 pictures of their own geometry IN SLOT LAYOUT (Y | U | V), on torch's current
+        stream, without a host synchronisation and without moving a picture.  `filt`: one hvqm4_amd.filters.Filter, or a list of one
+        per picture (equal ones share an entry of the call's table; more than 64 distinct ones: ValueError).  -> when every geometry is
+        the same one uint8 CUDA tensor [n, bytes], otherwise a list of n 1-D uint8 CUDA tensors (`out`, if given: of that same form,
+        contiguous, rows 16-byte aligned; it is overwritten whole and must not overlap a source).  Whatever takes src= or ref.ptr
+        takes a row of the result.  hvqm4_amd.filters builds the filters and gives the expected bytes (of_picture).  `src` as in
+        picture_checksums.  Ordering and slot safety are export()'s."""
+        import torch
+        from . import filters as fl
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        if n > 65535:
+            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        for s in set(sids):
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        if isinstance(filt, fl.Filter):
+            table, which = [filt], None
+        else:
+            if not isinstance(filt, (list, tuple)) or len(filt) != n:
+                raise ValueError(f"filt: one filters.Filter, or a list of {n}")
+            index, table, which = {}, [], []
+            for f in filt:
+                if not isinstance(f, fl.Filter):
+                    raise ValueError(f"filt: an entry is a filters.Filter, not {type(f).__name__}")
+                if f not in index:
+                    index[f] = len(table)
+                    table.append(f)
+                which.append(index[f])
+            if len(table) > fl.MAX_FILTERS:
+                raise ValueError(f"{len(table)} distinct filters: one call takes {fl.MAX_FILTERS} at the most")
+        for f in table:
+            fl.check(f)                                                    # ValueError beyond the library's limits
+        streams = set(sids)
+        pb = {s: self.pic_bytes(s) for s in streams}                       # a call usually repeats few streams: each is looked at once
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        nb = [pb[s] for s in sids]
+        uniform = len({self._geometry(s) for s in streams}) <= 1
+        if out is None:
+            out = torch.empty((n, nb[0] if n else 0), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
+        if uniform:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0] if n else 0) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0] if n else 0})")
+            device = out.device
+            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0] if n else 0) + np.uint64(out.data_ptr())     # rows of a multiple of 16 bytes
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors (the geometries differ)")
+            for i, t in enumerate(out):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
+            device = out[0].device
+            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
+            if len({t.get_device() for t in out}) > 1:
+                raise ValueError("out: the tensors lie on different devices")
+        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
+            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
+            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
+        if device.type != "cuda":
+            raise ValueError(f"out is on {device}, not a GPU")
+        if not n:
+            return out
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        from ._lib import HvqFilter
+        a_f = (HvqFilter * len(table))(*[f.to_struct() for f in table])
+        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, a_p, C.cast(a_f, C.c_void_p), len(table), a_w, a_d, C.c_void_p(stream)))
+        return out
+
     def _ssim_dims(self, sid):
         """((rows, cols) of the SSIM windows of Y, U, V) of a stream: hvq_ssim_windows on its geometry"""
         from .metrics import ssim_windows

@@ -535,4 +535,53 @@ _Static_assert(sizeof(HvqScaleJob) == 80, "HvqScaleJob must be 80 bytes");
 #endif
 
 
+/* one plane of one picture of the filter launch (hvq_filter.hip, hvq_filter_pictures): three jobs a picture, Y, U, V.  `src` and `dst`
+ * are planes of ny rows of nx samples, dense (pitch nx: a multiple of 4, as both addresses are).  `pf` names the plane's record in the
+ * table of HvqFilterPlaneDev that lies behind the job table in the same upload: 2 * filter for Y, 2 * filter + 1 for U and V.  Grid row
+ * = picture, its three jobs one behind the other; a workgroup of HVQ_FL_LANES lanes takes a tile of one plane -- HVQ_FL_TW x HVQ_FL_TH
+ * samples in the filter body, HVQ_FL_CTW x HVQ_FL_CTH in the copy body (a plane whose filter is the identity): tiles_x tiles side by
+ * side, `tiles` in all; the workgroups of a grid row walk the tiles of Y, then U, then V, those past them leave.  Every member is a
+ * dword or a qword (scalar loads); 48 bytes. */
+#define HVQ_FL_LANES  256u
+#define HVQ_FL_TW     64u           /* samples a tile of the filter body is wide: 16 dwords, one store a lane */
+#define HVQ_FL_TH     16u           /* its rows */
+#define HVQ_FL_CTW    256u          /* the copy body's tile: a wave moves 256 adjacent bytes of a row, a lane four rows 4 apart */
+#define HVQ_FL_CTH    16u
+#define HVQ_FL_MAX_R  15u           /* the largest radius: HVQ_FLT_MAX_RADIUS */
+#define HVQ_FL_HALO   16u           /* bytes staged left and right of a tile's 64: the radius rounded up to whole dwords */
+#define HVQ_FL_ROW_DWORDS ((HVQ_FL_TW + 2u * HVQ_FL_HALO) / 4u)   /* 24 */
+#define HVQ_FL_MAX_ROWS (HVQ_FL_TH + 2u * HVQ_FL_MAX_R)          /* 46 staged rows at the most */
+#define HVQ_FL_FILTER 0u
+#define HVQ_FL_COPY   1u
+typedef struct HvqFilterJob {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint32_t nx, ny;                   /* samples of the plane: nx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t pf;                       /* index of the plane's HvqFilterPlaneDev */
+    uint32_t body;                     /* HVQ_FL_FILTER or HVQ_FL_COPY */
+    uint32_t pad[2];
+} HvqFilterJob;
+
+/* a plane's filter as the kernel reads it: include/hvqm4_amd.h's HvqPlaneFilter with the taps widened to dwords, so that a tap is one
+ * scalar load.  Taps past 2 r + 1 are 0.  rmax = max(ry) over the terms: the rows staged above and below a tile. */
+typedef struct HvqFilterTermDev { int32_t rx, ry; int32_t wx[32], wy[32]; } HvqFilterTermDev;
+typedef struct HvqFilterPlaneDev {
+    int32_t terms, combine, shift, bias;
+    int32_t half, rmax, pad[2];        /* half = shift ? 1 << (shift - 1) : 0 */
+    HvqFilterTermDev term[2];
+} HvqFilterPlaneDev;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqFilterJob) == 48 && sizeof(HvqFilterJob) % 16 == 0, "HvqFilterJob must be 48 bytes: job tables are uploaded in 16-byte units");
+static_assert(sizeof(HvqFilterTermDev) == 264 && sizeof(HvqFilterPlaneDev) == 560 && sizeof(HvqFilterPlaneDev) % 16 == 0, "the filter table is uploaded in 16-byte units");
+static_assert(HVQ_FL_TW * HVQ_FL_TH == HVQ_FL_LANES * 4u, "a lane stores one dword of the tile");
+static_assert(HVQ_FL_CTW == 64u * 4u && HVQ_FL_CTH * 64u == HVQ_FL_LANES * 4u, "the copy body: 64 lanes side by side, four waves, four rows a lane");
+static_assert(HVQ_FL_HALO >= HVQ_FL_MAX_R && HVQ_FL_HALO % 4u == 0 && HVQ_FL_TW % 4u == 0, "the staged row: whole dwords that hold the halo");
+static_assert(HVQ_FL_MAX_ROWS * HVQ_FL_ROW_DWORDS <= 5u * HVQ_FL_LANES, "a lane stages five dwords at the most");
+#else
+_Static_assert(sizeof(HvqFilterJob) == 48, "HvqFilterJob must be 48 bytes");
+#endif
+
+
 #endif

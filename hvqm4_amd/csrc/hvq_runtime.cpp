@@ -42,6 +42,7 @@
 #include "hvq_jpeg.h"
 #include "hvq_phash.h"
 #include "hvq_scale.h"
+#include "hvq_filter.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -89,6 +90,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_hash_nearest(const uint64
 
 /* hvq_scale.hip.  Weak for the same reason: hvq_scale_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_filter.hip.  Weak for the same reason: hvq_filter_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -375,6 +378,7 @@ struct HvqContext {
      * serves every launch pair and every call, as ck_acc */
     uint8_t *ph_acc = nullptr;
     size_t ph_cap = 0;
+    bool fl_force_filter = false;      /* hvq_filter_force_filter: identity planes take the filter body of hvq_filter.hip, not the copy body */
     bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
@@ -3100,6 +3104,125 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
     if (!hvq_launch_scale) return fail(HVQ_E_NOGPU, "this build of the library has no scale kernel (hvq_scale.hip is not linked)");
     return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqScaleJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_scale(tab, n, max_tiles, st); });
+}
+
+/* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): an eleventh member of the export chain,
+ * hvq_scale_pictures' lookup, refusals and ordering.  Three jobs a picture, one per plane, and behind them the table of the planes'
+ * filters with the taps widened to dwords; one launch behind that upload on the caller's stream (export_enqueue).  Nothing but the
+ * destinations is written: no scratch memory, no memset. */
+static int filter_plane_check(const HvqPlaneFilter &p, const char *plane)
+{
+    if (p.terms != 1 && p.terms != 2) return fail(HVQ_E_ARG, "%s filter: %d terms (1 or 2)", plane, p.terms);
+    if (p.combine != HVQ_FLT_SUM && p.combine != HVQ_FLT_ABS_SUM && p.combine != HVQ_FLT_SUM_ABS) return fail(HVQ_E_ARG, "%s filter: combine %d", plane, p.combine);
+    if (p.shift < 0 || p.shift > HVQ_FLT_MAX_SHIFT) return fail(HVQ_E_ARG, "%s filter: shift %d outside 0 .. %d", plane, p.shift, HVQ_FLT_MAX_SHIFT);
+    if (p.bias < -255 || p.bias > 255) return fail(HVQ_E_ARG, "%s filter: bias %d outside -255 .. 255", plane, p.bias);
+    int64_t gain = 0;
+    for (int t = 0; t < p.terms; ++t) {
+        const HvqFilterTerm &T = p.term[t];
+        if (T.rx < 0 || T.rx > HVQ_FLT_MAX_RADIUS || T.ry < 0 || T.ry > HVQ_FLT_MAX_RADIUS)
+            return fail(HVQ_E_ARG, "%s filter, term %d: radii %d, %d outside 0 .. %d", plane, t, T.rx, T.ry, HVQ_FLT_MAX_RADIUS);
+        int64_t ax = 0, ay = 0;
+        for (int i = 0; i < HVQ_FLT_MAX_TAPS; ++i) {
+            if (i > 2 * T.rx && T.wx[i]) return fail(HVQ_E_ARG, "%s filter, term %d: wx[%d] = %d lies beyond the %d taps of radius %d", plane, t, i, T.wx[i], 2 * T.rx + 1, T.rx);
+            if (i > 2 * T.ry && T.wy[i]) return fail(HVQ_E_ARG, "%s filter, term %d: wy[%d] = %d lies beyond the %d taps of radius %d", plane, t, i, T.wy[i], 2 * T.ry + 1, T.ry);
+            ax += T.wx[i] < 0 ? -(int64_t)T.wx[i] : T.wx[i];
+            ay += T.wy[i] < 0 ? -(int64_t)T.wy[i] : T.wy[i];
+        }
+        gain += ax * ay;
+    }
+    if (gain < 1 || gain > HVQ_FLT_MAX_GAIN) return fail(HVQ_E_ARG, "%s filter: a gain of %lld (1 .. %d)", plane, (long long)gain, HVQ_FLT_MAX_GAIN);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_filter_check(const HvqFilter *f)
+{
+    if (!f) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = filter_plane_check(f->luma, "luma"); if (rc) return rc; }
+    return filter_plane_check(f->chroma, "chroma");
+}
+
+/* a checked plane filter as the kernel reads it */
+static HvqFilterPlaneDev filter_plane_dev(const HvqPlaneFilter &p)
+{
+    HvqFilterPlaneDev d;
+    memset(&d, 0, sizeof d);
+    d.terms = p.terms; d.combine = p.combine; d.shift = p.shift; d.bias = p.bias;
+    d.half = p.shift ? 1 << (p.shift - 1) : 0;
+    for (int t = 0; t < p.terms; ++t) {
+        d.term[t].rx = p.term[t].rx; d.term[t].ry = p.term[t].ry;
+        d.rmax = std::max(d.rmax, p.term[t].ry);
+        for (int i = 0; i < HVQ_FLT_MAX_TAPS; ++i) { d.term[t].wx[i] = p.term[t].wx[i]; d.term[t].wy[i] = p.term[t].wy[i]; }
+    }
+    return d;
+}
+
+HVQ_EXPORT int hvq_filter_force_filter(HvqContext *c, int on)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = c->fl_force_filter ? 1 : 0;
+    c->fl_force_filter = on != 0;
+    return was;
+}
+
+HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                   const HvqFilter *filters, int nfilters, const int *which, void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_FLT_MAX_RADIUS == (int)HVQ_FL_MAX_R && HVQ_FLT_MAX_TAPS == 2 * HVQ_FLT_MAX_RADIUS + 1 && HVQ_FLT_MAX_TAPS <= 32,
+                  "the header's limits are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !filters))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    if (nfilters < 1 || nfilters > HVQ_FLT_MAX_FILTERS) return fail(HVQ_E_ARG, "%d filters: one call takes 1 .. %d", nfilters, HVQ_FLT_MAX_FILTERS);
+    for (int f = 0; f < nfilters; ++f) { int rc = hvq_filter_check(filters + f); if (rc) return rc; }
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    const size_t job_bytes = (size_t)n * 3u * sizeof(HvqFilterJob), tab_bytes = (size_t)nfilters * 2u * sizeof(HvqFilterPlaneDev);
+    std::vector<uint8_t> up(job_bytes + tab_bytes);
+    HvqFilterJob *jobs = (HvqFilterJob *)up.data();
+    HvqFilterPlaneDev *tab = (HvqFilterPlaneDev *)(up.data() + job_bytes);
+    std::vector<int> copy((size_t)nfilters * 2u);
+    for (int f = 0; f < nfilters; ++f) {
+        tab[2 * f] = filter_plane_dev(filters[f].luma);
+        tab[2 * f + 1] = filter_plane_dev(filters[f].chroma);
+        for (int p = 0; p < 2; ++p) copy[(size_t)(2 * f + p)] = !c->fl_force_filter && hvq_fl_is_identity(&tab[2 * f + p]);
+    }
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        const int f = which ? which[i] : 0;
+        if (f < 0 || f >= nfilters) return fail(HVQ_E_ARG, "picture %d: filter %d of %d", i, f, nfilters);
+        const uint8_t *sp = a;
+        uint8_t *dp = (uint8_t *)dst[i];
+        uint32_t tiles = 0;
+        for (int p = 0; p < 3; ++p) {
+            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+            const uint32_t pf = (uint32_t)(2 * f + (p ? 1 : 0));
+            HvqFilterJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_fl_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, pf, copy[pf]);
+            tiles += j.tiles;
+            sp += (size_t)nx * ny;
+            dp += (size_t)nx * ny;
+        }
+        max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!hvq_launch_filter) return fail(HVQ_E_NOGPU, "this build of the library has no filter kernel (hvq_filter.hip is not linked)");
+    return export_enqueue(c, up.data(), up.size(), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_filter(t, n, max_tiles, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -638,6 +638,61 @@ int64_t hvq_scale_bytes(int width, int height, int h_samp, int v_samp);
 int     hvq_scale_body(int nx, int ny, int mx, int my);
 int     hvq_scale_force_direct(HvqContext *ctx, int on);
 
+/* Resident pictures FILTERED into uint8 pictures of THEIR OWN geometry in slot layout, where they lie: for `n` pictures, of any streams,
+ * sizes and samplings, in one kernel launch on the caller's HIP stream and without a host synchronisation, each plane through a sum of
+ * up to two separable integer kernels with one rounding.  Gaussian and binomial blur, Sobel / Scharr gradients and their magnitude,
+ * the Laplacian, a difference of Gaussians and unsharp masking are parameter sets of it (hvqm4_amd.filters builds them).  The result
+ * composes like hvq_scale_pictures': whatever takes `src` or `ref.ptr` takes it.  The values are specified as exact integers: this
+ * text is the authority for them.
+ *   Planes.    Y is filtered with filter.luma, U and V with filter.chroma, each at its own resolution: Ny rows x Nx samples a.
+ *   Values.    cx(v) = min(max(v, 0), Nx - 1), cy likewise: the border replicates the edge sample.  For term t of the plane's filter
+ *              T_t[y][x] = sum over j in [0, 2 ry_t], i in [0, 2 rx_t] of wy_t[j] wx_t[i] a[cy(y + j - ry_t)][cx(x + i - rx_t)]
+ *              -- correlation: tap i meets the sample i - rx to the right, nothing is flipped.  With terms == 1, T_1 = 0.
+ *              S   = T_0 + T_1 (HVQ_FLT_SUM), |T_0 + T_1| (HVQ_FLT_ABS_SUM) or |T_0| + |T_1| (HVQ_FLT_SUM_ABS)
+ *              h   = shift ? 1 << (shift - 1) : 0
+ *              out = min(255, max(0, floor((S + h) / 2^shift) + bias))
+ *              The floor is towards minus infinity (an arithmetic shift): ONE rounding, half up, for negative sums too: S = -1,
+ *              shift = 1 gives 0 and S = -3, shift = 1 gives -1.  Any evaluation order that yields these integers is allowed; no
+ *              intermediate rounding is.  With gain = sum over t of (sum |wx_t|) (sum |wy_t|) <= HVQ_FLT_MAX_GAIN = 2^22, every
+ *              partial sum and |S| + h stay below 255 * 2^22 + 2^21 < 2^31: 32-bit signed arithmetic serves everywhere.
+ *   Known answers.  The identity (terms 1, radii 0, weights {1}, shift 0, bias 0) copies the plane.  wx = {1, 0, 0} with rx = 1 (wy =
+ *              {1}) gives out[x] = a[max(x - 1, 0)]: orientation and border.  A flat plane stays flat whenever the weights sum to
+ *              2^shift.  {1, 2, 1} x {1, 2, 1}, shift 4, on the 3 x 3 plane that is 0 but for a 16 in the middle gives {1, 2, 1; 2, 4, 2;
+ *              1, 2, 1}.  Sobel-x ({-1, 0, 1} x {1, 2, 1}) with bias 128 on a flat plane gives 128.  The two negative ties above.
+ *   hvq_filter_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL filter or, in either plane: terms other than 1 or 2; a radius outside
+ *              0 .. HVQ_FLT_MAX_RADIUS; a tap beyond the first 2 r + 1 that is not 0 (of a term in use); combine outside the three
+ *              values; shift outside 0 .. HVQ_FLT_MAX_SHIFT; bias outside -255 .. 255; a gain of 0 or above HVQ_FLT_MAX_GAIN.
+ *              A term that is not in use (term[1] with terms == 1) is not looked at.
+ *   The call.  Output i has the geometry of its source, in slot layout (Y | U | V tightly packed): dst[i] is a non-null DEVICE pointer,
+ *              a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  dst[i] must not overlap any source of the call: the
+ *              caller's business, not checked.  which[i] selects filters[which[i]]; which == NULL: filters[0] for all.  nfilters is
+ *              1 .. HVQ_FLT_MAX_FILTERS; every filter of the table is checked, used or not.
+ *              hvq_filter_force_filter(ctx, 1) makes every later call of the context run identity planes through the filter body
+ *              instead of the copy body (0: the chosen one again) and returns the setting before: for tests that compare the two with ==.
+ *   HVQ_E_ARG for the whole call: what hvq_filter_check refuses; nfilters outside 1 .. 64; a which[i] outside 0 .. nfilters - 1; a null
+ *              or misaligned dst[i]; n above 65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no
+ *              multiple of 16; a NULL context, filters or dst.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before
+ *              anything is enqueued: a refused call leaves every destination untouched.  HVQ_E_NOGPU (after those checks) from a build
+ *              without the filter kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_scale_pictures'. */
+#define HVQ_FLT_MAX_RADIUS 15
+#define HVQ_FLT_MAX_TAPS   31            /* 2 * radius + 1 */
+#define HVQ_FLT_MAX_SHIFT  22
+#define HVQ_FLT_MAX_GAIN   (1 << 22)
+#define HVQ_FLT_MAX_FILTERS 64
+#define HVQ_FLT_SUM      0               /* S = T0 + T1          */
+#define HVQ_FLT_ABS_SUM  1               /* S = |T0 + T1|        */
+#define HVQ_FLT_SUM_ABS  2               /* S = |T0| + |T1|      */
+typedef struct HvqFilterTerm  { int32_t rx, ry; int16_t wx[HVQ_FLT_MAX_TAPS], wy[HVQ_FLT_MAX_TAPS]; } HvqFilterTerm;
+typedef struct HvqPlaneFilter { int32_t terms, combine, shift, bias; HvqFilterTerm term[2]; } HvqPlaneFilter;
+typedef struct HvqFilter      { HvqPlaneFilter luma, chroma; } HvqFilter;   /* chroma serves U and V, at their own resolution */
+int     hvq_filter_check(const HvqFilter *f);
+int     hvq_filter_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                            const HvqFilter *filters, int nfilters, const int *which, void *const *dst, void *hip_stream);
+int     hvq_filter_force_filter(HvqContext *ctx, int on);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
