@@ -80,6 +80,14 @@ class HvqFilter(C.Structure):                   # a filter of hvq_filter_picture
     _fields_ = [("luma", HvqPlaneFilter), ("chroma", HvqPlaneFilter)]
 
 
+class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
+    _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
+
+
+class HvqWarpDst(C.Structure):                  # a destination of hvq_warp_pictures: HvqScaleDst without the crop
+    _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp")]
+
+
 # every symbol include/hvqm4.h and include/hvqm4_amd.h declare: (restype, argtypes)
 SYMBOLS = {
     "HVQM4InitDecoder": (None, []),
@@ -160,6 +168,10 @@ SYMBOLS = {
     "hvq_filter_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "hvq_filter_force_filter": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_warp_check": (C.c_int, [C.c_void_p]),
+    "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
+    "hvq_warp_force_direct": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

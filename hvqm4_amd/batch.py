@@ -7,11 +7,15 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import HVQ_E_ARG, HvqError, HvqScaleDst, HvqStats, check, lib
+from ._lib import HVQ_E_ARG, HvqError, HvqScaleDst, HvqStats, HvqWarp, HvqWarpDst, check, lib
 
 # HvqScaleDst as a numpy record: a pointer and eight int32 (width, height, h_samp, v_samp, crop_x, crop_y, crop_w, crop_h)
 _SCALE_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (8,))])
 assert _SCALE_DST.itemsize == C.sizeof(HvqScaleDst)
+# HvqWarp (six coefficients and the border; fill[3] and pad) and HvqWarpDst (a pointer; width, height, h_samp, v_samp) likewise
+_WARP = np.dtype([("m", np.int32, (7,)), ("fill", np.uint8, (4,))])
+_WARP_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (4,))])
+assert _WARP.itemsize == C.sizeof(HvqWarp) == 32 and _WARP_DST.itemsize == C.sizeof(HvqWarpDst) == 24
 
 
 class Context:
@@ -746,6 +750,105 @@ class Context:
         a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
         a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
         check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, a_p, C.cast(a_f, C.c_void_p), len(table), a_w, a_d, C.c_void_p(stream)))
+        return out
+
+    def warp_force_direct(self, on) -> int:
+        """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen
+        one again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) -> the setting before.  The
+        values do not depend on it: for tests that compare the bodies with =="""
+        return check(lib().hvq_warp_force_direct(self._h, int(on)))
+
+    def warp_pictures(self, sids, ordinals, warp, size=None, sampling=None, src=None, out=None):
+        """hvq_warp_pictures: resident pictures (sids[i], ordinals[i]) through a per-picture affine map with bilinear taps (exact
+        integers, one rounding: include/hvqm4_amd.h) into uint8 pictures of a target geometry IN SLOT LAYOUT (Y | U | V), on torch's
+        current stream, without a host synchronisation and without moving a picture.  `warp`: one hvqm4_amd.warp.Warp, or a list of
+        one per picture; `size`: None (the source's), (w, h), or one per picture (None entries: the source's); `sampling`: likewise
+        with (h_samp, v_samp).  -> when every target geometry is the same one uint8 CUDA tensor [n, bytes], otherwise a list of n 1-D
+        uint8 CUDA tensors (`out`, if given: of that same form, contiguous, rows 16-byte aligned; it is overwritten whole and must
+        not overlap a source).  Whatever takes src= or ref.ptr takes a row of the result, with an open stream of the target geometry
+        to carry it.  hvqm4_amd.warp builds the maps and gives the expected bytes (of_picture).  `src` as in picture_checksums.
+        Ordering and slot safety are export()'s."""
+        import torch
+        from . import scale as sc
+        from . import warp as wp
+        from .checksums import sources
+        from .export import check_one_hip_runtime
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        if n > 65535:
+            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        streams = set(sids)
+        for s in streams:
+            if s not in self._geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        if isinstance(warp, wp.Warp):
+            warps = None                                                   # one map for all: one row, broadcast
+            wp.check(warp)
+        else:
+            if not isinstance(warp, (list, tuple)) or len(warp) != n:
+                raise ValueError(f"warp: one warp.Warp, or a list of {n}")
+            warps = list(warp)
+            for w in {id(w): w for w in warps}.values():
+                wp.check(w)                                                # ValueError beyond the library's limits
+        sizes, one_size = sc.per_picture(size, n, 2, "size")
+        samplings, one_sampling = sc.per_picture(sampling, n, 2, "sampling")
+        geoms = {s: self._geometry(s) for s in streams}
+        shapes = {}                                                        # a call usually repeats few shapes: each is looked at once
+        if n and one_size and one_sampling and len(set(geoms.values())) == 1:
+            keys = [(geoms[sids[0]], sizes[0], samplings[0])] * n
+            distinct = keys[:1]
+        else:
+            keys = [(geoms[s], sz, sm) for s, sz, sm in zip(sids, sizes, samplings)]
+            distinct = set(keys)
+        for key in distinct:
+            g, sz, sm = key
+            dst = (sz or g[:2]) + (sm or g[2:])
+            if dst[2:] not in sc.SAMPLINGS:
+                raise ValueError(f"sampling {dst[2:]}: one of {sc.SAMPLINGS}")
+            if dst[0] < 8 or dst[1] < 8 or dst[0] % 8 or dst[1] % 8 or dst[0] > 8192 or dst[1] > 8192:
+                raise ValueError(f"target {dst[0]}x{dst[1]}: multiples of 8 up to 8192")
+            shapes[key] = (dst, sc.nbytes(*dst))
+        pb = {s: self.pic_bytes(s) for s in streams}
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        uniform = len({v[0] for v in shapes.values()}) <= 1
+        nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
+        if out is None:
+            out = torch.empty((n, nb[0] if n else 0), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
+        if uniform:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0] if n else 0) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0] if n else 0})")
+            device = out.device
+            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0] if n else 0) + np.uint64(out.data_ptr())     # rows of a multiple of 16 bytes
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors (the target geometries differ)")
+            for i, t in enumerate(out):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
+            device = out[0].device
+            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
+            if len({t.get_device() for t in out}) > 1:
+                raise ValueError("out: the tensors lie on different devices")
+        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
+            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
+            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
+        if device.type != "cuda":
+            raise ValueError(f"out is on {device}, not a GPU")
+        if not n:
+            return out
+        check_one_hip_runtime()
+        stream = torch.cuda.current_stream(device).cuda_stream
+        a_s = (C.c_int * n)(*sids)
+        a_o = (C.c_int * n)(*ordinals)
+        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_w = np.empty(n, dtype=_WARP)                                       # HvqWarp[n]
+        a_w["m"] = warp.coefficients() + (warp.border,) if warps is None else [w.coefficients() + (w.border,) for w in warps]
+        a_w["fill"] = warp.fill + (0,) if warps is None else [w.fill + (0,) for w in warps]
+        a_d = np.empty(n, dtype=_WARP_DST)                                   # HvqWarpDst[n]
+        a_d["ptr"] = where
+        a_d["rest"] = shapes[keys[0]][0] if len(shapes) == 1 else [shapes[k][0] for k in keys]
+        check(lib().hvq_warp_pictures(self._h, n, a_s, a_o, a_p, C.c_void_p(a_w.ctypes.data), C.c_void_p(a_d.ctypes.data), C.c_void_p(stream)))
         return out
 
     def _ssim_dims(self, sid):

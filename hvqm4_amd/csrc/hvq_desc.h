@@ -584,4 +584,47 @@ _Static_assert(sizeof(HvqFilterJob) == 48, "HvqFilterJob must be 48 bytes");
 #endif
 
 
+/* one plane of one picture of the warp launch (hvq_warp.hip, hvq_warp_pictures): three jobs a picture, Y, U, V.  `src` is the source
+ * plane, ny rows of nx samples, `dst` the target plane, my rows of mx samples, both dense (pitches nx and mx: multiples of 4, as both
+ * addresses are).  The plane's inverse map in the units of include/hvqm4_amd.h: NU(x, y) = cu + au x + bu y and NV(x, y) = cv + av x +
+ * bv y (au = 2 m00 hx', bu = 2 m01 vy', cu = m00 hx' + m01 vy' + 2 t0 - 65536 hx, ...), U8 = (NU + (1 << (su - 1))) >> su with su = 8 + hx,
+ * sv = 8 + vy.  Grid row = picture, its three jobs one behind the other; a workgroup of HVQ_WP_LANES lanes takes a tile of HVQ_WP_TW x
+ * HVQ_WP_TH targets of one plane: tiles_x tiles side by side, `tiles` in all; the workgroups of a grid row walk the tiles of Y, then U,
+ * then V, those past them leave.  body HVQ_WP_DIRECT: a lane gathers its taps from global memory.  body HVQ_WP_TILED: the source
+ * bounding box of the tile (hvq_warp.h), clamped into the plane, is staged into LDS as aligned dwords, `pitch` dwords a row (odd: lanes
+ * that walk down a column of the box meet different banks) and at most `rows` rows, pitch * rows <= HVQ_WP_LDS_DWORDS; staged dword
+ * idx is row idx / pitch = idx * pitch_mul >> 32.  Every member is a dword or a qword (scalar loads); 112 bytes. */
+#define HVQ_WP_LANES  256u
+#define HVQ_WP_TW     64u           /* targets a tile is wide: 16 dwords, one store a lane */
+#define HVQ_WP_TH     16u           /* its rows: a lane computes four, 4 g .. 4 g + 3 for wave g */
+#define HVQ_WP_LDS_DWORDS 4096u     /* LDS of the staged box: 16 KiB, beside 1 KiB for the tile's bytes */
+#define HVQ_WP_DIRECT 0u
+#define HVQ_WP_TILED  1u
+#define HVQ_WP_MAX_M  (32 * 65536)  /* HVQ_WARP_MAX_SCALE */
+typedef struct HvqWarpJob {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    int64_t  cu, cv;                   /* NU, NV of target sample (0, 0) */
+    int32_t  au, bu, av, bv;           /* NU, NV from one target column / row to the next: |.| <= 2^23 */
+    uint32_t nx, ny;                   /* source samples: nx a multiple of 4 */
+    uint32_t mx, my;                   /* target samples: mx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t body;                     /* HVQ_WP_DIRECT or HVQ_WP_TILED */
+    uint32_t su, sv;                   /* 9 or 10 */
+    uint32_t border, fill;             /* HVQ_WARP_REPLICATE / HVQ_WARP_CONSTANT; the plane's fill value */
+    uint32_t pitch, rows;              /* the tiled body's */
+    uint32_t pitch_mul;                /* floor(2^32 / pitch) + 1 */
+    uint32_t pad[2];
+} HvqWarpJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqWarpJob) == 112 && sizeof(HvqWarpJob) % 16 == 0, "HvqWarpJob must be 112 bytes: job tables are uploaded in 16-byte units");
+static_assert(HVQ_WP_TW * HVQ_WP_TH == HVQ_WP_LANES * 4u && HVQ_WP_TW == 64u, "a lane stores one dword of the tile; a wave is a row of targets");
+/* the deltas of NU inside a tile stay in 32 bits: 2 * 2 * HVQ_WP_MAX_M * (63 + 15) < 2^31 */
+static_assert((int64_t)4 * HVQ_WP_MAX_M * (HVQ_WP_TW - 1u + HVQ_WP_TH - 1u) < ((int64_t)1 << 31), "a lane adds a 32-bit delta to the tile's origin");
+#else
+_Static_assert(sizeof(HvqWarpJob) == 112, "HvqWarpJob must be 112 bytes");
+#endif
+
+
 #endif

@@ -43,6 +43,7 @@
 #include "hvq_phash.h"
 #include "hvq_scale.h"
 #include "hvq_filter.h"
+#include "hvq_warp.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -92,6 +93,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_hash_nearest(const uint64
 extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_filter.hip.  Weak for the same reason: hvq_filter_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -378,6 +381,7 @@ struct HvqContext {
      * serves every launch pair and every call, as ck_acc */
     uint8_t *ph_acc = nullptr;
     size_t ph_cap = 0;
+    int wp_force = 0;                  /* hvq_warp_force_direct: 0 the chosen body of hvq_warp.hip, 1 the direct one, 2 the tiled one wherever LDS holds the box */
     bool fl_force_filter = false;      /* hvq_filter_force_filter: identity planes take the filter body of hvq_filter.hip, not the copy body */
     bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
@@ -3223,6 +3227,99 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
     if (!hvq_launch_filter) return fail(HVQ_E_NOGPU, "this build of the library has no filter kernel (hvq_filter.hip is not linked)");
     return export_enqueue(c, up.data(), up.size(), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_filter(t, n, max_tiles, st); });
+}
+
+/* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain,
+ * hvq_scale_pictures' lookup, refusals and ordering.  Three jobs a picture, one per plane, each with the plane's own inverse map; one
+ * launch behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no
+ * memset. */
+HVQ_EXPORT int hvq_warp_check(const HvqWarp *w)
+{
+    if (!w) return fail(HVQ_E_ARG, "bad arguments");
+    const int32_t m[4] = { w->m00, w->m01, w->m10, w->m11 };
+    for (int i = 0; i < 4; ++i)
+        if (m[i] > HVQ_WARP_MAX_SCALE || m[i] < -HVQ_WARP_MAX_SCALE) return fail(HVQ_E_ARG, "warp: m%d%d = %d beyond %d", i >> 1, i & 1, m[i], HVQ_WARP_MAX_SCALE);
+    if (w->border != HVQ_WARP_REPLICATE && w->border != HVQ_WARP_CONSTANT) return fail(HVQ_E_ARG, "warp: border %d", w->border);
+    if (w->pad) return fail(HVQ_E_ARG, "warp: pad %d is not 0", w->pad);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_warp_body(const HvqWarp *w, int dst_h, int dst_v, int src_h, int src_v, int nx, int ny)
+{
+    { int rc = hvq_warp_check(w); if (rc) return rc; }
+    if ((dst_h != 1 && dst_h != 2) || (dst_v != 1 && dst_v != 2) || (src_h != 1 && src_h != 2) || (src_v != 1 && src_v != 2))
+        return fail(HVQ_E_ARG, "samplings %d x %d -> %d x %d: each is 1 or 2", src_h, src_v, dst_h, dst_v);
+    if (nx < 1 || ny < 1 || nx > 8192 || ny > 8192) return fail(HVQ_E_ARG, "%d x %d: a plane has 1 .. 8192 samples a side", nx, ny);
+    const int32_t m[6] = { w->m00, w->m01, w->m10, w->m11, w->t0, w->t1 };
+    return (int)hvq_wp_job(0, 0, (uint32_t)nx, (uint32_t)ny, 8, 8, m, w->border, 0, dst_h, dst_v, src_h, src_v, 0).body;
+}
+
+HVQ_EXPORT int hvq_warp_force_direct(HvqContext *c, int on)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = c->wp_force;
+    c->wp_force = on == 2 ? 2 : on != 0;
+    return was;
+}
+
+HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                 const HvqWarp *warps, const HvqWarpDst *dst, void *hip_stream)
+{
+    static_assert(HVQ_WARP_DIRECT == (int)HVQ_WP_DIRECT && HVQ_WARP_TILED == (int)HVQ_WP_TILED && HVQ_WARP_MAX_SCALE == HVQ_WP_MAX_M,
+                  "the header's names are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !warps))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    for (int i = 0; i < n; ++i) { int rc = hvq_warp_check(warps + i); if (rc) return rc; }
+    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
+    std::vector<int> res_s, res_o;
+    for (int i = 0; i < n; ++i)
+        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
+    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    std::vector<HvqWarpJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    HvqWarpDst seen{};                                  /* a call usually repeats few shapes: the geometry check (a parser's tables) is kept from the picture before */
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        if (src && src[i]) {
+            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+            a = (const uint8_t *)src[i];
+        } else {
+            int rc = HVQ_OK;
+            a = resident_picture(c, streams[i], ordinals[i], &rc);
+            if (!a) return rc;
+        }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        const HvqWarpDst &d = dst[i];
+        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
+            int rc = scale_geometry(d.width, d.height, d.h_samp, d.v_samp);
+            if (rc) return rc;
+            seen = d;
+        }
+        const HvqWarp &w = warps[i];
+        const int32_t m[6] = { w.m00, w.m01, w.m10, w.m11, w.t0, w.t1 };
+        const int dws = d.h_samp == 2, dhs = d.v_samp == 2;
+        const uint8_t *sp = a;
+        uint8_t *dp = (uint8_t *)d.ptr;
+        uint32_t tiles = 0;
+        for (int p = 0; p < 3; ++p) {
+            const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0, xd = p ? dws : 0, yd = p ? dhs : 0;
+            const uint32_t nx = (uint32_t)(s.w >> xs), ny = (uint32_t)(s.h >> ys);
+            const uint32_t mx = (uint32_t)(d.width >> xd), my = (uint32_t)(d.height >> yd);
+            HvqWarpJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_wp_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, mx, my, m, w.border, w.fill[p], 1 << xd, 1 << yd, 1 << xs, 1 << ys, c->wp_force);
+            tiles += j.tiles;
+            sp += (size_t)nx * ny;
+            dp += (size_t)mx * my;
+        }
+        max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!hvq_launch_warp) return fail(HVQ_E_NOGPU, "this build of the library has no warp kernel (hvq_warp.hip is not linked)");
+    return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqWarpJob), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_warp(tab, n, max_tiles, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -693,6 +693,76 @@ int     hvq_filter_pictures(HvqContext *ctx, int n, const int *streams, const in
                             const HvqFilter *filters, int nfilters, const int *which, void *const *dst, void *hip_stream);
 int     hvq_filter_force_filter(HvqContext *ctx, int on);
 
+/* Resident pictures WARPED into uint8 pictures of a TARGET GEOMETRY in slot layout, where they lie: for `n` pictures, of any streams,
+ * sizes and samplings, in one kernel launch on the caller's HIP stream and without a host synchronisation, each plane through its own
+ * affine inverse map with bilinear taps in exact integers and one rounding.  Translation (stabilising a clip by its global motion),
+ * the mirrors, the transpose, the quarter turns (a portrait clip turned upright: the target swaps width and height), rotation, zoom
+ * and shear are parameter sets of it (hvqm4_amd.warp builds them); warp plus resize is one call.  The result composes like
+ * hvq_scale_pictures': whatever takes `src` or `ref.ptr` takes it.  The values are specified as exact integers: this text is the
+ * authority for them.
+ *   The map.   warps[i] = { m00, m01, m10, m11, t0, t1 } in Q16 (65536 = 1.0) maps TARGET luma coordinates to SOURCE luma coordinates:
+ *              u = m00 x + m01 y + t0, v = m10 x + m11 y + t1.  Sample centres lie at integer + 1/2; chroma is sited at the centre of
+ *              its luma cell (what the area filter of hvq_scale_pictures implies).
+ *   Values.    Plane p has target sampling (hx', vy') and source sampling (hx, vy), both (1, 1) for Y; the target plane has My x Mx
+ *              samples, the source plane a has Ny x Nx.  For target sample (x, y):
+ *              NU = m00 hx' (2x + 1) + m01 vy' (2y + 1) + 2 t0 - 65536 hx          (64 bits; Q17 luma units)
+ *              NV = m10 hx' (2x + 1) + m11 vy' (2y + 1) + 2 t1 - 65536 vy
+ *              U8 = floor((NU + 256 hx) / (512 hx))     V8 = floor((NV + 256 vy) / (512 vy))     (arithmetic shifts: hx, vy are 1 or 2)
+ *              ix = floor(U8 / 256), fx = U8 - 256 ix (0 .. 255); iy, fy likewise
+ *              tap(j, i) = a[cy(iy + j)][cx(ix + i)]                        border == HVQ_WARP_REPLICATE (cx, cy clamp into the plane)
+ *                        = inside the plane ? a[iy + j][ix + i] : fill[p]   border == HVQ_WARP_CONSTANT
+ *              S   = (256 - fy) ((256 - fx) tap(0,0) + fx tap(0,1)) + fy ((256 - fx) tap(1,0) + fx tap(1,1))
+ *              out = (S + 32768) >> 16                                      ONE rounding; S + 32768 < 2^31
+ *              Any evaluation order that yields these integers is allowed; no intermediate rounding is.  Saturating U8 to
+ *              [-512, 256 Nx] and V8 to [-512, 256 Ny] changes no value under either border (beyond them every tap lies on the same
+ *              side outside the plane): behind it a lane works in 32 bits.  Inside a tile of 64 x 16 targets the deltas of NU and NV
+ *              against the tile's first target stay below 2^31 under the limit on the coefficients.
+ *   Limits.    |m..| <= HVQ_WARP_MAX_SCALE = 32 * 65536; t0, t1 any int32; border 0 or 1; pad 0.  A singular matrix is not refused: an
+ *              all-zero linear part is a well-defined constant picture.
+ *   Known answers.  The identity (m00 = m11 = 65536, the rest 0) copies every plane in every sampling.  t0 = 32768 gives
+ *              (a[x] + a[x + 1] + 1) >> 1; m00 = 131072 gives (a[2x] + a[2x + 1] + 1) >> 1.  m00 = -65536, t0 = 65536 W is the exact
+ *              mirror, in Y and in 2:1-sampled chroma alike; m00 = m11 = 0, m01 = m10 = 65536 the exact transpose; the three quarter
+ *              turns are exact permutations whenever the chroma sampling is square.  A flat picture stays flat under REPLICATE.
+ *   dst[i]:    ptr: a non-null DEVICE pointer, a multiple of 16: Y | U | V tightly packed, the target geometry's slot layout,
+ *              hvq_scale_bytes(width, height, h_samp, v_samp) bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  It must not overlap a source of the call: the
+ *              caller's business, not checked.  width, height, h_samp, v_samp: the target geometry, one that hvq_stream_open accepts
+ *              (else HVQ_E_GEOMETRY).
+ *   hvq_warp_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL record, a coefficient beyond the limit, a bad border, a non-zero pad.
+ *   hvq_warp_body (host only): the body of the kernel a plane takes under a warp: (dst_h, dst_v) the TARGET sampling of the plane,
+ *              (src_h, src_v) its SOURCE sampling (both 1, 1 for Y), nx x ny its source samples.  HVQ_WARP_DIRECT: every lane gathers
+ *              its four taps from memory; serves every map.  HVQ_WARP_TILED: the source bounding box of a tile of 64 x 16 targets
+ *              goes through LDS (the body for turns, where a row of targets crosses many source rows).  The values do not depend on
+ *              it.  hvq_warp_force_direct(ctx, 1) makes every later call of the context take the direct body (0: the chosen one
+ *              again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) and returns the setting
+ *              before: for tests that compare the bodies with ==.
+ *   HVQ_E_ARG for the whole call: what hvq_warp_check refuses; a null or misaligned ptr; n above 65535; a bad stream or ordinal; a
+ *              src[i] with an ordinal other than -1 or that is no multiple of 16; a NULL context, warps or dst.  n == 0 is HVQ_OK and
+ *              does nothing.  Every argument is checked before anything is enqueued: a refused call leaves every destination
+ *              untouched.  HVQ_E_NOGPU (after those checks) from a build without the warp kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_scale_pictures'. */
+#define HVQ_WARP_MAX_SCALE (32 * 65536)
+#define HVQ_WARP_REPLICATE 0
+#define HVQ_WARP_CONSTANT  1
+#define HVQ_WARP_DIRECT    0
+#define HVQ_WARP_TILED     1
+typedef struct HvqWarp {
+    int32_t m00, m01, m10, m11, t0, t1;           /* Q16: target luma coordinates -> source luma coordinates */
+    int32_t border;                               /* HVQ_WARP_REPLICATE or HVQ_WARP_CONSTANT */
+    uint8_t fill[3];                              /* the value outside the plane under HVQ_WARP_CONSTANT: Y, U, V */
+    uint8_t pad;                                  /* 0 */
+} HvqWarp;
+typedef struct HvqWarpDst {
+    void   *ptr;                                  /* device, multiple of 16: Y | U | V tightly packed, the target geometry's slot layout */
+    int32_t width, height, h_samp, v_samp;        /* target geometry: one that hvq_stream_open accepts */
+} HvqWarpDst;
+int     hvq_warp_check(const HvqWarp *w);
+int     hvq_warp_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                          const HvqWarp *warps, const HvqWarpDst *dst, void *hip_stream);
+int     hvq_warp_body(const HvqWarp *w, int dst_h, int dst_v, int src_h, int src_v, int nx, int ny);
+int     hvq_warp_force_direct(HvqContext *ctx, int on);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
