@@ -176,6 +176,101 @@ class Context:
         check(lib().hvq_picture_device_ptr(self._h, sid, ordinal, C.byref(ptr)))
         return int(ptr.value or 0)
 
+    # ---- what the calls on resident pictures share (export() and everything below it): each check where the calls have it, in their
+    # order.  Static, and named through the class: the methods also run on a stand-in that has only _geom, _h and pic_bytes
+    @staticmethod
+    def _pictures(geom, sids, ordinals, limit: bool = False) -> int:
+        """the picture list of a call on a context whose open streams are `geom`'s keys -> n.  limit: a call of several jobs a picture
+        refuses more than 65535 pictures here, and looks at every distinct stream once"""
+        n = len(sids)
+        if len(ordinals) != n:
+            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
+        if limit and n > 65535:
+            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        for s in (set(sids) if limit else sids):
+            if s not in geom:
+                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        return n
+
+    @staticmethod
+    def _out_tensor(out, shape, dtype, device="cuda", name="out", align=0):
+        """the tensor a call writes: a new one, or the caller's after its checks (the device is checked last)"""
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}")
+        if align and out.data_ptr() & (align - 1):
+            raise ValueError(f"{name}: pointer {out.data_ptr():#x} must be a multiple of {align}")
+        if out.device.type != "cuda":
+            raise ValueError(f"{name} is on {out.device}, not a GPU")
+        return out
+
+    @staticmethod
+    def _out_list(out, n, check):
+        """the caller's list of n tensors that a call writes -> a list; check(i, t) raises on a tensor the call does not take (the device
+        is checked last)"""
+        if not isinstance(out, (list, tuple)) or len(out) != n:
+            raise ValueError(f"out must be a list of {n} tensors")
+        for i, t in enumerate(out):
+            check(i, t)
+            if t.device.type != "cuda":
+                raise ValueError(f"out[{i}] is on {t.device}, not a GPU")
+        return list(out)
+
+    @staticmethod
+    def _slot_outputs(out, nb, uniform, differ):
+        """the pictures in slot layout that a call writes, nb[i] bytes each: one uint8 tensor [n, bytes] when the geometries are one
+        (`uniform`), a list of n otherwise; a new one, or the caller's after its checks -> (out, its device, uint64[n] the pictures'
+        addresses).  differ: what differs when a list is asked for, for the message"""
+        import torch
+        n = len(nb)
+        width = nb[0] if n else 0
+        if out is None:
+            out = torch.empty((n, width), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
+        if uniform:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, width) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {width})")
+            device = out.device
+            where = np.arange(n, dtype=np.uint64) * np.uint64(width) + np.uint64(out.data_ptr())       # rows of a multiple of 16 bytes
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != n:
+                raise ValueError(f"out must be a list of {n} tensors (the {differ} differ)")
+            for i, t in enumerate(out):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
+            device = out[0].device if n else torch.device("cuda")
+            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
+            if len({t.get_device() for t in out}) > 1:
+                raise ValueError("out: the tensors lie on different devices")
+        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
+            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
+            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
+        if device.type != "cuda":
+            raise ValueError(f"out is on {device}, not a GPU")
+        return out, device, where
+
+    @staticmethod
+    def _ref_array(refs):
+        """metrics.references' result -> HvqMetricsRef[n], or None"""
+        from .metrics import HvqMetricsRef
+        return None if refs is None else C.cast((HvqMetricsRef * len(refs))(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
+
+    @staticmethod
+    def _ptr_array(ptrs):
+        """checksums.sources' result, or any list of addresses -> void *[n], or None"""
+        return None if ptrs is None else C.cast((C.c_void_p * len(ptrs))(*ptrs), C.c_void_p)
+
+    @staticmethod
+    def _launch_args(device, sids, ordinals):
+        """once everything is checked: one HIP runtime in the process, then (int[n] streams, int[n] ordinals, torch's current stream of
+        `device`; None: no stream)"""
+        import torch
+        from .export import check_one_hip_runtime
+        check_one_hip_runtime()
+        stream = None if device is None else torch.cuda.current_stream(device).cuda_stream
+        return (C.c_int * len(sids))(*sids), (C.c_int * len(ordinals))(*ordinals), C.c_void_p(stream)
+
     def export(self, sids, ordinals, out, fmt: str = "rgb") -> None:
         """hvq_export_pictures: resident pictures into uint8 CUDA tensors, in one launch on torch's current stream of `out`'s
         device, without a host synchronisation.  fmt "rgb" -> [H, W, 3], "rgbp" (RGB planar) and "yuv444p" -> [3, H, W]; `out` is
@@ -183,23 +278,14 @@ class Context:
         Work queued on that stream afterwards sees the pictures; the library keeps their slots from being rewritten before the
         export has read them."""
         import torch
-        from .export import FORMATS, HvqExportDst, check_one_hip_runtime, destinations
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        from .export import FORMATS, HvqExportDst, destinations
+        n = Context._pictures(self._geom, sids, ordinals)
         geoms = [self._geom[s] for s in sids]
         dsts = destinations(out, geoms, fmt)
-        check_one_hip_runtime()
         dev = out.device if isinstance(out, torch.Tensor) else (out[0].device if n else torch.device("cuda"))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
+        a_s, a_o, stream = Context._launch_args(dev, sids, ordinals)
         a_d = (HvqExportDst * n)(*[HvqExportDst(p, r, pl) for p, r, pl in dsts])
-        check(lib().hvq_export_pictures(self._h, n, a_s, a_o, FORMATS[fmt], C.cast(a_d, C.c_void_p),
-                                           C.c_void_p(stream)))
+        check(lib().hvq_export_pictures(self._h, n, a_s, a_o, FORMATS[fmt], C.cast(a_d, C.c_void_p), stream))
 
     def export_float(self, sids, ordinals, out, *, crop=None, mean=(0, 0, 0), std=(1, 1, 1), scale: float = 1 / 255,
                      antialias: bool = False) -> None:
@@ -221,28 +307,20 @@ class Context:
         """export_float; filt = None: hvq_export_tensors, else hvq_export_resampled with that HVQ_FILTER_* (tools and tests pass
         FILTER_TRIANGLE_DIRECT)"""
         import torch
-        from .export import HvqTensorDst, check_one_hip_runtime, crops, float_destinations, normalisation
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        from .export import HvqTensorDst, crops, float_destinations, normalisation
+        n = Context._pictures(self._geom, sids, ordinals)
         mul, add = normalisation(mean, std, scale)
         rects = crops(crop, [self._geom[s] for s in sids])
         dtype, dsts = float_destinations(out, n)
-        check_one_hip_runtime()
         dev = out.device if isinstance(out, torch.Tensor) else (out[0].device if n else torch.device("cuda"))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
+        a_s, a_o, stream = Context._launch_args(dev, sids, ordinals)
         a_d = (HvqTensorDst * n)(*[HvqTensorDst(p, r, pl, w, h, *rect) for (p, r, pl, w, h), rect in zip(dsts, rects)])
         if filt is None:
             check(lib().hvq_export_tensors(self._h, n, a_s, a_o, dtype, (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
-                                           C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
+                                           C.cast(a_d, C.c_void_p), stream))
         else:
             check(lib().hvq_export_resampled(self._h, n, a_s, a_o, dtype, int(filt), (C.c_float * 3)(*mul), (C.c_float * 3)(*add),
-                                             C.cast(a_d, C.c_void_p), C.c_void_p(stream)))
+                                             C.cast(a_d, C.c_void_p), stream))
 
     def picture_metrics(self, sids, ordinals, ref=None, out=None):
         """hvq_picture_metrics: per plane (Y, U, V) the exact integers sum_a, sum_b, sum |a - b| and sum (a - b)^2 of resident
@@ -254,28 +332,12 @@ class Context:
         hvqm4_amd.metrics turns the records into PSNR, mean absolute difference, mean and variance.  Ordering and slot safety are
         export()'s."""
         import torch
-        from .export import check_one_hip_runtime
-        from .metrics import HvqMetricsRef, references
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        from .metrics import references
+        n = Context._pictures(self._geom, sids, ordinals)
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
-        if out is None:
-            out = torch.empty((n, 3, 4), dtype=torch.int64, device="cuda")
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 3, 4) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 3, 4)")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_r = None if refs is None else C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
-        check(lib().hvq_picture_metrics(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        out = Context._out_tensor(out, (n, 3, 4), torch.int64)
+        a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
+        check(lib().hvq_picture_metrics(self._h, n, a_s, a_o, Context._ref_array(refs), C.c_void_p(out.data_ptr()), stream))
         return out
 
     def picture_ssim(self, sids, ordinals, ref, out=None, maps=False):
@@ -288,28 +350,16 @@ class Context:
         values of Y, U, V (views of one allocation per pair).  hvqm4_amd.metrics.ssim / ssim_all / ssim_db read the records.
         Ordering and slot safety are export()'s."""
         import torch
-        from .export import check_one_hip_runtime
-        from .metrics import HvqMetricsRef, references
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        from .metrics import references
+        n = Context._pictures(self._geom, sids, ordinals)
         if ref is None:
             raise ValueError("picture_ssim needs a reference for every picture (SSIM against zeros means nothing)")
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
         for i, r in enumerate(refs):
             if r[0] < 0 and r[2] is None:
                 raise ValueError(f"reference {i} is None: SSIM against zeros means nothing")
-        if out is None:
-            out = torch.empty((n, 3, 2), dtype=torch.int64, device="cuda")
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 3, 2) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 3, 2)")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
+        out = Context._out_tensor(out, (n, 3, 2), torch.int64)
+        a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
         views, a_m = None, None
         if maps:
             views, ptrs = [], []
@@ -322,12 +372,8 @@ class Context:
                     at += r * c
                 views.append(tuple(tri))
                 ptrs.append(buf.data_ptr())
-            a_m = C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_r = C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
-        check(lib().hvq_picture_ssim(self._h, n, a_s, a_o, a_r, C.c_void_p(out.data_ptr()), a_m, C.c_void_p(stream)))
+            a_m = Context._ptr_array(ptrs)
+        check(lib().hvq_picture_ssim(self._h, n, a_s, a_o, Context._ref_array(refs), C.c_void_p(out.data_ptr()), a_m, stream))
         return (out, views) if maps else out
 
     def picture_checksums(self, sids, ordinals, src=None, out=None):
@@ -341,27 +387,11 @@ class Context:
         are export()'s."""
         import torch
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        n = Context._pictures(self._geom, sids, ordinals)
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.int64, device="cuda")
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 8) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 8)")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
-        check(lib().hvq_picture_checksums(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        out = Context._out_tensor(out, (n, 8), torch.int64)
+        a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
+        check(lib().hvq_picture_checksums(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(out.data_ptr()), stream))
         return out
 
     def picture_hashes(self, sids, ordinals, src=None, out=None):
@@ -375,27 +405,11 @@ class Context:
         export()'s."""
         import torch
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        n = Context._pictures(self._geom, sids, ordinals)
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
-        if out is None:
-            out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n}, 4)")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
-        check(lib().hvq_picture_hashes(self._h, n, a_s, a_o, a_p, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        out = Context._out_tensor(out, (n, 4), torch.int64)
+        a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
+        check(lib().hvq_picture_hashes(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(out.data_ptr()), stream))
         return out
 
     def hash_nearest(self, queries, database=None, self_offset=-1, threshold=10, out=None):
@@ -408,24 +422,14 @@ class Context:
         de-duplication of a sequence -- column first_within is then hvqm4_amd.phash.duplicates.  A query without a candidate gets
         (-1, 65, 0, -1)."""
         import torch
-        from .export import check_one_hip_runtime
         from .phash import hash_views
         if not 0 <= threshold <= 64:
             raise ValueError(f"threshold {threshold} outside [0, 64]")
         (qp, nq, qs), (dp, ndb, ds), off = hash_views(queries, database, self_offset)
-        if out is None:
-            out = torch.empty((nq, 4), dtype=torch.int32, device=queries.device)
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (nq, 4) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int32 tensor of shape ({nq}, 4)")
-            if out.data_ptr() & 15:
-                raise ValueError(f"out: pointer {out.data_ptr():#x} must be a multiple of 16")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
+        out = Context._out_tensor(out, (nq, 4), torch.int32, device=queries.device, align=16)
+        stream = Context._launch_args(out.device, (), ())[2]
         check(lib().hvq_hash_nearest(self._h, C.c_void_p(qp), nq, qs, C.c_void_p(dp) if ndb else None, ndb, ds, off, threshold,
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+                                     C.c_void_p(out.data_ptr()), stream))
         return out
 
     def picture_histograms(self, sids, ordinals, ref=None, src=None, out=None):
@@ -439,35 +443,18 @@ class Context:
         Otsu, equalisation, histogram distances, maximum error).  Ordering and slot safety are export()'s."""
         import torch
         from .checksums import sources
-        from .export import check_one_hip_runtime
         from .histograms import BINS, HIST_ABSDIFF, HIST_VALUES
-        from .metrics import HvqMetricsRef, references
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        from .metrics import references
+        n = Context._pictures(self._geom, sids, ordinals)
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
         for i, r in enumerate(refs or ()):
             if r[0] < 0 and r[2] is None:
                 raise ValueError(f"reference {i} is None: |a - 0| is a itself, ref=None gives its histogram")
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
-        if out is None:
-            out = torch.empty((n, 3, BINS), dtype=torch.int32, device="cuda")
-        else:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (n, 3, BINS) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int32 tensor of shape ({n}, 3, {BINS})")
-            if out.device.type != "cuda":
-                raise ValueError(f"out is on {out.device}, not a GPU")
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
-        a_r = None if refs is None else C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
-        check(lib().hvq_picture_histograms(self._h, n, a_s, a_o, a_p, HIST_VALUES if refs is None else HIST_ABSDIFF, a_r,
-                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        out = Context._out_tensor(out, (n, 3, BINS), torch.int32)
+        a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
+        check(lib().hvq_picture_histograms(self._h, n, a_s, a_o, Context._ptr_array(ptrs), HIST_VALUES if refs is None else HIST_ABSDIFF,
+                                           Context._ref_array(refs), C.c_void_p(out.data_ptr()), stream))
         return out
 
     def picture_motion(self, sids, ordinals, ref, block=16, radius=8, out=None):
@@ -480,15 +467,9 @@ class Context:
         and height are multiples of 16), `radius` 0 .. 15.  hvqm4_amd.motion reads the fields on the host.  Ordering and slot safety
         are export()'s."""
         import torch
-        from .export import check_one_hip_runtime
-        from .metrics import HvqMetricsRef, references
+        from .metrics import references
         from .motion import MAX_RADIUS, blocks
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        n = Context._pictures(self._geom, sids, ordinals)
         if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_RADIUS:
             raise ValueError(f"radius {radius!r}: an integer in [0, {MAX_RADIUS}]")
         dims = [blocks(self._geom[s][0], self._geom[s][1], block) for s in sids]
@@ -501,21 +482,14 @@ class Context:
         if out is None:
             out = [torch.empty((r, c, 4), dtype=torch.int32, device="cuda") for r, c in dims]
         else:
-            if not isinstance(out, (list, tuple)) or len(out) != n:
-                raise ValueError(f"out must be a list of {n} tensors")
-            for i, (t, (r, c)) in enumerate(zip(out, dims)):
+            def field(i, t):
+                r, c = dims[i]
                 if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (r, c, 4) or not t.is_contiguous():
                     raise ValueError(f"out[{i}] must be a contiguous int32 tensor of shape ({r}, {c}, 4)")
-                if t.device.type != "cuda":
-                    raise ValueError(f"out[{i}] is on {t.device}, not a GPU")
-            out = list(out)
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(out[0].device).cuda_stream if n else None
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_r = C.cast((HvqMetricsRef * n)(*[HvqMetricsRef(s, o, p) for s, o, p in refs]), C.c_void_p)
-        a_f = C.cast((C.c_void_p * n)(*[t.data_ptr() for t in out]), C.c_void_p)
-        check(lib().hvq_picture_motion(self._h, n, a_s, a_o, a_r, block, radius, a_f, C.c_void_p(stream)))
+            out = Context._out_list(out, n, field)
+        a_s, a_o, stream = Context._launch_args(out[0].device if n else None, sids, ordinals)
+        a_f = Context._ptr_array([t.data_ptr() for t in out])
+        check(lib().hvq_picture_motion(self._h, n, a_s, a_o, Context._ref_array(refs), block, radius, a_f, stream))
         return out
 
     def encode_jpeg(self, sids, ordinals, quality=90, src=None, out=None, lengths=None):
@@ -529,46 +503,26 @@ class Context:
         pictures are; that memory is encoded in the picture's place and ordinals[i] must be -1.  Ordering and slot safety are export()'s."""
         import torch
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        for s in sids:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        n = Context._pictures(self._geom, sids, ordinals)
         if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
             raise ValueError(f"quality {quality!r}: an integer in [1, 100]")
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
         if out is None:
             out = [torch.empty(2 * self.pic_bytes(s) + 1024, dtype=torch.uint8, device="cuda") for s in sids]
         else:
-            if not isinstance(out, (list, tuple)) or len(out) != n:
-                raise ValueError(f"out must be a list of {n} tensors")
-            for i, t in enumerate(out):
+            def file(i, t):
                 if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.numel() < 631:
                     raise ValueError(f"out[{i}] must be a contiguous one-dimensional uint8 tensor of 631 elements at least")
                 if t.data_ptr() % 16:
                     raise ValueError(f"out[{i}]: the data pointer must be a multiple of 16")
-                if t.device.type != "cuda":
-                    raise ValueError(f"out[{i}] is on {t.device}, not a GPU")
-            out = list(out)
-        if lengths is None:
-            lengths = torch.empty(n, dtype=torch.int64, device="cuda")
-        else:
-            if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int64 or tuple(lengths.shape) != (n,) or not lengths.is_contiguous():
-                raise ValueError(f"lengths must be a contiguous int64 tensor of shape ({n},)")
-            if lengths.device.type != "cuda":
-                raise ValueError(f"lengths is on {lengths.device}, not a GPU")
+            out = Context._out_list(out, n, file)
+        lengths = Context._out_tensor(lengths, (n,), torch.int64, name="lengths")
         if not n:
             return out, lengths
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(lengths.device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
-        a_f = C.cast((C.c_void_p * n)(*[t.data_ptr() for t in out]), C.c_void_p)
+        a_s, a_o, stream = Context._launch_args(lengths.device, sids, ordinals)
+        a_f = Context._ptr_array([t.data_ptr() for t in out])
         a_c = C.cast((C.c_uint64 * n)(*[t.numel() for t in out]), C.c_void_p)
-        check(lib().hvq_encode_jpeg(self._h, n, a_s, a_o, a_p, quality, a_f, a_c, C.c_void_p(lengths.data_ptr()), C.c_void_p(stream)))
+        check(lib().hvq_encode_jpeg(self._h, n, a_s, a_o, Context._ptr_array(ptrs), quality, a_f, a_c, C.c_void_p(lengths.data_ptr()), stream))
         return out, lengths
 
     def _geometry(self, sid):
@@ -596,19 +550,10 @@ class Context:
         aligned; it is overwritten whole).  Whatever takes src= or ref.ptr takes a row of the result, with an open stream of the
         target geometry to carry it.  hvqm4_amd.scale gives the expected bytes (of_picture), the plane views and the target sizes
         (fit, pyramid).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
-        import torch
         from . import scale as sc
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        if n > 65535:
-            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
         streams = set(sids)
-        for s in streams:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
         sizes, one_size = sc.per_picture(size, n, 2, "size")
         if n and (sizes[0] is None if one_size else any(v is None for v in sizes)):
             raise ValueError("size: every picture needs a target size")
@@ -632,39 +577,14 @@ class Context:
         dst_geoms = {v[0] for v in shapes.values()}
         uniform = len(dst_geoms) == 1
         nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
-        if out is None:
-            out = torch.empty((n, nb[0]), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
-        if uniform:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0]) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0]})")
-            device = out.device
-            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0]) + np.uint64(out.data_ptr())       # rows of a multiple of 16 bytes
-        else:
-            if not isinstance(out, (list, tuple)) or len(out) != n:
-                raise ValueError(f"out must be a list of {n} tensors (the target geometries differ)")
-            for i, t in enumerate(out):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
-                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
-            device = out[0].device if n else torch.device("cuda")
-            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
-            if len({t.get_device() for t in out}) > 1:
-                raise ValueError("out: the tensors lie on different devices")
-        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
-            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
-            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
-        if device.type != "cuda":
-            raise ValueError(f"out is on {device}, not a GPU")
+        out, device, where = Context._slot_outputs(out, nb, uniform, "target geometries")
         if not n:
             return out
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         a_d = np.empty(n, dtype=_SCALE_DST)                                  # HvqScaleDst[n]
         a_d["ptr"] = where
         a_d["rest"] = shapes[keys[0]][2] if len(shapes) == 1 else [shapes[k][2] for k in keys]
-        check(lib().hvq_scale_pictures(self._h, n, a_s, a_o, a_p, C.c_void_p(a_d.ctypes.data), C.c_void_p(stream)))
+        check(lib().hvq_scale_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(a_d.ctypes.data), stream))
         return out
 
     def filter_force_filter(self, on: bool) -> bool:
@@ -682,18 +602,9 @@ class Context:
         contiguous, rows 16-byte aligned; it is overwritten whole and must not overlap a source).  Whatever takes src= or ref.ptr
         takes a row of the result.  hvqm4_amd.filters builds the filters and gives the expected bytes (of_picture).  `src` as in
         picture_checksums.  Ordering and slot safety are export()'s."""
-        import torch
         from . import filters as fl
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        if n > 65535:
-            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
-        for s in set(sids):
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
         if isinstance(filt, fl.Filter):
             table, which = [filt], None
         else:
@@ -716,40 +627,15 @@ class Context:
         ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
         nb = [pb[s] for s in sids]
         uniform = len({self._geometry(s) for s in streams}) <= 1
-        if out is None:
-            out = torch.empty((n, nb[0] if n else 0), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
-        if uniform:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0] if n else 0) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0] if n else 0})")
-            device = out.device
-            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0] if n else 0) + np.uint64(out.data_ptr())     # rows of a multiple of 16 bytes
-        else:
-            if not isinstance(out, (list, tuple)) or len(out) != n:
-                raise ValueError(f"out must be a list of {n} tensors (the geometries differ)")
-            for i, t in enumerate(out):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
-                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
-            device = out[0].device
-            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
-            if len({t.get_device() for t in out}) > 1:
-                raise ValueError("out: the tensors lie on different devices")
-        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
-            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
-            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
-        if device.type != "cuda":
-            raise ValueError(f"out is on {device}, not a GPU")
+        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
         if not n:
             return out
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         from ._lib import HvqFilter
         a_f = (HvqFilter * len(table))(*[f.to_struct() for f in table])
         a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
         a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
-        check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, a_p, C.cast(a_f, C.c_void_p), len(table), a_w, a_d, C.c_void_p(stream)))
+        check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_f, C.c_void_p), len(table), a_w, a_d, stream))
         return out
 
     def warp_force_direct(self, on) -> int:
@@ -768,20 +654,11 @@ class Context:
         not overlap a source).  Whatever takes src= or ref.ptr takes a row of the result, with an open stream of the target geometry
         to carry it.  hvqm4_amd.warp builds the maps and gives the expected bytes (of_picture).  `src` as in picture_checksums.
         Ordering and slot safety are export()'s."""
-        import torch
         from . import scale as sc
         from . import warp as wp
         from .checksums import sources
-        from .export import check_one_hip_runtime
-        n = len(sids)
-        if len(ordinals) != n:
-            raise ValueError(f"{n} streams but {len(ordinals)} ordinals")
-        if n > 65535:
-            raise ValueError(f"{n} pictures: one call takes 65535 at the most")
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
         streams = set(sids)
-        for s in streams:
-            if s not in self._geom:
-                raise HvqError(HVQ_E_ARG, f"bad stream {s}")
         if isinstance(warp, wp.Warp):
             warps = None                                                   # one map for all: one row, broadcast
             wp.check(warp)
@@ -813,42 +690,17 @@ class Context:
         ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
         uniform = len({v[0] for v in shapes.values()}) <= 1
         nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
-        if out is None:
-            out = torch.empty((n, nb[0] if n else 0), dtype=torch.uint8, device="cuda") if uniform else [torch.empty(b, dtype=torch.uint8, device="cuda") for b in nb]
-        if uniform:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, nb[0] if n else 0) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {nb[0] if n else 0})")
-            device = out.device
-            where = np.arange(n, dtype=np.uint64) * np.uint64(nb[0] if n else 0) + np.uint64(out.data_ptr())     # rows of a multiple of 16 bytes
-        else:
-            if not isinstance(out, (list, tuple)) or len(out) != n:
-                raise ValueError(f"out must be a list of {n} tensors (the target geometries differ)")
-            for i, t in enumerate(out):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.shape[0] != nb[i] or not t.is_contiguous():
-                    raise ValueError(f"out[{i}] must be a contiguous uint8 tensor of shape ({nb[i]},)")
-            device = out[0].device
-            where = np.array([t.data_ptr() for t in out], dtype=np.uint64)
-            if len({t.get_device() for t in out}) > 1:
-                raise ValueError("out: the tensors lie on different devices")
-        if n and int(np.bitwise_and(where, np.uint64(15)).max()):
-            i = int(np.flatnonzero(np.bitwise_and(where, np.uint64(15)))[0])
-            raise ValueError(f"out: the pointer of picture {i}, {int(where[i]):#x}, must be a multiple of 16")
-        if device.type != "cuda":
-            raise ValueError(f"out is on {device}, not a GPU")
+        out, device, where = Context._slot_outputs(out, nb, uniform, "target geometries")
         if not n:
             return out
-        check_one_hip_runtime()
-        stream = torch.cuda.current_stream(device).cuda_stream
-        a_s = (C.c_int * n)(*sids)
-        a_o = (C.c_int * n)(*ordinals)
-        a_p = None if ptrs is None else C.cast((C.c_void_p * n)(*ptrs), C.c_void_p)
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         a_w = np.empty(n, dtype=_WARP)                                       # HvqWarp[n]
         a_w["m"] = warp.coefficients() + (warp.border,) if warps is None else [w.coefficients() + (w.border,) for w in warps]
         a_w["fill"] = warp.fill + (0,) if warps is None else [w.fill + (0,) for w in warps]
         a_d = np.empty(n, dtype=_WARP_DST)                                   # HvqWarpDst[n]
         a_d["ptr"] = where
         a_d["rest"] = shapes[keys[0]][0] if len(shapes) == 1 else [shapes[k][0] for k in keys]
-        check(lib().hvq_warp_pictures(self._h, n, a_s, a_o, a_p, C.c_void_p(a_w.ctypes.data), C.c_void_p(a_d.ctypes.data), C.c_void_p(stream)))
+        check(lib().hvq_warp_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(a_w.ctypes.data), C.c_void_p(a_d.ctypes.data), stream))
         return out
 
     def _ssim_dims(self, sid):

@@ -2268,17 +2268,112 @@ static const uint8_t *resident_picture(HvqContext *c, int sid, int ordinal, int 
     return s.slot_ptr(slot);
 }
 
+/* ---- The lookup that hvq_read_pictures and every member of the export chain share ("The shared picture lookup") ---- */
+
+/* does (sid, ordinal) belong to the batch in flight?  A stream that does not exist has no say: the lookup refuses it afterwards */
+static bool in_flight(const HvqContext *c, int sid, int ordinal)
+{
+    return sid >= 0 && sid < (int)c->streams.size() && ordinal >= c->streams[(size_t)sid].inflight_from;
+}
+
+/* First half of a call.  Pictures of batches that hvq_flush_end has launched are used WITHOUT ending the batch in flight: a streaming
+ * player calls flush_end(k), flush_begin(k + 1), read(k) -- the work on batch k then runs beside the parse of batch k + 1.  Only when
+ * a requested resident picture belongs to the batch in flight is that batch ended first.  Both sides of a call are asked: picture i
+ * unless the caller's memory stands in for it (`src[i]`), and reference i when it names a stream; `src` and `ref` may be NULL. */
+static int chain_begin(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, const HvqMetricsRef *ref)
+{
+    HIPCHK(hipSetDevice(c->device));
+    for (int i = 0; i < n; ++i)
+        if ((!(src && src[i]) && in_flight(c, streams[i], ordinals[i])) || (ref && ref[i].stream >= 0 && in_flight(c, ref[i].stream, ref[i].ordinal)))
+            return flush_end(c);
+    return HVQ_OK;
+}
+
+/* Picture i of a call -> *a: the caller's memory (`src[i]`: a multiple of 16, laid out as the pictures of streams[i] are, ordinal -1)
+ * or the resident picture (streams[i], ordinals[i]).  Called once per picture, where the entry point's loop reaches it: the first
+ * fault in picture order is the one a call reports. */
+static int picture_source(HvqContext *c, int i, const int *streams, const int *ordinals, const void *const *src, const uint8_t **a)
+{
+    int rc = HVQ_OK;
+    if (src && src[i]) {
+        if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+        if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
+        if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
+        *a = (const uint8_t *)src[i];
+    } else {
+        *a = resident_picture(c, streams[i], ordinals[i], &rc);
+    }
+    return rc;
+}
+
+/* Reference i of a call (`r`, NULL when the call has none) against a picture of stream `sid` -> *b: a resident picture of the same
+ * geometry (r->stream >= 0, no pointer), the caller's memory (stream -1, a pointer that is a multiple of 16) or nullptr (stream -1, no
+ * pointer: zeros).  A call that takes no zeros (`zeros_ok` false) refuses a nullptr itself, in its own words. */
+static int picture_reference(HvqContext *c, int i, int sid, const HvqMetricsRef *r, bool zeros_ok, const uint8_t **b)
+{
+    *b = nullptr;
+    if (!r) return HVQ_OK;
+    if (r->stream >= 0) {
+        if (r->ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, r->stream);
+        int rc = HVQ_OK;
+        *b = resident_picture(c, r->stream, r->ordinal, &rc);
+        if (!*b) return rc;
+        const Stream &s = c->streams[(size_t)sid], &t = c->streams[(size_t)r->stream];
+        if (t.w != s.w || t.h != s.h || t.wshift != s.wshift || t.hshift != s.hshift)
+            return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
+                        r->stream, t.w, t.h, t.wshift, t.hshift, sid, s.w, s.h, s.wshift, s.hshift);
+    } else if (r->stream != -1) {
+        return zeros_ok ? fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory or zeros)", i, r->stream)
+                        : fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, r->stream);
+    } else if (r->ptr) {
+        if ((uintptr_t)r->ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
+        *b = (const uint8_t *)r->ptr;
+    }
+    return HVQ_OK;
+}
+
+/* Layout of the jobs whose workgroups take `chunk` consecutive 16-byte units of ONE plane (metrics, checksums, histograms): planes of
+ * ny, nc, nc bytes one behind the other; wg_first[0] is 0 already (the job was zeroed), wg_first[3] comes out as the picture's workgroups */
+static void plane_layout(size_t ny, size_t nc, uint32_t chunk, uint32_t plane_off[3], uint32_t units[3], uint32_t wg_first[4])
+{
+    const size_t len[3] = { ny, nc, nc };
+    size_t off = 0;
+    for (int p = 0; p < 3; ++p) {
+        plane_off[p] = (uint32_t)off;
+        units[p] = (uint32_t)(len[p] / 16u);
+        wg_first[p + 1] = wg_first[p] + (units[p] + chunk - 1u) / chunk;
+        off += len[p];
+    }
+}
+
+/* The context's own scratch of one kind of call (ck_acc, jp_scr, ph_acc), reused by every such call: the chain orders the calls.  When
+ * `need` elements of `elem` bytes exceed it, the chain is drained (an earlier call may still use the buffer that goes) and the buffer
+ * comes back at twice the need, a multiple of `align` elements and `limit` at the most (a `limit` never below the need). */
+template <class T>
+static int scratch_grow(HvqContext *c, T **buf, size_t *cap, size_t need, size_t align, size_t limit = SIZE_MAX)
+{
+    if (need <= *cap) return HVQ_OK;
+    { int rc = export_drain(c); if (rc) return rc; }
+    if (*buf) { HIPCHK(hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    const size_t ncap = std::min(align_up(need * 2, align), limit);
+    HIPCHK(hipMalloc((void **)buf, ncap * sizeof(T)));
+    *cap = ncap;
+    return HVQ_OK;
+}
+
+/* is this a geometry the library decodes, and so one whose pictures it handles?  (a parser's tables are the check) */
+static int geometry_supported(int width, int height, int h_samp, int v_samp)
+{
+    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
+    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
+    hvq_parser_destroy(p);
+    return HVQ_OK;
+}
+
 HVQ_EXPORT int hvq_read_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, void *const *dst)
 {
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    /* Pictures of batches that hvq_flush_end has launched are read WITHOUT ending the batch in flight: a streaming player calls
-     * flush_end(k), flush_begin(k + 1), read(k) -- the copies of batch k then run beside the parse of batch k + 1.  Only when a
-     * requested picture belongs to the batch in flight is that batch ended first. */
-    bool need_end = false;
-    for (int i = 0; i < n && !need_end; ++i)
-        if (streams[i] >= 0 && streams[i] < (int)c->streams.size() && ordinals[i] >= c->streams[(size_t)streams[i]].inflight_from) need_end = true;
-    if (need_end) { int rc = flush_end(c); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, nullptr); if (rc) return rc; }
     /* all copies are queued on the read stream behind the launches of the last ended batch (the event flush_end recorded); ONE
      * wait at the end */
     HIPCHK(hipStreamWaitEvent(c->read_stream, c->ev_read, 0));
@@ -2339,18 +2434,8 @@ HVQ_EXPORT int hvq_picture_device_ptr(HvqContext *c, int sid, int ordinal, const
     return rc;
 }
 
-/* What the two exports share, first half: the batch in flight is ended only when a requested picture belongs to it (as
- * hvq_read_pictures) */
-static int export_begin(HvqContext *c, int n, const int *streams, const int *ordinals)
-{
-    HIPCHK(hipSetDevice(c->device));
-    bool need_end = false;
-    for (int i = 0; i < n && !need_end; ++i)
-        if (streams[i] >= 0 && streams[i] < (int)c->streams.size() && ordinals[i] >= c->streams[(size_t)streams[i]].inflight_from) need_end = true;
-    return need_end ? flush_end(c) : HVQ_OK;
-}
-
-/* ... second half, once everything is checked: from here on the call enqueues.  The job table the export K calls ago used is free
+/* What the members of the export chain share, second half (chain_begin is the first), once everything is checked: from here on the
+ * call enqueues.  The job table the export K calls ago used is free
  * once that export has run (a host wait only when K exports are still queued); `launch(table in device memory, stream)` queues the
  * kernel behind the table's upload, the reconstruction of every flushed picture and the previous export */
 template <class Launch>
@@ -2388,13 +2473,12 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
     if (format != HVQ_FMT_RGB24 && format != HVQ_FMT_RGBP && format != HVQ_FMT_YUV444P) return fail(HVQ_E_ARG, "bad format %d", format);
     if (!n) return HVQ_OK;
-    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, nullptr); if (rc) return rc; }
     std::vector<HvqRgbJob> jobs((size_t)n);
     int max_lanes = 0, wide = 1;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!src) return rc;
+        const uint8_t *src = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &src); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const int64_t dense = format == HVQ_FMT_RGB24 ? (int64_t)s.w * 3 : (int64_t)s.w;
         const int64_t rp = dst[i].row_pitch ? dst[i].row_pitch : dense;
@@ -2415,9 +2499,9 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
                           [=](const void *tab, hipStream_t st) { return hvq_launch_rgb(tab, n, max_lanes, wide, format, st); });
 }
 
-/* Picture metrics (include/hvqm4_amd.h: the specification): a third member of the export chain.  The pictures of both sides are looked
- * up, and the batch in flight ended, exactly as the exports do it; the memset of the records and the launch go behind the job table
- * on the caller's stream (export_enqueue). */
+/* Picture metrics (include/hvqm4_amd.h: the specification): a third member of the export chain.  chain_begin over both sides of every
+ * pair, picture_source and picture_reference per pair (zeros are a reference here); the memset of the records and the launch go behind
+ * the job table on the caller's stream (export_enqueue). */
 HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                                    uint64_t *out, void *hip_stream)
 {
@@ -2426,47 +2510,21 @@ HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, con
     if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
     if (!n) return HVQ_OK;
     if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
-    /* both sides of every pair decide whether the batch in flight has to end */
-    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
-    for (int i = 0; ref && i < n; ++i)
-        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
-    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, ref); if (rc) return rc; }
     std::vector<HvqMetricsJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!a) return rc;
+        const uint8_t *a = nullptr, *b = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
+        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, true, &b); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
-        const uint8_t *b = nullptr;
-        if (ref && ref[i].stream >= 0) {
-            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
-            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
-            if (!b) return rc;
-            const Stream &r = c->streams[(size_t)ref[i].stream];
-            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
-                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
-                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
-        } else if (ref && ref[i].stream != -1) {
-            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory or zeros)", i, ref[i].stream);
-        } else if (ref && ref[i].ptr) {
-            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
-            b = (const uint8_t *)ref[i].ptr;
-        }
         const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
         if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
         HvqMetricsJob &j = jobs[(size_t)i];
         memset(&j, 0, sizeof j);
         j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 12u);
-        const size_t len[3] = { ny, nc, nc };
-        size_t off = 0;
-        for (int p = 0; p < 3; ++p) {
-            j.plane_off[p] = (uint32_t)off;
-            j.units[p] = (uint32_t)(len[p] / 16u);
-            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_MT_CHUNK - 1u) / HVQ_MT_CHUNK;
-            off += len[p];
-        }
+        plane_layout(ny, nc, HVQ_MT_CHUNK, j.plane_off, j.units, j.wg_first);
         max_wgs = std::max(max_wgs, j.wg_first[3]);
     }
     if (!hvq_launch_metrics) return fail(HVQ_E_NOGPU, "this build of the library has no metrics kernel (hvq_metrics.hip is not linked)");
@@ -2480,9 +2538,7 @@ HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, con
 /* Windows of SSIM per plane (include/hvqm4_amd.h): host only */
 HVQ_EXPORT int hvq_ssim_windows(int width, int height, int h_samp, int v_samp, int32_t dims[3][2])
 {
-    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
-    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
-    hvq_parser_destroy(p);
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
     const int cw = width >> (h_samp == 2), ch = height >> (v_samp == 2);
     const int w[3] = { width, cw, cw }, h[3] = { height, ch, ch };
     int total = 0;
@@ -2494,8 +2550,9 @@ HVQ_EXPORT int hvq_ssim_windows(int width, int height, int h_samp, int v_samp, i
     return total;
 }
 
-/* Windowed SSIM (include/hvqm4_amd.h: the specification): a fourth member of the export chain, hvq_picture_metrics' lookup, refusals and
- * ordering; the memset of the records and the launch go behind the job table on the caller's stream (export_enqueue). */
+/* Windowed SSIM (include/hvqm4_amd.h: the specification): a fourth member of the export chain: chain_begin over both sides of every
+ * pair, picture_source and picture_reference per pair, zeros refused here; the memset of the records and the launch go behind the job
+ * table on the caller's stream (export_enqueue). */
 HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                                 int64_t *out, float *const *maps, void *hip_stream)
 {
@@ -2506,35 +2563,15 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
     if (!ref) return fail(HVQ_E_ARG, "SSIM needs a reference for every picture (ref is NULL)");
     for (int i = 0; maps && i < n; ++i)
         if ((uintptr_t)maps[i] & 3u) return fail(HVQ_E_ARG, "map %d: the pointer must be a multiple of 4", i);
-    /* both sides of every pair decide whether the batch in flight has to end */
-    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
-    for (int i = 0; i < n; ++i)
-        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
-    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, ref); if (rc) return rc; }
     std::vector<HvqSsimJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!a) return rc;
+        const uint8_t *a = nullptr, *b = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
+        { int rc = picture_reference(c, i, streams[i], ref + i, false, &b); if (rc) return rc; }
+        if (!b) return fail(HVQ_E_ARG, "reference %d: SSIM against a picture of zeros means nothing (stream -1 needs a pointer)", i);
         const Stream &s = c->streams[(size_t)streams[i]];
-        const uint8_t *b = nullptr;
-        if (ref[i].stream >= 0) {
-            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
-            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
-            if (!b) return rc;
-            const Stream &r = c->streams[(size_t)ref[i].stream];
-            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
-                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
-                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
-        } else if (ref[i].stream != -1) {
-            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
-        } else if (ref[i].ptr) {
-            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
-            b = (const uint8_t *)ref[i].ptr;
-        } else {
-            return fail(HVQ_E_ARG, "reference %d: SSIM against a picture of zeros means nothing (stream -1 needs a pointer)", i);
-        }
         const uint32_t cw = (uint32_t)(s.w >> s.wshift), ch = (uint32_t)(s.h >> s.hshift);
         const uint32_t w[3] = { (uint32_t)s.w, cw, cw }, h[3] = { (uint32_t)s.h, ch, ch };
         if (((uintptr_t)a | w[0] | w[1] | h[0] | h[1]) & 3u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 4 x 4 blocks", i, streams[i]);
@@ -2563,9 +2600,10 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
                           });
 }
 
-/* Checksums of resident pictures (include/hvqm4_amd.h: the specification): a fifth member of the export chain, hvq_picture_metrics' lookup,
- * refusals and ordering.  The memset of the accumulators and the two launches go behind the job table on the caller's stream
- * (export_enqueue); the accumulators are the context's own, reused by every call: the chain orders the calls. */
+/* Checksums of resident pictures (include/hvqm4_amd.h: the specification): a fifth member of the export chain: chain_begin over the
+ * resident pictures, picture_source with `src` per picture.  The memset of the accumulators and the two launches go behind the job
+ * table on the caller's stream (export_enqueue); the accumulators are the context's own, reused by every call: the chain orders the
+ * calls. */
 HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                      uint64_t *out, void *hip_stream)
 {
@@ -2573,27 +2611,14 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
     if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
     if (!n) return HVQ_OK;
     if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqChecksumJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     size_t known_len[2] = { 0, 0 };                                /* x^(8 len) of the last two plane lengths seen: streams share geometries */
     uint32_t known_x[2] = { HVQ_CRC_ONE, HVQ_CRC_ONE };
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
         if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
@@ -2602,28 +2627,18 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
         memset(&j, 0, sizeof j);
         j.a = (uint64_t)(uintptr_t)a;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 8u);
-        const size_t len[3] = { ny, nc, nc };
-        size_t off = 0;
+        plane_layout(ny, nc, HVQ_CK_CHUNK, j.plane_off, j.units, j.wg_first);
         for (int p = 0; p < 3; ++p) {
-            j.plane_off[p] = (uint32_t)off;
-            j.units[p] = (uint32_t)(len[p] / 16u);
-            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_CK_CHUNK - 1u) / HVQ_CK_CHUNK;
+            const size_t len = p ? nc : ny;
             const int slot = p != 0;
-            if (known_len[slot] != len[p]) { known_len[slot] = len[p]; known_x[slot] = hvq_gf_xpow8(len[p]); }
+            if (known_len[slot] != len) { known_len[slot] = len; known_x[slot] = hvq_gf_xpow8(len); }
             j.xlen[p] = known_x[slot];
-            off += len[p];
         }
         max_wgs = std::max(max_wgs, j.wg_first[3]);
     }
     if (!hvq_launch_checksums) return fail(HVQ_E_NOGPU, "this build of the library has no checksum kernel (hvq_checksum.hip is not linked)");
     const size_t acc_bytes = (size_t)n * 96u;
-    if (acc_bytes > c->ck_cap) {
-        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
-        if (c->ck_acc) { HIPCHK(hipFree(c->ck_acc)); c->ck_acc = nullptr; c->ck_cap = 0; }
-        const size_t ncap = align_up(acc_bytes * 2, 4096);
-        HIPCHK(hipMalloc((void **)&c->ck_acc, ncap));
-        c->ck_cap = ncap;
-    }
+    { int rc = scratch_grow(c, &c->ck_acc, &c->ck_cap, acc_bytes, 4096); if (rc) return rc; }
     uint8_t *acc = c->ck_acc;
     for (int i = 0; i < n; ++i) jobs[(size_t)i].acc = (uint64_t)(uintptr_t)(acc + (size_t)i * 96u);
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqChecksumJob), hip_stream,
@@ -2633,9 +2648,9 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
                           });
 }
 
-/* Histograms of resident pictures (include/hvqm4_amd.h: the specification): a sixth member of the export chain, hvq_picture_metrics' lookup,
- * refusals and ordering, hvq_picture_checksums' `src`.  The memset of the records and the launch go behind the job table on the caller's
- * stream (export_enqueue). */
+/* Histograms of resident pictures (include/hvqm4_amd.h: the specification): a sixth member of the export chain: chain_begin over the
+ * resident pictures of both sides, picture_source with `src` and picture_reference per picture, zeros refused here.  The memset of the
+ * records and the launch go behind the job table on the caller's stream (export_enqueue). */
 HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, int mode,
                                       const HvqMetricsRef *ref, uint32_t *out, void *hip_stream)
 {
@@ -2647,46 +2662,15 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
     if (!n) return HVQ_OK;
     if (!out || ((uintptr_t)out & 3u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 4");
     if (mode == HVQ_HIST_ABSDIFF && !ref) return fail(HVQ_E_ARG, "HVQ_HIST_ABSDIFF needs a reference for every picture (ref is NULL)");
-    /* the resident pictures of both sides decide whether the batch in flight has to end; the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i) {
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-        if (ref && ref[i].stream >= 0) { res_s.push_back(ref[i].stream); res_o.push_back(ref[i].ordinal); }
-    }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, ref); if (rc) return rc; }
     std::vector<HvqHistogramJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     for (int i = 0; i < n; ++i) {
-        const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        const uint8_t *a = nullptr, *b = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, false, &b); if (rc) return rc; }
+        if (ref && !b) return fail(HVQ_E_ARG, "reference %d: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)", i);
         const Stream &s = c->streams[(size_t)streams[i]];
-        const uint8_t *b = nullptr;
-        if (ref && ref[i].stream >= 0) {
-            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
-            int rc = HVQ_OK;
-            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
-            if (!b) return rc;
-            const Stream &r = c->streams[(size_t)ref[i].stream];
-            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
-                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
-                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
-        } else if (ref && ref[i].stream != -1) {
-            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
-        } else if (ref && ref[i].ptr) {
-            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
-            b = (const uint8_t *)ref[i].ptr;
-        } else if (ref) {
-            return fail(HVQ_E_ARG, "reference %d: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)", i);
-        }
         const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
         if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
         if (ny / 16u > HVQ_HG_MAX_UNITS) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, streams[i], HVQ_HG_MAX_UNITS);
@@ -2694,14 +2678,7 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
         memset(&j, 0, sizeof j);
         j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 3u * HVQ_HIST_BINS);
-        const size_t len[3] = { ny, nc, nc };
-        size_t off = 0;
-        for (int p = 0; p < 3; ++p) {
-            j.plane_off[p] = (uint32_t)off;
-            j.units[p] = (uint32_t)(len[p] / 16u);
-            j.wg_first[p + 1] = j.wg_first[p] + (j.units[p] + HVQ_HG_CHUNK - 1u) / HVQ_HG_CHUNK;
-            off += len[p];
-        }
+        plane_layout(ny, nc, HVQ_HG_CHUNK, j.plane_off, j.units, j.wg_first);
         max_wgs = std::max(max_wgs, j.wg_first[3]);
     }
     if (!hvq_launch_histograms) return fail(HVQ_E_NOGPU, "this build of the library has no histogram kernel (hvq_histogram.hip is not linked)");
@@ -2715,18 +2692,16 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
 /* Blocks of a motion field (include/hvqm4_amd.h): host only */
 HVQ_EXPORT int hvq_motion_blocks(int width, int height, int h_samp, int v_samp, int block, int32_t dims[2])
 {
-    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
-    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
-    hvq_parser_destroy(p);
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
     if (block != 8 && block != 16) return fail(HVQ_E_ARG, "block %d (8 or 16)", block);
     if (width % block || height % block) return fail(HVQ_E_ARG, "blocks of %d do not tile a %d x %d picture", block, width, height);
     if (dims) { dims[0] = height / block; dims[1] = width / block; }
     return (height / block) * (width / block);
 }
 
-/* Motion fields between resident pictures (include/hvqm4_amd.h: the specification): a seventh member of the export chain,
- * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_ssim's references.  Only the launch goes behind the job table on the
- * caller's stream (export_enqueue): it writes every record, nothing is zeroed in front of it. */
+/* Motion fields between resident pictures (include/hvqm4_amd.h: the specification): a seventh member of the export chain: chain_begin
+ * over both sides of every pair, picture_source and picture_reference per pair, zeros refused here.  Only the launch goes behind the
+ * job table on the caller's stream (export_enqueue): it writes every record, nothing is zeroed in front of it. */
 HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                                   int block, int radius, int32_t *const *out, void *hip_stream)
 {
@@ -2740,35 +2715,15 @@ HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, cons
     if (!ref) return fail(HVQ_E_ARG, "motion needs a reference for every picture (ref is NULL)");
     for (int i = 0; i < n; ++i)
         if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "field %d: the pointer must be a non-null multiple of 16", i);
-    /* both sides of every pair decide whether the batch in flight has to end */
-    std::vector<int> all_s(streams, streams + n), all_o(ordinals, ordinals + n);
-    for (int i = 0; i < n; ++i)
-        if (ref[i].stream >= 0) { all_s.push_back(ref[i].stream); all_o.push_back(ref[i].ordinal); }
-    { int rc = export_begin(c, (int)all_s.size(), all_s.data(), all_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, ref); if (rc) return rc; }
     std::vector<HvqMotionJob> jobs((size_t)n);
     uint32_t max_tiles = 0;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *a = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!a) return rc;
+        const uint8_t *a = nullptr, *b = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
+        { int rc = picture_reference(c, i, streams[i], ref + i, false, &b); if (rc) return rc; }
+        if (!b) return fail(HVQ_E_ARG, "reference %d: motion against a picture of zeros means nothing (stream -1 needs a pointer)", i);
         const Stream &s = c->streams[(size_t)streams[i]];
-        const uint8_t *b = nullptr;
-        if (ref[i].stream >= 0) {
-            if (ref[i].ptr) return fail(HVQ_E_ARG, "reference %d: a pointer together with stream %d (a resident reference takes no pointer)", i, ref[i].stream);
-            b = resident_picture(c, ref[i].stream, ref[i].ordinal, &rc);
-            if (!b) return rc;
-            const Stream &r = c->streams[(size_t)ref[i].stream];
-            if (r.w != s.w || r.h != s.h || r.wshift != s.wshift || r.hshift != s.hshift)
-                return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
-                            ref[i].stream, r.w, r.h, r.wshift, r.hshift, streams[i], s.w, s.h, s.wshift, s.hshift);
-        } else if (ref[i].stream != -1) {
-            return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, ref[i].stream);
-        } else if (ref[i].ptr) {
-            if ((uintptr_t)ref[i].ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
-            b = (const uint8_t *)ref[i].ptr;
-        } else {
-            return fail(HVQ_E_ARG, "reference %d: motion against a picture of zeros means nothing (stream -1 needs a pointer)", i);
-        }
         if (s.w % block || s.h % block) return fail(HVQ_E_ARG, "picture %d: blocks of %d do not tile stream %d (%d x %d)", i, block, streams[i], s.w, s.h);
         if ((uintptr_t)a & 15u || s.w >= (int)HVQ_MV_MAX_SIDE || s.h >= (int)HVQ_MV_MAX_SIDE)
             return fail(HVQ_E_ARG, "picture %d: stream %d (%d x %d) is beyond what the motion kernel addresses", i, streams[i], s.w, s.h);
@@ -2790,9 +2745,7 @@ HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, cons
 /* The header and the bound of a JPEG file (include/hvqm4_amd.h): host only */
 static int jpeg_geometry(int width, int height, int h_samp, int v_samp)
 {
-    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
-    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
-    hvq_parser_destroy(p);
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
     if (width >= (int)HVQ_JP_MAX_SIDE || height >= (int)HVQ_JP_MAX_SIDE || hvq_jpeg_bound_of((uint32_t)width, (uint32_t)height, (uint32_t)h_samp, (uint32_t)v_samp) >> 32)
         return fail(HVQ_E_GEOMETRY, "%d x %d is beyond what a JPEG file of this library holds", width, height);
     return HVQ_OK;
@@ -2817,10 +2770,10 @@ HVQ_EXPORT size_t hvq_jpeg_bound(int width, int height, int h_samp, int v_samp)
     return (size_t)hvq_jpeg_bound_of((uint32_t)width, (uint32_t)height, (uint32_t)h_samp, (uint32_t)v_samp);
 }
 
-/* Baseline JPEG files of resident pictures (include/hvqm4_amd.h: the specification): an eighth member of the export chain,
- * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_checksums' `src`.  The three launches go behind the job table on the
- * caller's stream (export_enqueue); the table carries the call's quantisers and one header per distinct geometry behind the jobs; the
- * scratch is the context's own, reused by every call: the chain orders the calls. */
+/* Baseline JPEG files of resident pictures (include/hvqm4_amd.h: the specification): an eighth member of the export chain: chain_begin
+ * over the resident pictures, picture_source with `src` per picture.  The three launches go behind the job table on the caller's
+ * stream (export_enqueue); the table carries the call's quantisers and one header per distinct geometry behind the jobs; the scratch
+ * is the context's own, reused by every call: the chain orders the calls. */
 HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, int quality,
                                void *const *out, const uint64_t *cap, uint64_t *lengths, void *hip_stream)
 {
@@ -2835,11 +2788,7 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
         if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "file %d: the pointer must be a non-null multiple of 16", i);
         if (cap[i] < HVQ_JPEG_HEADER_BYTES + 2u) return fail(HVQ_E_ARG, "file %d: %llu bytes hold not even the header and EOI (%u)", i, (unsigned long long)cap[i], HVQ_JPEG_HEADER_BYTES + 2u);
     }
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     const size_t quant_off = (size_t)n * sizeof(HvqJpegJob), hdr0 = quant_off + sizeof(HvqJpegQuant);
     std::vector<uint8_t> table(hdr0);
     std::vector<uint32_t> geoms;                                        /* w, h, hs << 4 | vs of every header in the table */
@@ -2847,16 +2796,7 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
     size_t scr_dwords = 0;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const uint32_t hs = 1u << s.wshift, vs = 1u << s.hshift;
         if (((uintptr_t)a & 15u) || s.w % 8 || s.h % 8 || s.w >= (int)HVQ_JP_MAX_SIDE || s.h >= (int)HVQ_JP_MAX_SIDE || hs > 2u || vs > 2u ||
@@ -2886,22 +2826,16 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
         for (int k = 0; k < 64; ++k) qt.q[t][k] = hvq_jpeg_qpack(hvq_jpeg_q(HVQ_JPEG_QBASE[t][k], quality));
     memcpy(table.data() + quant_off, &qt, sizeof qt);
     if (!hvq_launch_jpeg) return fail(HVQ_E_NOGPU, "this build of the library has no JPEG kernels (hvq_jpeg.hip is not linked)");
-    if (scr_dwords > c->jp_cap) {
-        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
-        if (c->jp_scr) { HIPCHK(hipFree(c->jp_scr)); c->jp_scr = nullptr; c->jp_cap = 0; }
-        const size_t ncap = align_up(scr_dwords * 2, 1024);
-        HIPCHK(hipMalloc((void **)&c->jp_scr, ncap * sizeof(uint32_t)));
-        c->jp_cap = ncap;
-    }
+    { int rc = scratch_grow(c, &c->jp_scr, &c->jp_cap, scr_dwords, 1024); if (rc) return rc; }
     uint32_t *scr = c->jp_scr;
     return export_enqueue(c, table.data(), table.size(), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_jpeg(tab, n, max_mh, (uint32_t)quant_off, scr, st); });
 }
 
-/* Perceptual hashes of resident pictures (include/hvqm4_amd.h: the specification): a ninth member of the export chain,
- * hvq_picture_checksums' lookup, refusals, `src` and ordering.  The memset of the cells and the two launches go behind the job table on
- * the caller's stream (export_enqueue), HVQ_PH_BATCH pictures a launch pair: the cells are the context's own, reused by every pair and
- * every call -- the stream orders the pairs, the chain the calls. */
+/* Perceptual hashes of resident pictures (include/hvqm4_amd.h: the specification): a ninth member of the export chain: chain_begin
+ * over the resident pictures, picture_source with `src` per picture.  The memset of the cells and the two launches go behind the job
+ * table on the caller's stream (export_enqueue), HVQ_PH_BATCH pictures a launch pair: the cells are the context's own, reused by every
+ * pair and every call -- the stream orders the pairs, the chain the calls. */
 #ifndef HVQ_PH_CPW
 #define HVQ_PH_CPW HVQ_PH_MAX_CPW      /* most row cells of a workgroup (measurements: 1, 2, 4) */
 #endif
@@ -2912,25 +2846,12 @@ HVQ_EXPORT int hvq_picture_hashes(HvqContext *c, int n, const int *streams, cons
     if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
     if (!n) return HVQ_OK;
     if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqHashJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         if (((uintptr_t)a & 15u) || (s.w & 7) || (s.h & 7) || s.w < 8 || s.h < 8 || s.w > (int)HVQ_PH_MAX_SIDE || s.h > (int)HVQ_PH_MAX_SIDE)
             return fail(HVQ_E_ARG, "picture %d: stream %d (%d x %d) is beyond what the hash kernels address", i, streams[i], s.w, s.h);
@@ -2952,13 +2873,7 @@ HVQ_EXPORT int hvq_picture_hashes(HvqContext *c, int n, const int *streams, cons
     if (!hvq_launch_hashes) return fail(HVQ_E_NOGPU, "this build of the library has no hash kernels (hvq_phash.hip is not linked)");
     const size_t cell_bytes = (size_t)HVQ_PH_CELLS * 8u;
     const size_t acc_bytes = (size_t)std::min(n, (int)HVQ_PH_BATCH) * cell_bytes;
-    if (acc_bytes > c->ph_cap) {
-        { int rc = export_drain(c); if (rc) return rc; }          /* an earlier call may still use the buffer that goes */
-        if (c->ph_acc) { HIPCHK(hipFree(c->ph_acc)); c->ph_acc = nullptr; c->ph_cap = 0; }
-        const size_t ncap = std::min(align_up(acc_bytes * 2, 4096), align_up((size_t)HVQ_PH_BATCH * cell_bytes, 4096));
-        HIPCHK(hipMalloc((void **)&c->ph_acc, ncap));
-        c->ph_cap = ncap;
-    }
+    { int rc = scratch_grow(c, &c->ph_acc, &c->ph_cap, acc_bytes, 4096, align_up((size_t)HVQ_PH_BATCH * cell_bytes, 4096)); if (rc) return rc; }
     uint8_t *acc = c->ph_acc;
     for (int i = 0; i < n; ++i) jobs[(size_t)i].acc = (uint64_t)(uintptr_t)(acc + (size_t)(i % (int)HVQ_PH_BATCH) * cell_bytes);
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqHashJob), hip_stream,
@@ -2997,21 +2912,13 @@ HVQ_EXPORT int hvq_hash_nearest(HvqContext *c, const uint64_t *q, int nq, int q_
     return HVQ_OK;
 }
 
-/* Scaled copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a tenth member of the export chain,
- * hvq_picture_metrics' lookup, refusals and ordering, hvq_picture_checksums' `src`.  Three jobs a picture, one per plane; one launch
+/* Scaled copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a tenth member of the export chain:
+ * chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane; one launch
  * behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no
  * memset. */
-static int scale_geometry(int width, int height, int h_samp, int v_samp)
-{
-    HvqParser *p = hvq_parser_create(width, height, h_samp, v_samp, 1);
-    if (!p) return fail(HVQ_E_GEOMETRY, "unsupported geometry %dx%d sampling %dx%d", width, height, h_samp, v_samp);
-    hvq_parser_destroy(p);
-    return HVQ_OK;
-}
-
 HVQ_EXPORT int64_t hvq_scale_bytes(int width, int height, int h_samp, int v_samp)
 {
-    { int rc = scale_geometry(width, height, h_samp, v_samp); if (rc) return rc; }
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
     return (int64_t)width * height + 2 * (int64_t)(width >> (h_samp == 2)) * (height >> (v_samp == 2));
 }
 
@@ -3040,11 +2947,7 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
     if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
     if (!n) return HVQ_OK;
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqScaleJob> jobs((size_t)n * 3u);
     uint32_t max_tiles = 0;
     /* a call usually repeats few shapes: the geometry check (a parser's tables) and the multipliers of a plane are kept from the picture before */
@@ -3053,21 +2956,12 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
     memset(last, 0, sizeof last);
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqScaleDst &d = dst[i];
         if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
         if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
-            int rc = scale_geometry(d.width, d.height, d.h_samp, d.v_samp);
+            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
             if (rc) return rc;
             seen = d;
         }
@@ -3110,10 +3004,10 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
                           [=](const void *tab, hipStream_t st) { return hvq_launch_scale(tab, n, max_tiles, st); });
 }
 
-/* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): an eleventh member of the export chain,
- * hvq_scale_pictures' lookup, refusals and ordering.  Three jobs a picture, one per plane, and behind them the table of the planes'
- * filters with the taps widened to dwords; one launch behind that upload on the caller's stream (export_enqueue).  Nothing but the
- * destinations is written: no scratch memory, no memset. */
+/* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): an eleventh member of the export
+ * chain: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane, and
+ * behind them the table of the planes' filters with the taps widened to dwords; one launch behind that upload on the caller's stream
+ * (export_enqueue).  Nothing but the destinations is written: no scratch memory, no memset. */
 static int filter_plane_check(const HvqPlaneFilter &p, const char *plane)
 {
     if (p.terms != 1 && p.terms != 2) return fail(HVQ_E_ARG, "%s filter: %d terms (1 or 2)", plane, p.terms);
@@ -3178,11 +3072,7 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
     if (!n) return HVQ_OK;
     if (nfilters < 1 || nfilters > HVQ_FLT_MAX_FILTERS) return fail(HVQ_E_ARG, "%d filters: one call takes 1 .. %d", nfilters, HVQ_FLT_MAX_FILTERS);
     for (int f = 0; f < nfilters; ++f) { int rc = hvq_filter_check(filters + f); if (rc) return rc; }
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     const size_t job_bytes = (size_t)n * 3u * sizeof(HvqFilterJob), tab_bytes = (size_t)nfilters * 2u * sizeof(HvqFilterPlaneDev);
     std::vector<uint8_t> up(job_bytes + tab_bytes);
     HvqFilterJob *jobs = (HvqFilterJob *)up.data();
@@ -3196,16 +3086,7 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
     uint32_t max_tiles = 0;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
         const int f = which ? which[i] : 0;
@@ -3229,10 +3110,10 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
                           [=](const void *t, hipStream_t st) { return hvq_launch_filter(t, n, max_tiles, st); });
 }
 
-/* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain,
- * hvq_scale_pictures' lookup, refusals and ordering.  Three jobs a picture, one per plane, each with the plane's own inverse map; one
- * launch behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no
- * memset. */
+/* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain:
+ * chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane, each with the
+ * plane's own inverse map; one launch behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is
+ * written: no scratch memory, no memset. */
 HVQ_EXPORT int hvq_warp_check(const HvqWarp *w)
 {
     if (!w) return fail(HVQ_E_ARG, "bad arguments");
@@ -3271,31 +3152,18 @@ HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const
     if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
     if (!n) return HVQ_OK;
     for (int i = 0; i < n; ++i) { int rc = hvq_warp_check(warps + i); if (rc) return rc; }
-    /* the resident pictures decide whether the batch in flight has to end; a picture in the caller's memory has no say */
-    std::vector<int> res_s, res_o;
-    for (int i = 0; i < n; ++i)
-        if (!(src && src[i])) { res_s.push_back(streams[i]); res_o.push_back(ordinals[i]); }
-    { int rc = export_begin(c, (int)res_s.size(), res_s.data(), res_o.data()); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqWarpJob> jobs((size_t)n * 3u);
     uint32_t max_tiles = 0;
     HvqWarpDst seen{};                                  /* a call usually repeats few shapes: the geometry check (a parser's tables) is kept from the picture before */
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
-        if (src && src[i]) {
-            if (streams[i] < 0 || streams[i] >= (int)c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
-            if (ordinals[i] != -1) return fail(HVQ_E_ARG, "picture %d: a pointer together with ordinal %d (the caller's memory takes ordinal -1)", i, ordinals[i]);
-            if ((uintptr_t)src[i] & 15u) return fail(HVQ_E_ARG, "picture %d: the pointer must be a multiple of 16", i);
-            a = (const uint8_t *)src[i];
-        } else {
-            int rc = HVQ_OK;
-            a = resident_picture(c, streams[i], ordinals[i], &rc);
-            if (!a) return rc;
-        }
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqWarpDst &d = dst[i];
         if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
         if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
-            int rc = scale_geometry(d.width, d.height, d.h_samp, d.v_samp);
+            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
             if (rc) return rc;
             seen = d;
         }
@@ -3365,15 +3233,14 @@ HVQ_EXPORT int hvq_export_tensors(HvqContext *c, int n, const int *streams, cons
         nm.mul[k] = mul[k]; nm.add[k] = add[k];
     }
     if (!n) return HVQ_OK;
-    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, nullptr); if (rc) return rc; }
     const int64_t es = dtype == HVQ_T_F32 ? 4 : 2;
     const int run = (int)(16 / es);                          /* output samples of a row per lane */
     std::vector<HvqTensorJob> jobs((size_t)n);
     int max_lanes = 0;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!src) return rc;
+        const uint8_t *src = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &src); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqTensorDst &d = dst[i];
         if (!d.ptr) return fail(HVQ_E_ARG, "null destination %d", i);
@@ -3514,7 +3381,7 @@ HVQ_EXPORT int hvq_export_resampled(HvqContext *c, int n, const int *streams, co
         nm.mul[k] = mul[k]; nm.add[k] = add[k];
     }
     if (!n) return HVQ_OK;
-    { int rc = export_begin(c, n, streams, ordinals); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, nullptr, nullptr); if (rc) return rc; }
     const int64_t es = dtype == HVQ_T_F32 ? 4 : 2;
     const int run = (int)(16 / es);
     /* the upload: n job records, then every distinct (n_src, n_out) axis table once -- first[n_out], start[n_out + 1], weights, padded to
@@ -3545,14 +3412,12 @@ HVQ_EXPORT int hvq_export_resampled(HvqContext *c, int n, const int *streams, co
     };
     int max_wgs = 0;
     for (int i = 0; i < n; ++i) {
-        int rc = HVQ_OK;
-        const uint8_t *src = resident_picture(c, streams[i], ordinals[i], &rc);
-        if (!src) return rc;
+        const uint8_t *src = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, nullptr, &src); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqTensorDst &d = dst[i];
         TensorGeom g;
-        rc = tensor_dst_check(s, d, i, es, &g);
-        if (rc) return rc;
+        { int rc = tensor_dst_check(s, d, i, es, &g); if (rc) return rc; }
         const int tx = axis(g.cw, d.out_w), ty = tx < 0 ? -1 : axis(g.ch, d.out_h);
         if (tx < 0 || ty < 0) return fail(HVQ_E_OVERFLOW, "the weight tables of the call exceed 2 GiB");
         const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);

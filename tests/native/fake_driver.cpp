@@ -13,68 +13,19 @@
  *   X <export pictures asked for> <export pictures logged>
  * The caller-side resources of the exports (a stream, destination memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
-#include "fake_device.h"
+#define DRIVER_NAME "fake_driver"
+#include "fake_driver_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/hvqm4_amd.h"
-
-struct Pic { int type; const uint8_t *p; size_t len; };
-struct Clip {
-    std::string name;
-    std::vector<uint8_t> data;
-    HvqH4mInfo info;
-    std::vector<Pic> pics;
-};
-
-static std::string g_golden, g_out;
-static FILE *g_res, *g_bin;
+static FILE *g_bin;
 static size_t g_bin_off = 0;
-static std::map<std::string, Clip> g_clips;
 struct Asked { std::string clip; int ordinal; std::string label; };
 static std::vector<std::vector<Asked>> g_exports;              /* per export call, in call order */
-
-#define CHECK(expr) do { const int rc_ = (expr); if (rc_ < 0) { fprintf(stderr, "fake_driver: %s = %d: %s\n", #expr, rc_, hvq_last_error_string()); exit(3); } } while (0)
 
 static uint64_t fnv1a(const uint8_t *p, size_t n)
 {
     uint64_t h = 0xcbf29ce484222325ull;
     for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
     return h;
-}
-
-static const Clip &clip(const std::string &name)
-{
-    auto it = g_clips.find(name);
-    if (it != g_clips.end()) return it->second;
-    Clip &c = g_clips[name];
-    c.name = name;
-    const std::string path = g_golden + "/" + name + ".h4m";
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "fake_driver: cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    c.data.resize((size_t)ftell(f));
-    fseek(f, 0, SEEK_SET);
-    if (fread(c.data.data(), 1, c.data.size(), f) != c.data.size()) exit(2);
-    fclose(f);
-    CHECK(hvq_h4m_header(c.data.data(), c.data.size(), &c.info));
-    HvqH4mIter it2;
-    hvq_h4m_begin(&it2);
-    int type; uint32_t disp; const uint8_t *p; size_t len;
-    while (hvq_h4m_next(c.data.data(), c.data.size(), &it2, &type, &disp, &p, &len) == 1) c.pics.push_back(Pic{ type, p, len });
-    return c;
-}
-
-static int open_stream(HvqContext *ctx, const Clip &c, int extra = 3)
-{
-    const int sid = hvq_stream_open(ctx, c.info.width, c.info.height, c.info.h_samp, c.info.v_samp, c.info.is_1_5, (int)c.pics.size() + extra);
-    CHECK(sid);
-    return sid;
 }
 
 static void submit_host(HvqContext *ctx, int sid, const Clip &c)
@@ -185,13 +136,6 @@ static void export_pictures(HvqContext *ctx, const std::vector<std::pair<int, co
 }
 
 static void free_exported(Exported *e) { for (void *p : e->mem) (void)hipFree(p); e->mem.clear(); }
-
-static hipStream_t caller_stream()
-{
-    hipStream_t s = nullptr;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) exit(3);
-    return s;
-}
 
 static const char *ALL[] = { "i16", "ip8", "ipb32", "gop64x48_15", "gop64x48_13", "portrait48x64", "portrait152x280", "nest_exact280x152", "wide296x160",
     "weird128x96", "weird64x64", "realistic128x96", "flat128x96", "ragged24x40", "twogops64x48", "natural128x96", "bigshift64x48", "yuv444_64x48",

@@ -14,70 +14,10 @@
  *   S <label> <bytes that still hold the sentinel> <bytes>     an output buffer after refused calls
  * Caller-side resources (a stream, output records, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
-#include "fake_device.h"
+#define DRIVER_NAME "fake_histograms_driver"
+#include "fake_driver_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/hvqm4_amd.h"
-
-struct Pic { int type; const uint8_t *p; size_t len; };
-struct Clip {
-    std::string name;
-    std::vector<uint8_t> data;
-    HvqH4mInfo info;
-    std::vector<Pic> pics;
-};
-
-static std::string g_golden, g_out;
-static FILE *g_res;
-static std::map<std::string, Clip> g_clips;
 static const size_t REC = 3u * HVQ_HIST_BINS;           /* dwords of a record */
-
-#define CHECK(expr) do { const int rc_ = (expr); if (rc_ < 0) { fprintf(stderr, "fake_histograms_driver: %s = %d: %s\n", #expr, rc_, hvq_last_error_string()); exit(3); } } while (0)
-#define HIP(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "fake_histograms_driver: %s failed\n", #expr); exit(3); } } while (0)
-
-static const Clip &clip(const std::string &name)
-{
-    auto it = g_clips.find(name);
-    if (it != g_clips.end()) return it->second;
-    Clip &c = g_clips[name];
-    c.name = name;
-    const std::string path = g_golden + "/" + name + ".h4m";
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "fake_histograms_driver: cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    c.data.resize((size_t)ftell(f));
-    fseek(f, 0, SEEK_SET);
-    if (fread(c.data.data(), 1, c.data.size(), f) != c.data.size()) exit(2);
-    fclose(f);
-    CHECK(hvq_h4m_header(c.data.data(), c.data.size(), &c.info));
-    HvqH4mIter it2;
-    hvq_h4m_begin(&it2);
-    int type; uint32_t disp; const uint8_t *p; size_t len;
-    while (hvq_h4m_next(c.data.data(), c.data.size(), &it2, &type, &disp, &p, &len) == 1) c.pics.push_back(Pic{ type, p, len });
-    return c;
-}
-
-static int decode(HvqContext *ctx, const Clip &c, int extra = 3)
-{
-    const int sid = hvq_stream_open(ctx, c.info.width, c.info.height, c.info.h_samp, c.info.v_samp, c.info.is_1_5, (int)c.pics.size() + extra);
-    CHECK(sid);
-    for (const Pic &p : c.pics) CHECK(hvq_stream_submit(ctx, sid, p.type, p.p, p.len));
-    CHECK(hvq_flush(ctx));
-    return sid;
-}
-
-static hipStream_t caller_stream()
-{
-    hipStream_t s = nullptr;
-    HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    return s;
-}
 
 /* one side of a pair: a resident picture (mem == NULL) or the caller's memory, and what the test is told about it */
 struct Side { int sid, k; const void *mem; const char *form; int kk; };

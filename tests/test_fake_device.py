@@ -57,17 +57,19 @@ SCENARIOS = [
 ]
 
 
-def _build(kind):
-    out = os.path.join(BUILD, "fake_" + kind)
+def build_driver(kind, tag, exe_name, cxx_sources, test_file):
+    """The stand-alone driver `exe_name` of build `kind` (a key of BUILDS) from C_SOURCES and `cxx_sources`, in BUILD/<tag>_<kind>; built
+    again when a source, a header or one of the two test files (this one, and `test_file` of the test that asks) is newer"""
+    out = os.path.join(BUILD, tag + "_" + kind)
     os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "fake_driver")
+    exe = os.path.join(out, exe_name)
     flags = COMMON + BUILDS[kind]
-    deps = C_SOURCES + CXX_SOURCES + [os.path.join(d, f) for d in (CSRC, NATIVE, os.path.join(NATIVE, "fakehip", "hip"), os.path.join(ROOT, "oracle"),
-                                                                  os.path.join(ROOT, "include")) for f in os.listdir(d) if f.endswith(".h")]
-    if os.path.exists(exe) and all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps + [__file__]):
+    dirs = (CSRC, NATIVE, os.path.join(NATIVE, "fakehip", "hip"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "include"))
+    deps = C_SOURCES + cxx_sources + [os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith(".h")]
+    if os.path.exists(exe) and all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps + [test_file, __file__]):
         return exe
     jobs, objs = [], []
-    for src in C_SOURCES + CXX_SOURCES:
+    for src in C_SOURCES + cxx_sources:
         obj = os.path.join(out, os.path.basename(src) + ".o")
         objs.append(obj)
         cc = ["g++", "-std=c++17"] if src.endswith(".cpp") else ["gcc"]
@@ -81,7 +83,7 @@ def _build(kind):
 
 @pytest.fixture(scope="module")
 def drivers():
-    return {kind: _build(kind) for kind in BUILDS}
+    return {kind: build_driver(kind, "fake", "fake_driver", CXX_SOURCES, __file__) for kind in BUILDS}
 
 
 _oracle, _hash = {}, {}

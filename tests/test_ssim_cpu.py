@@ -193,32 +193,9 @@ def test_the_launch_is_a_weak_reference():
 
 
 # ------------------------------------------------------------------------------------------------- the runtime on the CPU fake device
-def _build(kind):
-    """tests/test_fake_device.py's build of its driver, with this driver's sources"""
-    out = os.path.join(fd.BUILD, "ssim_" + kind)
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "fake_ssim_driver")
-    flags = fd.COMMON + fd.BUILDS[kind]
-    dirs = (fd.CSRC, NATIVE, os.path.join(NATIVE, "fakehip", "hip"), os.path.join(fd.ROOT, "oracle"), os.path.join(fd.ROOT, "include"))
-    deps = fd.C_SOURCES + CXX_SOURCES + [os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith(".h")]
-    if os.path.exists(exe) and all(os.path.getmtime(d) <= os.path.getmtime(exe) for d in deps + [__file__, fd.__file__]):
-        return exe
-    jobs, objs = [], []
-    for src in fd.C_SOURCES + CXX_SOURCES:
-        obj = os.path.join(out, os.path.basename(src) + ".o")
-        objs.append(obj)
-        cc = ["g++", "-std=c++17"] if src.endswith(".cpp") else ["gcc"]
-        jobs.append((src, subprocess.Popen(cc + flags + ["-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for src, p in jobs:
-        log = p.communicate()[0]
-        assert p.returncode == 0, f"{src} ({kind}):\n{log}"
-    subprocess.run(["g++"] + flags + objs + ["-o", exe], check=True)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def drivers():
-    return {kind: _build(kind) for kind in fd.BUILDS}
+    return {kind: fd.build_driver(kind, "ssim", "fake_ssim_driver", CXX_SOURCES, __file__) for kind in fd.BUILDS}
 
 
 def _geometry(name):
