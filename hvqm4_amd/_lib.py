@@ -88,6 +88,14 @@ class HvqWarpDst(C.Structure):                  # a destination of hvq_warp_pict
     _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp")]
 
 
+class HvqComposeLayer(C.Structure):             # include/hvqm4_amd.h: a layer of hvq_compose_pictures, luma samples
+    _fields_ = [(n, C.c_int32) for n in ("mode", "sx", "sy", "w", "h", "dx", "dy")] + [("weight", C.c_int32 * 3)]
+
+
+class HvqComposeDst(C.Structure):               # a target of hvq_compose_pictures: its geometry, its layers, the finish
+    _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "first", "count", "shift")] + [("bias", C.c_int32 * 3)]
+
+
 # every symbol include/hvqm4.h and include/hvqm4_amd.h declare: (restype, argtypes)
 SYMBOLS = {
     "HVQM4InitDecoder": (None, []),
@@ -172,6 +180,9 @@ SYMBOLS = {
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
     "hvq_warp_force_direct": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_compose_check": (C.c_int, [C.c_void_p]),
+    "hvq_compose_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvq_compose_force_general": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_adler32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "hvq_resample_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t,

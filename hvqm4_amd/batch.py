@@ -7,7 +7,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import HVQ_E_ARG, HvqError, HvqScaleDst, HvqStats, HvqWarp, HvqWarpDst, check, lib
+from ._lib import HVQ_E_ARG, HvqComposeDst, HvqComposeLayer, HvqError, HvqScaleDst, HvqStats, HvqWarp, HvqWarpDst, check, lib
 
 # HvqScaleDst as a numpy record: a pointer and eight int32 (width, height, h_samp, v_samp, crop_x, crop_y, crop_w, crop_h)
 _SCALE_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (8,))])
@@ -16,6 +16,9 @@ assert _SCALE_DST.itemsize == C.sizeof(HvqScaleDst)
 _WARP = np.dtype([("m", np.int32, (7,)), ("fill", np.uint8, (4,))])
 _WARP_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (4,))])
 assert _WARP.itemsize == C.sizeof(HvqWarp) == 32 and _WARP_DST.itemsize == C.sizeof(HvqWarpDst) == 24
+# HvqComposeLayer (ten dwords) and HvqComposeDst (a pointer; width, height, h_samp, v_samp, first, count, shift, bias[3]) likewise
+_COMPOSE_DST = np.dtype([("ptr", np.uint64), ("rest", np.int32, (10,))])
+assert C.sizeof(HvqComposeLayer) == 40 and _COMPOSE_DST.itemsize == C.sizeof(HvqComposeDst) == 48
 
 
 class Context:
@@ -701,6 +704,58 @@ class Context:
         a_d["ptr"] = where
         a_d["rest"] = shapes[keys[0]][0] if len(shapes) == 1 else [shapes[k][0] for k in keys]
         check(lib().hvq_warp_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(a_w.ctypes.data), C.c_void_p(a_d.ctypes.data), stream))
+        return out
+
+    def compose_force_general(self, on: bool) -> bool:
+        """hvq_compose_force_general: every later compose_pictures of this context takes the general body of the kernel for every
+        layer (False: the chosen one again) -> the setting before.  The values do not depend on it: for tests that compare the two
+        with =="""
+        return bool(check(lib().hvq_compose_force_general(self._h, int(bool(on)))))
+
+    def compose_pictures(self, sids, ordinals, targets, src=None, out=None):
+        """hvq_compose_pictures: pictures built from layers of the resident pictures (sids[i], ordinals[i]) -- the call's flat list,
+        which compose.Layer.source indexes; a picture that several layers use stands in it once -- with exact integers and one rounding
+        (include/hvqm4_amd.h), IN SLOT LAYOUT (Y | U | V), on torch's current stream, without a host synchronisation and without
+        moving a picture.  `targets`: a list of hvqm4_amd.compose.Target.  -> when every target geometry is the same one uint8 CUDA
+        tensor [len(targets), bytes], otherwise a list of 1-D uint8 CUDA tensors (`out`, if given: of that same form, contiguous,
+        rows 16-byte aligned; it is overwritten whole and must not overlap a source).  Whatever takes src= or ref.ptr takes a row of
+        the result, with an open stream of the target geometry to carry it.  hvqm4_amd.compose builds the targets and gives the
+        expected bytes (of_pictures).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
+        from . import compose as cp
+        from . import scale as sc
+        from .checksums import sources
+        n = Context._pictures(self._geom, sids, ordinals)
+        if not isinstance(targets, (list, tuple)):
+            raise ValueError("targets: a list of compose.Target")
+        nt = len(targets)
+        if nt > 65535:
+            raise ValueError(f"{nt} targets: one call takes 65535 at the most")
+        by_stream = {s: self._geometry(s) for s in set(sids)}
+        geoms = [by_stream[s] for s in sids]
+        source, nums, rows = cp.check_call(targets, geoms)                  # ValueError beyond the library's limits
+        nl = len(source)
+        if nl > cp.MAX_TOTAL:
+            raise ValueError(f"{nl} layers: one call takes {cp.MAX_TOTAL} at the most")
+        pb = {s: self.pic_bytes(s) for s in by_stream}
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        dst_geoms = [tuple(r) for r in rows[:, :4].tolist()]
+        uniform = len(set(dst_geoms)) <= 1
+        nb = [sc.nbytes(*dst_geoms[0])] * nt if uniform and nt else [sc.nbytes(*g) for g in dst_geoms]
+        out, device, where = Context._slot_outputs(out, nb, uniform, "target geometries")
+        if not nt:
+            return out
+        _s, _o, stream = Context._launch_args(device, (), ())
+        # the call's flat arrays: layer l reads picture source[l] of the method's list
+        a_s = np.ascontiguousarray(np.asarray(sids, dtype=np.int32).reshape(n)[source])
+        a_o = np.ascontiguousarray(np.asarray(ordinals, dtype=np.int32).reshape(n)[source])
+        a_p = None if ptrs is None else np.ascontiguousarray(np.array([p or 0 for p in ptrs], dtype=np.uint64).reshape(n)[source])
+        a_l = np.ascontiguousarray(nums)                                     # HvqComposeLayer[nlayers]
+        a_d = np.empty(nt, dtype=_COMPOSE_DST)                               # HvqComposeDst[ntargets]
+        a_d["ptr"] = where
+        a_d["rest"] = rows
+        as_int = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        check(lib().hvq_compose_pictures(self._h, nl, as_int(a_s), as_int(a_o), None if a_p is None else C.c_void_p(a_p.ctypes.data),
+                                         C.c_void_p(a_l.ctypes.data), nt, C.c_void_p(a_d.ctypes.data), stream))
         return out
 
     def _ssim_dims(self, sid):

@@ -627,4 +627,52 @@ _Static_assert(sizeof(HvqWarpJob) == 112, "HvqWarpJob must be 112 bytes");
 #endif
 
 
+/* the compose launch (hvq_compose.hip, hvq_compose_pictures): three HvqComposeJob a target, Y, U, V, and behind the jobs of all targets,
+ * in the same upload, three HvqComposeRec a layer, Y, U, V: record 3 l + p is plane p of layer l of the call.  A job names its layers
+ * as the call does: layers first .. first + count - 1, in that order.  `dst` is the target plane, my rows of mx samples, dense (pitch
+ * mx: a multiple of 4, as the address is).  A record holds the layer's two rectangles in samples of its plane: the w x h samples whose
+ * first one is (sx, sy) of the source plane (`src`, ny rows of `pitch` samples, dense; pitch a multiple of 4, as the address is) land
+ * at (dx, dy) of the target plane.  Grid row = target; a workgroup of HVQ_CP_LANES lanes takes a tile of HVQ_CP_TW x HVQ_CP_TH targets
+ * of one plane, a lane one dword of it: tiles_x tiles side by side, `tiles` in all; the workgroups of a grid row walk the tiles of Y,
+ * then U, then V, those past them leave.  body HVQ_CP_ALIGNED: dx, w and sx - dx are multiples of 4, a target dword is covered whole or
+ * not at all and takes one aligned source dword.  body HVQ_CP_GENERAL: any offset, a cover mask per byte, the four source bytes from
+ * the two aligned dwords that hold them.  Every member is a dword or a qword (scalar loads). */
+#define HVQ_CP_LANES  256u
+#define HVQ_CP_TW     64u           /* targets a tile is wide: 16 dwords, one store a lane */
+#define HVQ_CP_TH     16u           /* its rows: lane l owns dword l & 15 of row l >> 4 */
+#define HVQ_CP_ALIGNED 0u
+#define HVQ_CP_GENERAL 1u
+#define HVQ_CP_PUT    0u            /* HVQ_CMP_PUT */
+#define HVQ_CP_ADD    1u            /* HVQ_CMP_ADD */
+#define HVQ_CP_MAX_GAIN (1 << 22)   /* HVQ_CMP_MAX_GAIN */
+typedef struct HvqComposeJob {
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint32_t mx, my;                   /* target samples: mx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t first, count;             /* the target's layers, in layers of the call */
+    int32_t  shift, half, bias;        /* half = shift ? 1 << (shift - 1) : 0 */
+    uint32_t plane;                    /* 0: Y, 1: U, 2: V: which record of a layer */
+} HvqComposeJob;
+typedef struct HvqComposeRec {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint32_t pitch, ny;                /* the source plane: ny rows of pitch samples, pitch a multiple of 4 */
+    int32_t  sx, sy;                   /* the rectangle's first sample in the source plane */
+    int32_t  dx, dy;                   /* where it lands in the target plane */
+    int32_t  w, h;                     /* its samples, both at least 1 */
+    int32_t  weight;                   /* |weight| <= HVQ_CP_MAX_GAIN */
+    uint32_t mode;                     /* HVQ_CP_PUT or HVQ_CP_ADD */
+    uint32_t body;                     /* HVQ_CP_ALIGNED or HVQ_CP_GENERAL */
+    uint32_t pad[3];
+} HvqComposeRec;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqComposeJob) == 48 && sizeof(HvqComposeRec) == 64, "job tables are uploaded in 16-byte units");
+static_assert(HVQ_CP_TW * HVQ_CP_TH == HVQ_CP_LANES * 4u && HVQ_CP_TW == 64u, "a lane owns one dword of the tile");
+/* |acc| + half <= 255 * 2^22 + 2^21 < 2^31: 32-bit signed arithmetic serves; a weight fits the 24-bit multiplier */
+static_assert((int64_t)255 * HVQ_CP_MAX_GAIN + (HVQ_CP_MAX_GAIN >> 1) < ((int64_t)1 << 31) && HVQ_CP_MAX_GAIN < (1 << 23), "the accumulators are 32 bits");
+#else
+_Static_assert(sizeof(HvqComposeJob) == 48, "HvqComposeJob must be 48 bytes");
+#endif
+
+
 #endif

@@ -44,6 +44,7 @@
 #include "hvq_scale.h"
 #include "hvq_filter.h"
 #include "hvq_warp.h"
+#include "hvq_compose.h"
 
 #ifdef GP_PROBE
 extern "C" hipError_t hvq_launch_parse_probe(const HvqParseJob *jobs_dev, HvqParseResult *results_dev, uint32_t n, uint32_t rowbuf_stride,
@@ -95,6 +96,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_de
 extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_compose(const void *tab_dev, int ntargets, uint32_t max_tiles, hipStream_t stream);
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -381,6 +384,7 @@ struct HvqContext {
      * serves every launch pair and every call, as ck_acc */
     uint8_t *ph_acc = nullptr;
     size_t ph_cap = 0;
+    bool cp_force_general = false;     /* hvq_compose_force_general: every layer plane takes the general body of hvq_compose.hip */
     int wp_force = 0;                  /* hvq_warp_force_direct: 0 the chosen body of hvq_warp.hip, 1 the direct one, 2 the tiled one wherever LDS holds the box */
     bool fl_force_filter = false;      /* hvq_filter_force_filter: identity planes take the filter body of hvq_filter.hip, not the copy body */
     bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
@@ -3188,6 +3192,112 @@ HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const
     if (!hvq_launch_warp) return fail(HVQ_E_NOGPU, "this build of the library has no warp kernel (hvq_warp.hip is not linked)");
     return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqWarpJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_warp(tab, n, max_tiles, st); });
+}
+
+/* Pictures composed of layers of resident pictures, in slot layout (include/hvqm4_amd.h: the specification): a thirteenth member of the
+ * export chain: chain_begin over the flat layer sources, picture_source with `src` per layer.  Three jobs a target, one per plane, and
+ * behind them three records a layer, the rectangles of both sides in samples of the plane; one launch behind that upload on the caller's
+ * stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no memset. */
+HVQ_EXPORT int hvq_compose_check(const HvqComposeLayer *l)
+{
+    if (!l) return fail(HVQ_E_ARG, "bad arguments");
+    if (l->mode != HVQ_CMP_PUT && l->mode != HVQ_CMP_ADD) return fail(HVQ_E_ARG, "layer: mode %d", l->mode);
+    if (l->sx < 0 || l->sy < 0 || l->w < 0 || l->h < 0 || l->dx < 0 || l->dy < 0)
+        return fail(HVQ_E_ARG, "layer: a negative number in %d, %d, %d x %d -> %d, %d", l->sx, l->sy, l->w, l->h, l->dx, l->dy);
+    if (l->w == 0 && (l->sx || l->sy || l->h)) return fail(HVQ_E_ARG, "layer: w == 0 means the whole source and takes sx, sy and h as 0");
+    if (l->w > 0 && l->h == 0) return fail(HVQ_E_ARG, "layer: the rectangle %d x %d is empty", l->w, l->h);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_compose_force_general(HvqContext *c, int on)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = c->cp_force_general ? 1 : 0;
+    c->cp_force_general = on != 0;
+    return was;
+}
+
+HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *streams, const int *ordinals, const void *const *src,
+                                    const HvqComposeLayer *layers, int ntargets, const HvqComposeDst *dst, void *hip_stream)
+{
+    static_assert(HVQ_CMP_PUT == (int)HVQ_CP_PUT && HVQ_CMP_ADD == (int)HVQ_CP_ADD && HVQ_CMP_MAX_GAIN == HVQ_CP_MAX_GAIN && HVQ_CMP_MAX_SHIFT < 31,
+                  "the header's names are the kernel's");
+    if (!c || nlayers < 0 || ntargets < 0 || (nlayers && (!streams || !ordinals || !layers)) || (ntargets && !dst)) return fail(HVQ_E_ARG, "bad arguments");
+    if (ntargets > 65535) return fail(HVQ_E_ARG, "%d targets: one call takes 65535 at the most", ntargets);
+    if (nlayers > HVQ_CMP_MAX_TOTAL) return fail(HVQ_E_ARG, "%d layers: one call takes %d at the most", nlayers, HVQ_CMP_MAX_TOTAL);
+    if (!ntargets) return HVQ_OK;
+    for (int l = 0; l < nlayers; ++l) { int rc = hvq_compose_check(layers + l); if (rc) return rc; }
+    HvqComposeDst seen{};                               /* a call usually repeats few shapes: the geometry check (a parser's tables) is kept from the target before */
+    for (int t = 0; t < ntargets; ++t) {
+        const HvqComposeDst &d = dst[t];
+        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "target %d: the pointer must be a non-null multiple of 16", t);
+        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
+            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
+            if (rc) return rc;
+            seen = d;
+        }
+        if (d.shift < 0 || d.shift > HVQ_CMP_MAX_SHIFT) return fail(HVQ_E_ARG, "target %d: shift %d outside 0 .. %d", t, d.shift, HVQ_CMP_MAX_SHIFT);
+        for (int p = 0; p < 3; ++p)
+            if (d.bias[p] < -255 || d.bias[p] > 255) return fail(HVQ_E_ARG, "target %d: bias %d outside -255 .. 255", t, d.bias[p]);
+        if (d.first < 0 || d.count < 0 || d.first > nlayers || d.count > nlayers - d.first)
+            return fail(HVQ_E_ARG, "target %d: layers %d .. %d + %d of %d", t, d.first, d.first, d.count, nlayers);
+        if (d.count > HVQ_CMP_MAX_LAYERS) return fail(HVQ_E_ARG, "target %d: %d layers, a target takes %d at the most", t, d.count, HVQ_CMP_MAX_LAYERS);
+    }
+    { int rc = chain_begin(c, nlayers, streams, ordinals, src, nullptr); if (rc) return rc; }
+    const size_t job_bytes = (size_t)ntargets * 3u * sizeof(HvqComposeJob), rec_bytes = (size_t)nlayers * 3u * sizeof(HvqComposeRec);
+    std::vector<uint8_t> up(job_bytes + rec_bytes);
+    HvqComposeJob *jobs = (HvqComposeJob *)up.data();
+    HvqComposeRec *recs = (HvqComposeRec *)(up.data() + job_bytes);
+    for (int l = 0; l < nlayers; ++l) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, l, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[l]];
+        const HvqComposeLayer &L = layers[l];
+        const int sx = L.sx, sy = L.sy, w = L.w ? L.w : s.w, h = L.w ? L.h : s.h;
+        if (sx > s.w - w || sy > s.h - h || w > s.w || h > s.h)
+            return fail(HVQ_E_ARG, "layer %d: the rectangle %d, %d, %d x %d leaves the %d x %d source", l, sx, sy, w, h, s.w, s.h);
+        if (((sx | w | L.dx) & ((1 << s.wshift) - 1)) || ((sy | h | L.dy) & ((1 << s.hshift) - 1)))
+            return fail(HVQ_E_ARG, "layer %d: %d, %d, %d x %d -> %d, %d does not lie on the chroma samples of stream %d", l, sx, sy, w, h, L.dx, L.dy, streams[l]);
+        const uint8_t *sp = a;
+        for (int p = 0; p < 3; ++p) {
+            const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0;
+            const uint32_t nx = (uint32_t)(s.w >> xs), ny = (uint32_t)(s.h >> ys);
+            recs[(size_t)l * 3u + (size_t)p] = hvq_cp_rec((uint64_t)(uintptr_t)sp, nx, ny, sx >> xs, sy >> ys, w >> xs, h >> ys, L.dx >> xs, L.dy >> ys,
+                                                          L.weight[p], (uint32_t)L.mode, c->cp_force_general);
+            sp += (size_t)nx * ny;
+        }
+    }
+    uint32_t max_tiles = 0;
+    for (int t = 0; t < ntargets; ++t) {
+        const HvqComposeDst &d = dst[t];
+        const int dws = d.h_samp == 2, dhs = d.v_samp == 2;
+        int64_t gain[3] = { 0, 0, 0 };
+        for (int l = d.first; l < d.first + d.count; ++l) {
+            const Stream &s = c->streams[(size_t)streams[l]];
+            const HvqComposeLayer &L = layers[l];
+            if (s.wshift != dws || s.hshift != dhs)
+                return fail(HVQ_E_ARG, "target %d, layer %d: stream %d has not the target's sampling %d x %d (scale it first)", t, l, streams[l], d.h_samp, d.v_samp);
+            const int w = L.w ? L.w : s.w, h = L.w ? L.h : s.h;
+            if (L.dx > d.width - w || L.dy > d.height - h || w > d.width || h > d.height)
+                return fail(HVQ_E_ARG, "target %d, layer %d: %d x %d at %d, %d leaves the %d x %d target", t, l, w, h, L.dx, L.dy, d.width, d.height);
+            for (int p = 0; p < 3; ++p) gain[p] += L.weight[p] < 0 ? -(int64_t)L.weight[p] : L.weight[p];
+        }
+        for (int p = 0; p < 3; ++p)
+            if (gain[p] > HVQ_CMP_MAX_GAIN) return fail(HVQ_E_ARG, "target %d, plane %d: a gain of %lld (at most %d)", t, p, (long long)gain[p], HVQ_CMP_MAX_GAIN);
+        uint8_t *dp = (uint8_t *)d.ptr;
+        uint32_t tiles = 0;
+        for (int p = 0; p < 3; ++p) {
+            const uint32_t mx = (uint32_t)(d.width >> (p ? dws : 0)), my = (uint32_t)(d.height >> (p ? dhs : 0));
+            HvqComposeJob &j = jobs[(size_t)t * 3u + (size_t)p];
+            j = hvq_cp_job((uint64_t)(uintptr_t)dp, mx, my, (uint32_t)d.first, (uint32_t)d.count, d.shift, d.bias[p], (uint32_t)p);
+            tiles += j.tiles;
+            dp += (size_t)mx * my;
+        }
+        max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!hvq_launch_compose) return fail(HVQ_E_NOGPU, "this build of the library has no compose kernel (hvq_compose.hip is not linked)");
+    return export_enqueue(c, up.data(), up.size(), hip_stream,
+                          [=](const void *tab, hipStream_t st) { return hvq_launch_compose(tab, ntargets, max_tiles, st); });
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -763,6 +763,87 @@ int     hvq_warp_pictures(HvqContext *ctx, int n, const int *streams, const int 
 int     hvq_warp_body(const HvqWarp *w, int dst_h, int dst_v, int src_h, int src_v, int nx, int ny);
 int     hvq_warp_force_direct(HvqContext *ctx, int on);
 
+/* Resident pictures COMPOSED into uint8 pictures of a TARGET GEOMETRY in slot layout: `ntargets` pictures, each built from an ordered
+ * list of LAYERS -- rectangles of resident pictures (or of the caller's device memory), each with a signed integer weight per plane,
+ * that replace (PUT) or join (ADD) what lies below them -- in one kernel launch on the caller's HIP stream and without a host
+ * synchronisation.  Contact sheets, side-by-side and picture-in-picture, cross-fades and temporal averages, difference pictures and
+ * translucent overlays are parameter sets of it (hvqm4_amd.compose builds them).  The result composes like hvq_scale_pictures':
+ * whatever takes `src` or `ref.ptr` takes it.  The values are specified as exact integers: this text is the authority for them.
+ *   Sources.   The sources of all layers are given flat, as every other call takes pictures: layer l reads picture (streams[l],
+ *              ordinals[l]) or the caller's memory src[l] with ordinal -1; a picture used by several layers is repeated.  layers[l]
+ *              holds the layer's numbers.  Target t takes layers[first .. first + count), in this order; ranges of several targets
+ *              may share layers.  A layer's source has the sampling of every target that uses it.
+ *   Values.    Plane p of a target has sampling (hx, vy), (1, 1) for Y.  A layer's rectangles in plane p are its luma numbers divided
+ *              by hx (x numbers) and vy (y numbers), which they must be multiples of: sx_p, sy_p, w_p, h_p, dx_p, dy_p.  For target
+ *              sample (x, y) of the plane, a_l the source of layer l:
+ *              acc = 0
+ *              for l in the target's layers, in order:
+ *                  if dx_p <= x < dx_p + w_p and dy_p <= y < dy_p + h_p:
+ *                      s   = a_l[p][y - dy_p + sy_p][x - dx_p + sx_p]
+ *                      acc = (mode_l == HVQ_CMP_PUT ? 0 : acc) + weight_l[p] * s
+ *              h   = shift ? 1 << (shift - 1) : 0
+ *              out = min(255, max(0, floor((acc + h) / 2^shift) + bias[p]))
+ *              The floor is towards minus infinity (an arithmetic shift): ONE rounding, half up, for negative sums too, the finish of
+ *              hvq_filter_pictures.  Any evaluation order that yields these integers is allowed; no intermediate rounding is.  With
+ *              gain_p = sum over the target's layers of |weight_l[p]| <= HVQ_CMP_MAX_GAIN = 2^22, |acc| + h stays below 255 * 2^22 +
+ *              2^21 < 2^31: 32-bit signed arithmetic serves.  A sample that no layer covers is min(255, max(0, bias[p])): the
+ *              background colour.
+ *   Known answers.  One whole-picture PUT with weight 1 and shift 0 copies the picture, in every sampling.  Two ADDs of weight 1 with
+ *              shift 1 give (a + b + 1) >> 1.  Weights +1 and -1 with bias 128 on equal pictures give 128 everywhere.  The two
+ *              negative ties of the filter text: acc = -1, shift 1 gives 0 and acc = -3, shift 1 gives -1 (before the bias).  A PUT
+ *              above ADDs discards them inside its rectangle only.  count == 0 is a flat picture of the bias.  A translucent overlay
+ *              of alpha a / 256 over a region is PUT base (whole, 256), PUT base (region, 256 - a), ADD overlay (region, a), shift 8:
+ *              (base (256 - a) + overlay a + 128) >> 8 inside the region with one rounding, base outside it.
+ *   layers[l]: mode HVQ_CMP_PUT or HVQ_CMP_ADD.  sx, sy, w, h: the source rectangle in luma samples; w == 0 (then sx == sy == h == 0):
+ *              the whole source.  dx, dy: where its top-left sample lands in the target, in luma samples.  weight[3]: Y, U, V.
+ *   dst[t]:    ptr: a non-null DEVICE pointer, a multiple of 16: Y | U | V tightly packed, the target geometry's slot layout,
+ *              hvq_scale_bytes(width, height, h_samp, v_samp) bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  It must not overlap a source of the call: the
+ *              caller's business, not checked.  width, height, h_samp, v_samp: the target geometry, one that hvq_stream_open accepts
+ *              (else HVQ_E_GEOMETRY).  first, count: its layers; count may be 0.  shift 0 .. HVQ_CMP_MAX_SHIFT; bias[3] -255 .. 255.
+ *   hvq_compose_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL record, a mode outside the two values, a negative sx, sy, w, h, dx
+ *              or dy, w == 0 with another of sx, sy, h not 0, or w > 0 with h == 0.
+ *   Bodies.    A plane of a layer whose dx_p, w_p and sx_p - dx_p are all multiples of 4 takes the kernel's aligned body (one aligned
+ *              source dword per target dword), any other the general body (a cover mask per byte, the bytes from the two aligned
+ *              dwords that hold them).  The values do not depend on it.  hvq_compose_force_general(ctx, 1) makes every later call of
+ *              the context take the general body everywhere (0: the chosen one again) and returns the setting before: for tests that
+ *              compare the two with ==.
+ *   HVQ_E_ARG for the whole call: what hvq_compose_check refuses; a layer of a target whose source sampling is not the target's (scale
+ *              first); a source rectangle that leaves its source or a landing rectangle that leaves the target (nothing is clipped);
+ *              x numbers that are no multiples of h_samp or y numbers that are no multiples of v_samp; a target's gain above
+ *              HVQ_CMP_MAX_GAIN in a plane; shift or bias outside their ranges; first or count negative, first + count above nlayers,
+ *              count above HVQ_CMP_MAX_LAYERS; ntargets above 65535 or nlayers above HVQ_CMP_MAX_TOTAL; a null or misaligned ptr; a
+ *              bad stream or ordinal; a src[l] with an ordinal other than -1 or that is no multiple of 16; a NULL context, dst, or
+ *              (with nlayers > 0) streams, ordinals or layers.  A layer that belongs to no target is checked like any other (against
+ *              its source) but is not read.  ntargets == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is
+ *              enqueued: a refused call leaves every destination untouched.  HVQ_E_NOGPU (after those checks) from a build without
+ *              the compose kernel.
+ *   a_l and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_scale_pictures'. */
+#define HVQ_CMP_PUT 0                /* acc = w * s   : replaces what lies below, inside the layer's rectangle */
+#define HVQ_CMP_ADD 1                /* acc += w * s                                                           */
+#define HVQ_CMP_MAX_LAYERS 256       /* per target: a 16 x 16 contact sheet                                     */
+#define HVQ_CMP_MAX_TOTAL  (1 << 18) /* layers per call                                                         */
+#define HVQ_CMP_MAX_GAIN   (1 << 22) /* per target and plane: sum over its layers of |weight[p]|                */
+#define HVQ_CMP_MAX_SHIFT  22
+typedef struct HvqComposeLayer {
+    int32_t mode;                                 /* HVQ_CMP_PUT or HVQ_CMP_ADD */
+    int32_t sx, sy, w, h;                         /* source rectangle, luma samples; w == 0 (then sx == sy == h == 0): the whole source */
+    int32_t dx, dy;                               /* where its top-left lands in the target, luma samples */
+    int32_t weight[3];                            /* Y, U, V: signed integers */
+} HvqComposeLayer;
+typedef struct HvqComposeDst {
+    void   *ptr;                                  /* device, multiple of 16: Y | U | V tightly packed, hvq_scale_bytes() bytes */
+    int32_t width, height, h_samp, v_samp;        /* target geometry: one that hvq_stream_open accepts */
+    int32_t first, count;                         /* its layers: layers[first .. first + count), in this order; count may be 0 */
+    int32_t shift;                                /* 0 .. HVQ_CMP_MAX_SHIFT */
+    int32_t bias[3];                              /* -255 .. 255 per plane */
+} HvqComposeDst;
+int     hvq_compose_check(const HvqComposeLayer *l);
+int     hvq_compose_pictures(HvqContext *ctx, int nlayers, const int *streams, const int *ordinals, const void *const *src,
+                             const HvqComposeLayer *layers, int ntargets, const HvqComposeDst *dst, void *hip_stream);
+int     hvq_compose_force_general(HvqContext *ctx, int on);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
