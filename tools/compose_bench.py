@@ -1,6 +1,6 @@
 """Composed pictures in slot layout (hvq_compose_pictures) on the GPU: what the kernel costs against the memory it moves and against torch.
 
-Two measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
+Two measurements (steps of tools/benchlib.py):
   calls   128 640x480 4:2:0 streams, 8 resident pictures each, 1024 pictures, on natural content.  The cases: a copy of every picture; the
           cross-fade of every picture with its neighbour; the average of 8 neighbours; the difference of two; a translucent 160x120
           inset at an odd chroma offset (the general body); 64 sheets of 4 x 4 cells of 160x120 from 1024 thumbnails (scale_pictures
@@ -9,22 +9,21 @@ Two measurements, each a child process of this driver under its own `timeout`; a
           writes each picture once, (c) a torch route on a device copy of the same pictures in planar YUV: slices per plane, int32
           tensor arithmetic, clamp, cast, concatenation.  HIP-event timed per call on one stream in alternating rounds after a
           warm-up; medians over the rounds.  (a) must equal hvqm4_amd.compose on targets read back.
-  trace   rocprofv3 --kernel-trace --stats around a child that launches every case and the yardstick in a fixed order, one warm-up and
+  trace   the kernel trace of a child that launches every case and the yardstick in a fixed order, one warm-up and
           `reps` launches each.  Kernel times are read from the trace: median with min-max per case, and per case the multiple of
           `bytes ratio x yardstick` it takes (bytes ratio: the bytes the case reads and writes over the yardstick's).
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from tools.benchlib import (add_common_arguments, cut_by_plan, drive, launch_stats, picture_lists, read_kernel_trace, resident, resources,  # noqa: E402
+                            timed)
 
 W, H = 640, 480
 SRC = (W, H, 2, 2)
@@ -98,25 +97,12 @@ def torch_route(torch, label, copy, thumbs):
     raise ValueError(label)
 
 
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
 def setup(args):
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
-    from scale_bench import resident
     ctx = batch.Context(0)
-    sids = resident(ctx, args.contents.split(",")[0], args.streams, args.per, args.distinct)
-    a_s = [s for s in sids for _ in range(args.per)]
-    a_o = [k for _ in sids for k in range(args.per)]
+    a_s, a_o = picture_lists(resident(ctx, preset=args.contents.split(",")[0], streams=args.streams, per=args.per, distinct=args.distinct), args.per)
     n = len(a_s)
     thumbs = ctx.scale_pictures(a_s, a_o, CELL)
     cell_sid = ctx.open_stream(CELL[0], CELL[1], 2, 2, True, 3)          # never submitted to: it names the geometry of the thumbnails
@@ -199,34 +185,23 @@ def child_trace(args):
     print(json.dumps({"launches": 1 + args.reps, "pictures": len(a_s), "content": args.contents.split(",")[0]}))
 
 
-def trace_summary(trace_dir, plan, calls):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = {"hvq_compose_kernel": [], "hvq_scale_kernel": []}
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = (row.get("Kernel_Name") or row.get("Name") or "").split("(")[0].strip()
-            name = name[:-3] if name.endswith(".kd") else name
-            k = name.split(" ")[-1]
-            if k in rows:
-                rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), row.get("VGPR_Count"), row.get("LDS_Block_Size"),
-                                row.get("Scratch_Size")))
+def trace_summary(trace_dir, plan, earlier=None):
+    calls = (earlier or {}).get("calls")
     per = plan["launches"]
-    ck, sc = sorted(rows["hvq_compose_kernel"]), sorted(rows["hvq_scale_kernel"])
-    sc = sc[-per:]                                                                    # the thumbnails of the set-up come first
-    if len(ck) != per * len(CASES) or len(sc) != per:
-        return {"error": f"{len(ck)} compose and {len(sc)} scale launches in the trace, {per * len(CASES)} and {per} planned"}
-
-    def stats(r):
-        d = sorted(x[1] for x in r[1:])                                               # without the warm-up launch
-        return {"launches": len(d), "median_us": round(statistics.median(d) / 1e3, 1), "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1)}
-
-    res = {"pictures": plan["pictures"], "content": plan["content"], "vgprs": ck[0][2], "lds": ck[0][3], "scratch": ck[0][4], "cases": {}}
-    yard = stats(sc)
+    launches = read_kernel_trace(trace_dir, ("hvq_compose_kernel", "hvq_scale_kernel"))
+    if isinstance(launches, dict):
+        return launches
+    blocks = [(label, "hvq_compose_kernel", per) for label, _f, _u in CASES] + [("hvq_scale_kernel_identity", "hvq_scale_kernel", per)]
+    thumbnails = max(0, len(launches) - per * len(blocks))                            # the scale launches of the set-up come first
+    cut = cut_by_plan(launches, [("set-up", "hvq_scale_kernel", thumbnails)] + blocks)
+    if "error" in cut:
+        return cut
+    stats = lambda r: launch_stats(l.ns for l in r[1:])                               # without the warm-up launch
+    res = {"pictures": plan["pictures"], "content": plan["content"], **resources(cut[CASES[0][0]][0]), "cases": {}}
+    yard = stats(cut["hvq_scale_kernel_identity"])
     res["hvq_scale_kernel_identity"] = yard
-    for i, (label, force, units) in enumerate(CASES):
-        m = stats(ck[i * per:(i + 1) * per])
+    for label, force, units in CASES:
+        m = stats(cut[label])
         m["force_general"] = force
         m["bytes_ratio"] = round(units / 2048, 4)
         m["multiple_of_bytes_ratio_x_yardstick"] = round(m["median_us"] / (units / 2048 * yard["median_us"]), 2)
@@ -236,60 +211,14 @@ def trace_summary(trace_dir, plan, calls):
     return res
 
 
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("calls", "trace"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
+    add_common_arguments(ap, children=("calls", "trace"), reps=10, warmup=2, rounds=3, steps="calls,trace", out_dir="compose_bench_out", out="--out")
     ap.add_argument("--contents", default="natural")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--steps", default="calls,trace")
-    ap.add_argument("--step-timeout", type=int, default=300)
-    ap.add_argument("--out-dir", default="compose_bench_out")
-    ap.add_argument("--out", default=None, help="all measurements as one JSON file (profiles/compose_bench.json)")
     args = ap.parse_args()
     if args.child:
         return {"calls": child_calls, "trace": child_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps), "--warmup", str(args.warmup),
-              "--rounds", str(args.rounds), "--contents", args.contents]
-    everything = {}
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "calls":
-            res = json.loads(run(me + ["--child", step] + common, args.step_timeout, os.path.join(args.out_dir, step + ".log")))
-        elif step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line), everything.get("calls"))
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        else:
-            sys.exit(f"unknown step {step}")
-        everything[step] = res
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
-        if args.out:
-            with open(args.out, "w") as f:
-                json.dump(everything, f, indent=1)
-                f.write("\n")
+    drive(args, {"calls": ("calls", None), "trace": ("trace", trace_summary)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

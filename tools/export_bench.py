@@ -17,38 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from hvqm4_amd import batch  # noqa: E402
-from hvqm4_amd.container import video_pictures  # noqa: E402
-from hvqm4_amd.synth import SynthConfig, make_clip  # noqa: E402
-
-PEAK = 8.0e12
-SAMPLINGS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}
-
-
-def resident_streams(ctx, sampling, streams, per, distinct, w, h):
-    hs, vs = SAMPLINGS[sampling]
-    clips = [make_clip(SynthConfig(width=w, height=h, version="1.5", gop="IPBBPBBPBBPBBPBB", seed=1000 + i, preset="dense",
-                                   sampling=sampling)) for i in range(distinct)]
-    pics = [[(ft, bytes(p)) for ft, _d, p in video_pictures(c.data)][:per] for c in clips]
-    sids = [ctx.open_stream(w, h, hs, vs, True, per + 2) for _ in range(streams)]
-    a_s, a_t, a_p = [], [], []
-    for k in range(per):                                   # decode order, streams interleaved
-        for i, sid in enumerate(sids):
-            ft, p = pics[i % distinct][k]
-            a_s.append(sid); a_t.append(ft); a_p.append(p)
-    ctx.submit_many(a_s, a_t, a_p, threads=16)
-    ctx.flush()
-    ctx.sync()
-    return sids
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
+from tools.benchlib import PEAK, SAMPLINGS, picture_lists, resident, timed  # noqa: E402
 
 
 def main():
@@ -67,17 +36,16 @@ def main():
     res = {"streams": args.streams, "pictures": args.streams * args.per, "size": f"{w}x{h}", "reps": args.reps, "peak_bytes_per_s": PEAK}
     for sampling in args.samplings.split(","):
         ctx = batch.Context(0)
-        sids = resident_streams(ctx, sampling, args.streams, args.per, args.distinct, w, h)
+        sids = resident(ctx, preset="dense", sampling=sampling, streams=args.streams, per=args.per, distinct=args.distinct, w=w, h=h)
         hs, vs = SAMPLINGS[sampling]
         src = w * h + 2 * (w // (hs)) * (h // (vs))
         n = len(sids) * args.per
-        all_s = [s for s in sids for _ in range(args.per)]
-        all_o = [k for _ in sids for k in range(args.per)]
+        all_s, all_o = picture_lists(sids, args.per)
         for fmt in ("rgb", "rgbp", "yuv444p"):
             out = torch.empty((n, h, w, 3) if fmt == "rgb" else (n, 3, h, w), dtype=torch.uint8, device="cuda")
             fn = lambda: ctx.export(all_s, all_o, out, fmt)
-            timed(fn, args.warmup)
-            ms = timed(fn, args.reps)
+            timed(torch, fn, args.warmup)
+            ms = timed(torch, fn, args.reps)
             by = n * (src + 3 * w * h)
             res[f"{sampling}_{fmt}_all"] = {"ms": round(ms, 4), "bytes": by, "tb_per_s": round(by / ms / 1e9, 3),
                                             "of_peak": round(by / ms / 1e9 / (PEAK / 1e12), 3)}
@@ -86,11 +54,11 @@ def main():
         if sampling == "420":
             out = torch.empty((len(sids), h, w, 3), dtype=torch.uint8, device="cuda")
             fn = lambda: ctx.export(sids, [args.per - 1] * len(sids), out, "rgb")
-            timed(fn, args.warmup)
+            timed(torch, fn, args.warmup)
             ctx.rgb_bench(args.warmup)
             ab = {"export_ms": [], "rgb_bench_ms": []}
             for _ in range(args.ab_rounds):
-                ab["export_ms"].append(round(timed(fn, args.reps), 4))
+                ab["export_ms"].append(round(timed(torch, fn, args.reps), 4))
                 ms, by, npic = ctx.rgb_bench(args.reps)
                 ab["rgb_bench_ms"].append(round(ms / args.reps, 4))
             by = len(sids) * (src + 3 * w * h)

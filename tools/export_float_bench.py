@@ -1,7 +1,7 @@
 """Float export (hvq_export_tensors, Context.export_float) on the GPU: 128 dense 640x480 4:2:0 streams, 8 resident pictures each.
 
-Two measurements, each a child process of this driver under its own `timeout`:
-  trace   rocprofv3 --kernel-trace --stats around a child that exports all 1024 pictures at their own size (the identity body) as
+Four measurements (steps of tools/benchlib.py; --steps defaults to the first two):
+  trace   the kernel trace of a child (`identity`) that exports all 1024 pictures at their own size (the identity body) as
           float32 / float16 / bfloat16, and -- in the same process, on the same box -- as uint8 planar RGB and RGB24 through
           hvq_export_pictures.  Kernel times are read from the trace; bytes = source planes read + destination written; share of
           8 TB/s.
@@ -13,46 +13,32 @@ Two measurements, each a child process of this driver under its own `timeout`:
           (b) the same forced to the direct body (HVQ_FILTER_TRIANGLE_DIRECT: an argument for this tool and the tests, not a switch
           of the product), (c) the plain two-tap call at the same shapes, (d) the torch route export("rgbp") -> .float() ->
           F.interpolate(antialias=True) -> normalise.  Event-timed on one stream in alternating rounds.
-  aa_trace  rocprofv3 --kernel-trace --stats around legs (a), (b), (c) in a fixed order: the kernel times of the legs.
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+  aa_trace  the kernel trace of legs (a), (b), (c) in a fixed order: the kernel times of the legs.
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PEAK = 8.0e12
+from tools.benchlib import PEAK, add_common_arguments, drive, launch_stats, picture_lists, read_kernel_trace, read_planned, resident, timed  # noqa: E402
+
 W, H = 640, 480
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 ES = {"float32": 4, "float16": 2, "bfloat16": 2}
+KERNELS = ("hvq_yuv_tensor_kernel", "hvq_yuv_resample_kernel", "hvq_yuv_rgb_kernel")
 
 
 def setup(args):
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
-    from tools.export_bench import resident_streams
     ctx = batch.Context(0)
-    sids = resident_streams(ctx, "420", args.streams, args.per, args.distinct, W, H)
-    all_s = [s for s in sids for _ in range(args.per)]
-    all_o = [k for _ in sids for k in range(args.per)]
+    all_s, all_o = picture_lists(resident(ctx, preset="dense", streams=args.streams, per=args.per, distinct=args.distinct), args.per)
     return torch, ctx, all_s, all_o
-
-
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def child_identity(args):
@@ -199,41 +185,25 @@ def child_aa_trace(args):
     print(json.dumps({"plan": plan}))
 
 
-def aa_trace_summary(trace_dir, plan):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = []
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name") or row.get("Name") or ""
-            if "hvq_yuv_resample_kernel" in name or "hvq_yuv_tensor_kernel" in name:
-                rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), name.split("(")[0],
-                             row.get("VGPR_Count"), row.get("LDS_Block_Size")))
-    rows.sort()
-    if len(rows) != sum(c for _l, c in plan):
-        return {"error": f"{len(rows)} export launches in the trace, {sum(c for _l, c in plan)} planned"}
-    res, at = {}, 0
-    for label, count in plan:
-        part = rows[at + 1:at + count]                                            # without the warm-up launch
-        at += count
-        d = sorted(r[1] for r in part)
-        res[label] = {"kernel": part[0][2], "launches": len(d), "median_us": round(statistics.median(d) / 1e3, 1),
-                      "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1), "lds": part[0][4]}
+def aa_trace_summary(trace_dir, printed, _earlier=None):
+    cut = read_planned(trace_dir, [(label, None, count) for label, count in printed["plan"]], KERNELS[:2])
+    if "error" in cut:
+        return cut
+    res = {}
+    for label, part in cut.items():
+        part = part[1:]                                                           # without the warm-up launch
+        res[label] = {"kernel": part[0].shown, **launch_stats(l.ns for l in part), "lds": part[0].lds}
     return res
 
 
-def trace_summary(trace_dir, n):
-    """median / min of every export kernel in the kernel trace -> share of 8 TB/s"""
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
+def trace_summary(trace_dir, calls, _earlier=None):
+    """what the child printed, and median / min of every export kernel in the kernel trace -> share of 8 TB/s"""
+    launches = read_kernel_trace(trace_dir, KERNELS)
+    if isinstance(launches, dict):
+        return launches
     dur = {}
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name") or row.get("Name") or ""
-            if "hvq_yuv_" in name:
-                dur.setdefault(name, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+    for l in launches:
+        dur.setdefault(l.shown, []).append(l.ns)
     src = W * H * 3 // 2
     per_px = {"<float>": 12, "<_Float16>": 6, "<hvq_bf16>": 6, "hvq_yuv_rgb_kernel": 3}
     res = {}
@@ -243,65 +213,25 @@ def trace_summary(trace_dir, n):
         b = next((v for k, v in per_px.items() if k in name), None)
         if b is None:
             continue
-        by = n * (src + b * W * H)
+        by = calls["pictures"] * (src + b * W * H)
         med = statistics.median(big)
-        res[name.split("(")[0]] = {"launches": len(big), "median_us": round(med / 1e3, 1), "min_us": round(big[0] / 1e3, 1), "bytes": by,
-                                   "of_peak_median": round(by / (med * 1e-9) / PEAK, 3), "of_peak_best": round(by / (big[0] * 1e-9) / PEAK, 3)}
-    return res
+        res[name] = {"launches": len(big), "median_us": round(med / 1e3, 1), "min_us": round(big[0] / 1e3, 1), "bytes": by,
+                     "of_peak_median": round(by / (med * 1e-9) / PEAK, 3), "of_peak_best": round(by / (big[0] * 1e-9) / PEAK, 3)}
+    return {"calls": calls, "kernels": res}
 
 
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+STEPS = {"trace": ("identity", trace_summary), "route": ("route", None), "aa": ("aa", None), "aa_trace": ("aa_trace", aa_trace_summary)}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("identity", "route", "aa", "aa_trace"), default=None)
+    add_common_arguments(ap, children=("identity", "route", "aa", "aa_trace"), reps=30, warmup=3, rounds=5, steps="trace,route", step_timeout=400,
+                         out_dir="export_float_bench_out")
     ap.add_argument("--aa-streams", type=int, default=16, help="streams of 8 resident pictures for the aa steps (16: 128 pictures)")
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", default="trace,route")
-    ap.add_argument("--step-timeout", type=int, default=400)
-    ap.add_argument("--out-dir", default="export_float_bench_out")
     args = ap.parse_args()
     if args.child:
         return {"identity": child_identity, "route": child_route, "aa": child_aa, "aa_trace": child_aa_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps),
-              "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--aa-streams", str(args.aa_streams)]
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "identity"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = {"calls": json.loads(line), "kernels": trace_summary(tdir, args.streams * args.per)}
-        elif step == "route":
-            res = json.loads(run(me + ["--child", "route"] + common, args.step_timeout, os.path.join(args.out_dir, "route.log")))
-        elif step == "aa":
-            res = json.loads(run(me + ["--child", "aa"] + common, args.step_timeout, os.path.join(args.out_dir, "aa.log")))
-        elif step == "aa_trace":
-            tdir = os.path.join(args.out_dir, "aa_trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "aa_trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "aa_trace.log"))
-            res = aa_trace_summary(tdir, json.loads(line)["plan"])
-        else:
-            sys.exit(f"unknown step {step}")
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
+    drive(args, STEPS, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

@@ -3,29 +3,27 @@ each, 1024 pictures per call; natural content (the decoded pictures) and flat co
 every wave adds into the same bin), HVQ_HIST_VALUES and HVQ_HIST_ABSDIFF (natural: picture k against k - 1 inside the stream's 8
 pictures; flat: one constant against another).
 
-Two measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
+Two measurements (steps of tools/benchlib.py):
   calls   HIP-event timed on one stream, in alternating rounds: (a) the four histogram calls; (b) picture_metrics on the same pictures
           (against zeros: the bytes VALUES reads; against the predecessor: the bytes ABSDIFF reads) -- the project's streaming bound for
           reading those bytes; (c) the route a user takes without the call: export(..., "yuv444p") of the 1024 pictures, then ONE
           torch.bincount over all planes (each plane's values offset into bins of its own), which is kinder to the route than a
           bincount per plane.  The route's chroma counts are of the replicated planes, so only luma is compared with the call's.
-  trace   rocprofv3 --kernel-trace --stats around a child that launches the same six calls in a fixed order, one warm-up and `reps`
+  trace   the kernel trace of a child that launches the same six calls in a fixed order, one warm-up and `reps`
           launches each.  Kernel times are read from the trace: median with min-max; bytes = pic_bytes per picture and side; share of
           8 TB/s; the histogram kernel's time over the metrics kernel's for the same bytes.
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PEAK = 8.0e12
+from tools.benchlib import PEAK, add_common_arguments, drive, launch_stats, picture_lists, read_planned, resident, resources, timed  # noqa: E402
+
 W, H = 640, 480
 PIC_BYTES = W * H * 3 // 2
 FLAT_A, FLAT_B = 128, 100
@@ -35,16 +33,14 @@ def setup(args):
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
-    from tools.export_bench import resident_streams
     ctx = batch.Context(0)
-    sids = resident_streams(ctx, "420", args.streams, args.per, args.distinct, W, H)
+    sids = resident(ctx, preset="dense", streams=args.streams, per=args.per, distinct=args.distinct)
     return torch, ctx, sids
 
 
 def workload(torch, ctx, sids, per):
     """label -> (callable, kernel name, sides read): the six calls over the same 1024 pictures"""
-    a_s = [s for s in sids for _ in range(per)]
-    a_o = [k for _ in sids for k in range(per)]
+    a_s, a_o = picture_lists(sids, per)
     refs = [(s, (k - 1) % per) for s in sids for k in range(per)]
     n = len(a_s)
     flat_a = torch.full((n, PIC_BYTES), FLAT_A, dtype=torch.uint8, device="cuda")
@@ -61,16 +57,6 @@ def workload(torch, ctx, sids, per):
         "metrics_pairs": (lambda: ctx.picture_metrics(a_s, a_o, refs, out=met), "hvq_metrics_kernel", 2),
     }
     return calls, (a_s, a_o, refs, hist, met, flat_a, flat_b)
-
-
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def child_calls(args):
@@ -129,32 +115,18 @@ def child_trace(args):
     print(json.dumps({"plan": plan}))
 
 
-def trace_summary(trace_dir, plan):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = []
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name") or row.get("Name") or ""
-            if "hvq_histogram_kernel" in name or "hvq_metrics_kernel" in name:
-                rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), name.split("(")[0],
-                             row.get("VGPR_Count"), row.get("LDS_Block_Size"), row.get("Scratch_Size")))
-    rows.sort()
-    if len(rows) != sum(p[2] for p in plan):
-        return {"error": f"{len(rows)} launches of the two kernels in the trace, {sum(p[2] for p in plan)} planned"}
-    res, at = {}, 0
-    for label, kernel, count, n, per_picture in plan:
-        part = rows[at + 1:at + count]                                            # without the warm-up launch
-        at += count
-        if any(kernel not in r[2] for r in part):
-            return {"error": f"{label}: the launches in the trace are not in the planned order"}
-        d = sorted(r[1] for r in part)
+def trace_summary(trace_dir, printed, _earlier=None):
+    plan = printed["plan"]
+    cut = read_planned(trace_dir, [p[:3] for p in plan])
+    if "error" in cut:
+        return cut
+    res = {}
+    for label, _kernel, _count, n, per_picture in plan:
+        part = cut[label][1:]                                                     # without the warm-up launch
+        d = [l.ns for l in part]
         by = n * per_picture
-        med = statistics.median(d)
-        res[label] = {"kernel": part[0][2], "pictures": n, "launches": len(d), "median_us": round(med / 1e3, 1), "min_us": round(d[0] / 1e3, 1),
-                      "max_us": round(d[-1] / 1e3, 1), "bytes": by, "of_peak_median": round(by / (med * 1e-9) / PEAK, 3),
-                      "vgprs": part[0][3], "lds": part[0][4], "scratch": part[0][5]}
+        res[label] = {"kernel": part[0].shown, "pictures": n, **launch_stats(d), "bytes": by,
+                      "of_peak_median": round(by / (statistics.median(d) * 1e-9) / PEAK, 3), **resources(part[0])}
     us = {k: v["median_us"] for k, v in res.items()}
     res["values_natural_over_metrics_zeros"] = round(us["values_natural"] / us["metrics_zeros"], 2)
     res["absdiff_natural_over_metrics_pairs"] = round(us["absdiff_natural"] / us["metrics_pairs"], 2)
@@ -163,53 +135,14 @@ def trace_summary(trace_dir, plan):
     return res
 
 
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("calls", "trace"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
-    ap.add_argument("--reps", type=int, default=30)
+    add_common_arguments(ap, children=("calls", "trace"), reps=30, warmup=2, rounds=5, steps="calls,trace", out_dir="histogram_bench_out")
     ap.add_argument("--route-reps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", default="calls,trace")
-    ap.add_argument("--step-timeout", type=int, default=300)
-    ap.add_argument("--out-dir", default="histogram_bench_out")
     args = ap.parse_args()
     if args.child:
         return {"calls": child_calls, "trace": child_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps),
-              "--route-reps", str(args.route_reps), "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line)["plan"])
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        elif step == "calls":
-            res = json.loads(run(me + ["--child", "calls"] + common, args.step_timeout, os.path.join(args.out_dir, "calls.log")))
-        else:
-            sys.exit(f"unknown step {step}")
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
+    drive(args, {"calls": ("calls", None), "trace": ("trace", trace_summary)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

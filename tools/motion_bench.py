@@ -3,27 +3,26 @@ pairs per call, at B = 16 with R = 8 and R = 15 and at B = 8 with R = 8; three c
 stream's 8 pictures), flat (a flat reference in the caller's memory: every candidate of a block ties) and a picture against itself
 (every cost is 0 at the zero vector).
 
-Two measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
+Two measurements (steps of tools/benchlib.py):
   calls   HIP-event timed on one stream, in alternating rounds: (a) the nine motion calls; (b) the route a user takes without the call,
           on the natural pairs at each setting: export(..., "yuv444p") of both pictures, then per displacement abs of the shifted luma
           difference and avg_pool2d(B), and a running minimum of the packed tuple (cost, |dy| + |dx|, dy, dx) -- in chunks of pictures,
           so that the route's temporaries fit.  The fields of the route and of the call are compared before anything is timed.
-  trace   rocprofv3 --kernel-trace --stats around a child that launches the same nine calls in a fixed order, one warm-up and `reps`
+  trace   the kernel trace of a child that launches the same nine calls in a fixed order, one warm-up and `reps`
           launches each.  Kernel times are read from the trace: median with min-max, beside the arithmetic estimate of the time the byte
           differences alone would take as 4-byte SAD lane operations at the VALU issue rate (blocks x candidates x B^2 / 4 lane
           operations; 256 CUs x 64 lanes per clock at 2.4 GHz), and the fraction of it reached.
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from tools.benchlib import add_common_arguments, drive, launch_stats, picture_lists, read_planned, resident, resources, timed  # noqa: E402
 
 W, H = 640, 480
 PIC_BYTES = W * H * 3 // 2
@@ -37,9 +36,8 @@ def setup(args):
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
-    from tools.export_bench import resident_streams
     ctx = batch.Context(0)
-    sids = resident_streams(ctx, "420", args.streams, args.per, args.distinct, W, H)
+    sids = resident(ctx, preset="dense", streams=args.streams, per=args.per, distinct=args.distinct)
     return torch, ctx, sids
 
 
@@ -50,8 +48,7 @@ def label(content, B, R):
 def workload(torch, ctx, sids, per):
     """label -> callable: the nine calls over the same 1024 pictures"""
     from hvqm4_amd.motion import blocks
-    a_s = [s for s in sids for _ in range(per)]
-    a_o = [k for _ in sids for k in range(per)]
+    a_s, a_o = picture_lists(sids, per)
     n = len(a_s)
     flat = torch.full((PIC_BYTES,), FLAT, dtype=torch.uint8, device="cuda")
     refs = {"natural": [(s, (k - 1) % per) for s in sids for k in range(per)], "flat": [flat] * n, "itself": list(zip(a_s, a_o))}
@@ -61,16 +58,6 @@ def workload(torch, ctx, sids, per):
         for c in CONTENTS:
             calls[label(c, B, R)] = (lambda c=c, B=B, R=R: ctx.picture_motion(a_s, a_o, refs[c], block=B, radius=R, out=outs[B]))
     return calls, (a_s, a_o, refs, outs, flat)
-
-
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def torch_route(torch, ctx, a_s, a_o, refs, B, R, chunk):
@@ -155,82 +142,31 @@ def estimate_ms(n, B, R):
     return n * cand * (B * B // 4) / LANE_OPS_PER_S * 1e3
 
 
-def trace_summary(trace_dir, plan):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = []
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name") or row.get("Name") or ""
-            if "hvq_motion_kernel" in name:
-                rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), name.split("(")[0],
-                             row.get("VGPR_Count"), row.get("LDS_Block_Size"), row.get("Scratch_Size")))
-    rows.sort()
-    if len(rows) != sum(p[1] for p in plan):
-        return {"error": f"{len(rows)} launches of the kernel in the trace, {sum(p[1] for p in plan)} planned"}
-    res, at = {}, 0
-    for lab, count, n in plan:
-        part = rows[at + 1:at + count]                                            # without the warm-up launch
-        at += count
-        d = sorted(r[1] for r in part)
-        med = statistics.median(d)
+def trace_summary(trace_dir, printed, _earlier=None):
+    plan = printed["plan"]
+    cut = read_planned(trace_dir, [(lab, "hvq_motion_kernel", count) for lab, count, _n in plan])
+    if "error" in cut:
+        return cut
+    res = {}
+    for lab, _count, n in plan:
+        part = cut[lab][1:]                                                       # without the warm-up launch
+        d = [l.ns for l in part]
         B, R = int(lab.split("_b")[1].split("_r")[0]), int(lab.split("_r")[1])
         est = estimate_ms(n, B, R)
-        res[lab] = {"pictures": n, "launches": len(d), "median_us": round(med / 1e3, 1), "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1),
-                    "sad_estimate_us": round(est * 1e3, 1), "estimate_over_median": round(est * 1e6 / med, 3),
-                    "vgprs": part[0][3], "lds": part[0][4], "scratch": part[0][5]}
+        res[lab] = {"pictures": n, **launch_stats(d), "sad_estimate_us": round(est * 1e3, 1), "estimate_over_median": round(est * 1e6 / statistics.median(d), 3),
+                    **resources(part[0])}
     return res
-
-
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("calls", "trace"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
-    ap.add_argument("--reps", type=int, default=10)
+    add_common_arguments(ap, children=("calls", "trace"), reps=10, warmup=2, rounds=3, steps="calls,trace", step_timeout=420, out_dir="motion_bench_out")
     ap.add_argument("--route-reps", type=int, default=1)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=128, help="pictures the torch route handles at a time")
-    ap.add_argument("--steps", default="calls,trace")
-    ap.add_argument("--step-timeout", type=int, default=420)
-    ap.add_argument("--out-dir", default="motion_bench_out")
     args = ap.parse_args()
     if args.child:
         return {"calls": child_calls, "trace": child_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps),
-              "--route-reps", str(args.route_reps), "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--chunk", str(args.chunk)]
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line)["plan"])
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        elif step == "calls":
-            res = json.loads(run(me + ["--child", "calls"] + common, args.step_timeout, os.path.join(args.out_dir, "calls.log")))
-        else:
-            sys.exit(f"unknown step {step}")
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
+    drive(args, {"calls": ("calls", None), "trace": ("trace", trace_summary)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

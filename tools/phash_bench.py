@@ -1,6 +1,6 @@
 """Perceptual hashes and nearest-hash search (hvq_picture_hashes / hvq_hash_nearest) on the GPU.
 
-Three measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
+Three measurements (steps of tools/benchlib.py):
   hashes   128 640x480 4:2:0 streams, 8 resident pictures each, 1024 pictures per call, on dense, natural and flat content:
            (a) picture_hashes, (b) picture_metrics against zeros on the same pictures -- existing code that reads Y, U and V once, 1.5
            times the bytes (a) needs -- and (c) the torch route on the same pictures: export to YUV 4:4:4, area pooling of Y to 32 x 32,
@@ -9,54 +9,24 @@ Three measurements, each a child process of this driver under its own `timeout`;
   nearest  16 384 x 16 384 and 65 536 x 65 536 random hashes: (a) hash_nearest, (b) a torch route (xor, a byte-table popcount, min over
            chunks of queries); pairs per second, the factor (b)/(a), and the share of the v_bcnt_u32_b32 issue bound reached (two per pair;
            --valu-per-pair is the inner loop's vector instructions per pair from profiles/phash_isa.txt).  (a) and (b) must agree.
-  trace    rocprofv3 --kernel-trace --stats around a child that launches picture_hashes, picture_metrics and hash_nearest in a fixed
+  trace    the kernel trace of a child that launches picture_hashes, picture_metrics and hash_nearest in a fixed
            order, one warm-up and `reps` launches each.  Kernel times are read from the trace: median with min-max per kernel.
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PEAK = 8.0e12
+from tools.benchlib import PEAK, add_common_arguments, drive, launch_stats, picture_lists, read_per_kernel, resident, resources, timed  # noqa: E402
+
 CLOCK, SIMDS = 2.4e9, 1024                       # a wave64 vector instruction issues over 2 cycles on a SIMD
 W, H = 640, 480
 PIC_BYTES = W * H * 3 // 2
 KERNELS = ("hvq_phash_cells_kernel", "hvq_phash_finish_kernel", "hvq_metrics_kernel", "hvq_hash_nearest_kernel")
-
-
-def resident(ctx, preset, streams, per, distinct):
-    from hvqm4_amd.container import video_pictures
-    from hvqm4_amd.synth import SynthConfig, make_clip
-    clips = [make_clip(SynthConfig(width=W, height=H, version="1.5", gop="IPBBPBBPBBPBBPBB", seed=1000 + i, preset=preset, sampling="420"))
-             for i in range(distinct)]
-    pics = [[(ft, bytes(p)) for ft, _d, p in video_pictures(c.data)][:per] for c in clips]
-    sids = [ctx.open_stream(W, H, 2, 2, True, per + 2) for _ in range(streams)]
-    a_s, a_t, a_p = [], [], []
-    for k in range(per):
-        for i, sid in enumerate(sids):
-            ft, p = pics[i % distinct][k]
-            a_s.append(sid); a_t.append(ft); a_p.append(p)
-    ctx.submit_many(a_s, a_t, a_p, threads=16)
-    ctx.flush()
-    ctx.sync()
-    return sids
-
-
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def torch_route(torch, ctx, a_s, a_o, yuv, dct):
@@ -78,9 +48,7 @@ def child_hashes(args):
     dct = torch.from_numpy(phash.TABLE.astype("float32") / 4096).cuda()
     for preset in args.contents.split(","):
         ctx = batch.Context(0)
-        sids = resident(ctx, preset, args.streams, args.per, args.distinct)
-        a_s = [s for s in sids for _ in range(args.per)]
-        a_o = [k for _ in sids for k in range(args.per)]
+        a_s, a_o = picture_lists(resident(ctx, preset=preset, streams=args.streams, per=args.per, distinct=args.distinct), args.per)
         n = len(a_s)
         out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
         met = torch.empty((n, 3, 4), dtype=torch.int64, device="cuda")
@@ -157,14 +125,12 @@ def child_nearest(args):
 
 
 def child_trace(args):
-    """the launches the trace is taken of"""
+    """the launches the trace is taken of: a picture_hashes call launches hvq_phash_cells_kernel and hvq_phash_finish_kernel in turn"""
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
     ctx = batch.Context(0)
-    sids = resident(ctx, "dense", args.streams, args.per, args.distinct)
-    a_s = [s for s in sids for _ in range(args.per)]
-    a_o = [k for _ in sids for k in range(args.per)]
+    a_s, a_o = picture_lists(resident(ctx, preset="dense", streams=args.streams, per=args.per, distinct=args.distinct), args.per)
     n = len(a_s)
     out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
     met = torch.empty((n, 3, 4), dtype=torch.int64, device="cuda")
@@ -184,28 +150,13 @@ def child_trace(args):
     print(json.dumps({"launches": 1 + args.reps, "pictures": n, "nearest": nn}))
 
 
-def trace_summary(trace_dir, plan):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = {k: [] for k in KERNELS}
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = (row.get("Kernel_Name") or row.get("Name") or "").split("(")[0].strip()
-            name = name[:-3] if name.endswith(".kd") else name
-            for k in KERNELS:
-                if name.split(" ")[-1] == k:
-                    rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]),
-                                    row.get("VGPR_Count"), row.get("LDS_Block_Size"), row.get("Scratch_Size")))
+def trace_summary(trace_dir, plan, _earlier=None):
+    cut = read_per_kernel(trace_dir, KERNELS, plan["launches"])
+    if "error" in cut:
+        return cut
     res = {"pictures": plan["pictures"], "nearest": plan["nearest"]}
-    for k in KERNELS:
-        r = sorted(rows[k])
-        if len(r) != plan["launches"]:
-            return {"error": f"{len(r)} launches of {k} in the trace, {plan['launches']} planned"}
-        d = sorted(x[1] for x in r[1:])                                           # without the warm-up launch
-        med = statistics.median(d)
-        res[k] = {"launches": len(d), "median_us": round(med / 1e3, 1), "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1),
-                  "vgprs": r[0][2], "lds": r[0][3], "scratch": r[0][4]}
+    for k, r in cut.items():
+        res[k] = {**launch_stats(l.ns for l in r[1:]), **resources(r[0])}         # without the warm-up launch
     luma, pic = plan["pictures"] * W * H, plan["pictures"] * PIC_BYTES
     res[KERNELS[0]].update({"bytes": luma, "of_peak_median": round(luma / (res[KERNELS[0]]["median_us"] * 1e-6) / PEAK, 3)})
     res[KERNELS[2]].update({"bytes": pic, "of_peak_median": round(pic / (res[KERNELS[2]]["median_us"] * 1e-6) / PEAK, 3)})
@@ -214,64 +165,18 @@ def trace_summary(trace_dir, plan):
     return res
 
 
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("hashes", "nearest", "trace"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
+    add_common_arguments(ap, children=("hashes", "nearest", "trace"), reps=20, warmup=3, rounds=5, steps="hashes,nearest,trace", out_dir="phash_bench_out",
+                         out="--out")
     ap.add_argument("--contents", default="dense,natural,flat")
     ap.add_argument("--nearest-sizes", default="16384,65536")
     ap.add_argument("--chunk", type=int, default=512, help="queries per chunk of the torch route")
     ap.add_argument("--valu-per-pair", type=float, default=9.6, help="vector instructions per pair of the inner loop (profiles/phash_isa.txt)")
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", default="hashes,nearest,trace")
-    ap.add_argument("--step-timeout", type=int, default=300)
-    ap.add_argument("--out-dir", default="phash_bench_out")
-    ap.add_argument("--out", default=None, help="all measurements as one JSON file (profiles/phash_bench.json)")
     args = ap.parse_args()
     if args.child:
         return {"hashes": child_hashes, "nearest": child_nearest, "trace": child_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps), "--warmup", str(args.warmup),
-              "--rounds", str(args.rounds), "--contents", args.contents, "--nearest-sizes", args.nearest_sizes, "--chunk", str(args.chunk),
-              "--valu-per-pair", str(args.valu_per_pair)]
-    everything = {}
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step in ("hashes", "nearest"):
-            res = json.loads(run(me + ["--child", step] + common, args.step_timeout, os.path.join(args.out_dir, step + ".log")))
-        elif step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line))
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        else:
-            sys.exit(f"unknown step {step}")
-        everything[step] = res
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
-        if args.out:
-            with open(args.out, "w") as f:
-                json.dump(everything, f, indent=1)
-                f.write("\n")
+    drive(args, {"hashes": ("hashes", None), "nearest": ("nearest", None), "trace": ("trace", trace_summary)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 """Windowed SSIM (hvq_picture_ssim, Context.picture_ssim) on the GPU: the workload of tools/metrics_bench.py -- 128 dense 640x480 4:2:0
 streams, 8 resident pictures each, 1024 pairs (k, k - 1) (k - 1 taken inside the stream's 8 pictures).
 
-Two measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
-  trace   rocprofv3 --kernel-trace --stats around a child that launches, in a fixed order, hvq_ssim_kernel without maps, with maps, and
+Two measurements (steps of tools/benchlib.py):
+  trace   the kernel trace of a child that launches, in a fixed order, hvq_ssim_kernel without maps, with maps, and
           -- in the same process, on the same pairs -- hvq_metrics_kernel, the yardstick: it reads exactly the same bytes.  One warm-up
           launch and `reps` launches each.  Kernel times are read from the trace: median with min-max; bytes = 2 x pic_bytes per pair
           (plus the maps written); the two ratios to the metrics kernel.
@@ -10,10 +10,8 @@ Two measurements, each a child process of this driver under its own `timeout`; a
           avg_pool2d(8, stride 4) on a, b, a^2 + b^2 and a b -> the formula -> the mean per plane.  Both event-timed on one stream in
           alternating rounds; the two must agree on the luma mean (the chroma planes of the export are replicated to full size, so
           only luma is compared, and the route's float32 variances only agree to about 1e-4).
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
@@ -22,9 +20,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tools.metrics_bench import H, PEAK, PIC_BYTES, W, pairs, run, setup, timed      # noqa: E402
-
-KERNELS = ("hvq_ssim_kernel", "hvq_metrics_kernel")
+from tools.benchlib import PEAK, add_common_arguments, drive, launch_stats, read_planned, resources, timed  # noqa: E402
+from tools.metrics_bench import H, PIC_BYTES, W, pairs, setup      # noqa: E402
 
 
 def child_trace(args):
@@ -54,32 +51,18 @@ def child_trace(args):
     print(json.dumps({"plan": plan}))
 
 
-def trace_summary(trace_dir, plan):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = []
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Kernel_Name") or row.get("Name") or ""
-            if any(k in name for k in KERNELS):
-                rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), name.split("(")[0],
-                             row.get("VGPR_Count"), row.get("LDS_Block_Size"), row.get("Scratch_Size")))
-    rows.sort()
-    if len(rows) != sum(p[2] for p in plan):
-        return {"error": f"{len(rows)} launches of the two kernels in the trace, {sum(p[2] for p in plan)} planned"}
-    res, at = {}, 0
-    for label, kernel, count, n, per_pair in plan:
-        part = rows[at + 1:at + count]                                            # without the warm-up launch
-        at += count
-        if any(kernel not in r[2] for r in part):
-            return {"error": f"{label}: the launches in the trace are not in the planned order"}
-        d = sorted(r[1] for r in part)
+def trace_summary(trace_dir, printed, _earlier=None):
+    plan = printed["plan"]
+    cut = read_planned(trace_dir, [p[:3] for p in plan])
+    if "error" in cut:
+        return cut
+    res = {}
+    for label, _kernel, _count, n, per_pair in plan:
+        part = cut[label][1:]                                                     # without the warm-up launch
+        d = [l.ns for l in part]
         by = n * per_pair
-        med = statistics.median(d)
-        res[label] = {"kernel": part[0][2], "pairs": n, "launches": len(d), "median_us": round(med / 1e3, 1), "min_us": round(d[0] / 1e3, 1),
-                      "max_us": round(d[-1] / 1e3, 1), "bytes": by, "of_peak_median": round(by / (med * 1e-9) / PEAK, 3),
-                      "vgprs": part[0][3], "lds": part[0][4], "scratch": part[0][5]}
+        res[label] = {"kernel": part[0].shown, "pairs": n, **launch_stats(d), "bytes": by,
+                      "of_peak_median": round(by / (statistics.median(d) * 1e-9) / PEAK, 3), **resources(part[0])}
     res["ssim_over_metrics"] = round(res["ssim"]["median_us"] / res["metrics"]["median_us"], 2)
     res["ssim_maps_over_metrics"] = round(res["ssim_maps"]["median_us"] / res["metrics"]["median_us"], 2)
     return res
@@ -137,40 +120,11 @@ def child_route(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("trace", "route"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", default="trace,route")
-    ap.add_argument("--step-timeout", type=int, default=300)
-    ap.add_argument("--out-dir", default="ssim_bench_out")
+    add_common_arguments(ap, children=("trace", "route"), reps=30, warmup=3, rounds=5, steps="trace,route", out_dir="ssim_bench_out")
     args = ap.parse_args()
     if args.child:
         return {"trace": child_trace, "route": child_route}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps),
-              "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line)["plan"])
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        elif step == "route":
-            res = json.loads(run(me + ["--child", "route"] + common, args.step_timeout, os.path.join(args.out_dir, "route.log")))
-        else:
-            sys.exit(f"unknown step {step}")
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
+    drive(args, {"trace": ("trace", trace_summary), "route": ("route", None)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Warped pictures in slot layout (hvq_warp_pictures) on the GPU: the measurement that sets the rule of hvq_wp_choose (hvq_warp.h).
 
-Two measurements, each a child process of this driver under its own `timeout`; a step that fails ends the run:
+Two measurements (steps of tools/benchlib.py):
   calls   128 640x480 4:2:0 streams, 8 resident pictures each, 1024 pictures per call, on natural content, through the identity, a
           half-sample translation, rotations by 5 and 45 degrees, the quarter turn into 480x640, zoom 1/2 into 320x240 and zoom 2, each
           under the chosen body, the forced direct body and the tiled body wherever LDS holds the box: (a) warp_pictures, (b)
@@ -8,29 +8,29 @@ Two measurements, each a child process of this driver under its own `timeout`; a
           the identity --, (c) a torch route on a device copy of the same pictures: per plane a float view, affine_grid + grid_sample,
           rounding, cast, concatenation.  HIP-event timed per call on one stream in alternating rounds after a warm-up; medians over
           the rounds.  (a) must equal hvqm4_amd.warp on pictures read back under every body.
-  trace   rocprofv3 --kernel-trace --stats around a child that launches warp_pictures per map and body and scale_pictures (identity) in a
+  trace   the kernel trace of a child that launches warp_pictures per map and body and scale_pictures (identity) in a
           fixed order, one warm-up and `reps` launches each; one configuration (the identity under the direct body) is repeated at the
           start, in the middle and at the end: the largest distance between the medians of its three blocks is the run-to-run spread.
           Kernel times are read from the trace: median with min-max per map and body, and per map whether the body the rule chose is
           no slower than the direct one plus the spread.
-One JSON line per measurement on stdout and in --out-dir.  torch is imported before the library, so both share one HIP runtime."""
+"""
 import argparse
-import csv
-import glob
 import json
 import os
 import statistics
-import subprocess
 import sys
 from fractions import Fraction
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from tools.benchlib import (add_common_arguments, drive, launch_stats, optional_route, picture_lists, read_planned, resident, resources,  # noqa: E402
+                            timed)
 
 W, H = 640, 480
 SRC = (W, H, 2, 2)
 BODIES = (("chosen", 0), ("direct", 1), ("tiled", 2))
+SPREAD_AFTER = 3                                     # the spread block is repeated after the map of this index
 
 
 def the_maps():
@@ -41,16 +41,6 @@ def the_maps():
     return [("identity", wp.identity(), SRC), ("translate_half", wp.translate(Fraction(-1, 2), Fraction(-1, 2)), SRC), ("rotate5", wp.rotate(5, W, H), SRC),
             ("rotate45", wp.rotate(45, W, H), SRC), ("quarter_turn", turn, size + (2, 2)), ("zoom_half_to_320x240", wp.zoom(Fraction(1, 2)), (320, 240, 2, 2)),
             ("zoom2", wp.zoom(2, centre=c), SRC)]
-
-
-def timed(torch, fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def torch_route(torch, copy, w, tg, chunk=128):
@@ -84,11 +74,8 @@ def setup(args):
     import torch
     torch.cuda.init()
     from hvqm4_amd import batch
-    from scale_bench import resident
     ctx = batch.Context(0)
-    sids = resident(ctx, args.contents.split(",")[0], args.streams, args.per, args.distinct)
-    a_s = [s for s in sids for _ in range(args.per)]
-    a_o = [k for _ in sids for k in range(args.per)]
+    a_s, a_o = picture_lists(resident(ctx, preset=args.contents.split(",")[0], streams=args.streams, per=args.per, distinct=args.distinct), args.per)
     return torch, ctx, a_s, a_o
 
 
@@ -111,7 +98,6 @@ def child_calls(args):
     for label, w, tg in the_maps():
         out = torch.empty((n, scale.nbytes(*tg)), dtype=torch.uint8, device="cuda")
         call = lambda: ctx.warp_pictures(a_s, a_o, w, tg[:2], tg[2:], out=out)
-        route = lambda: torch_route(torch, copy, w, tg)
         want = {i: wp.of_picture(host[i], SRC, w, tg) for i in probe}
         r = {"bodies_of_planes": [wp.body(w, SRC, tg, p) for p in (0, 1)], "target": list(tg), "scale_identity_ms": [], "torch_ms": []}
         agree = True
@@ -121,13 +107,9 @@ def child_calls(args):
             got = out.cpu().numpy()
             agree = agree and all(np.array_equal(got[i], want[i]) for i in probe)
             r[name + "_ms"] = []
-        try:                                                    # a torch build without this sampler: the route is reported as missing
-            timed(torch, route, 1)
+        route, off = optional_route(torch, lambda: torch_route(torch, copy, w, tg))     # a torch build without this sampler
+        if route:
             off = int((route().to(torch.int16) - out.to(torch.int16)).abs().max())
-        except RuntimeError as e:
-            if "HIP" in str(e) or "illegal" in str(e):              # a fault of the device, not a missing operator: nothing more is started
-                raise
-            off, route = str(e)[:200], None
         for _ in range(args.rounds):
             for name, force in BODIES:
                 ctx.warp_force_direct(force)
@@ -165,7 +147,7 @@ def child_trace(args):
     for i, (_label, w, tg) in enumerate(the_maps()):
         for _name, force in BODIES:
             block(w, tg, force)
-        if i == 3:
+        if i == SPREAD_AFTER:
             block(wp.identity(), SRC, 1)
     block(wp.identity(), SRC, 1)
     ctx.warp_force_direct(0)
@@ -176,41 +158,25 @@ def child_trace(args):
     print(json.dumps({"launches": 1 + args.reps, "pictures": n, "content": args.contents.split(",")[0]}))
 
 
-def trace_summary(trace_dir, plan):
+def trace_summary(trace_dir, plan, _earlier=None):
     from hvqm4_amd import warp as wp
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    if not files:
-        return {"error": f"no kernel trace under {trace_dir}"}
-    rows = {"hvq_warp_kernel": [], "hvq_scale_kernel": []}
-    with open(files[0], newline="") as f:
-        for row in csv.DictReader(f):
-            name = (row.get("Kernel_Name") or row.get("Name") or "").split("(")[0].strip()
-            name = name[:-3] if name.endswith(".kd") else name
-            k = name.split(" ")[-1]
-            if k in rows:
-                rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]), row.get("VGPR_Count"), row.get("LDS_Block_Size"),
-                                row.get("Scratch_Size")))
-    per = plan["launches"]
     maps = the_maps()
-    wk, sc = sorted(rows["hvq_warp_kernel"]), sorted(rows["hvq_scale_kernel"])
-    blocks = 3 + 3 * len(maps)
-    if len(wk) != per * blocks or len(sc) != per:
-        return {"error": f"{len(wk)} warp and {len(sc)} scale launches in the trace, {per * blocks} and {per} planned"}
-
-    def stats(r):
-        d = sorted(x[1] for x in r[1:])                                               # without the warm-up launch
-        return {"launches": len(d), "median_us": round(statistics.median(d) / 1e3, 1), "min_us": round(d[0] / 1e3, 1), "max_us": round(d[-1] / 1e3, 1)}
-
-    res = {"pictures": plan["pictures"], "content": plan["content"], "vgprs": wk[0][2], "lds": wk[0][3], "scratch": wk[0][4], "maps": {}}
-    cut = [wk[i * per:(i + 1) * per] for i in range(blocks)]
-    spread_blocks = [stats(cut[0]), stats(cut[1 + 3 * 4]), stats(cut[-1])]
-    rest = cut[1:1 + 3 * 4] + cut[2 + 3 * 4:-1]
+    blocks = ["spread0"]
+    for i, (label, _w, _tg) in enumerate(maps):
+        blocks += [f"{label}/{name}" for name, _f in BODIES] + (["spread1"] if i == SPREAD_AFTER else [])
+    cut = read_planned(trace_dir, [(b, "hvq_warp_kernel", plan["launches"]) for b in blocks + ["spread2"]] +
+                       [("hvq_scale_kernel_identity", "hvq_scale_kernel", plan["launches"])])
+    if "error" in cut:
+        return cut
+    stats = lambda b: launch_stats(l.ns for l in cut[b][1:])                          # without the warm-up launch
+    res = {"pictures": plan["pictures"], "content": plan["content"], **resources(cut["spread0"][0]), "maps": {}}
+    spread_blocks = [stats("spread0"), stats("spread1"), stats("spread2")]
     med = [b["median_us"] for b in spread_blocks]
     res["spread"] = {"configuration": "identity, direct body", "blocks": spread_blocks, "spread_us": round(max(med) - min(med), 1)}
-    res["hvq_scale_kernel_identity"] = stats(sc)
+    res["hvq_scale_kernel_identity"] = stats("hvq_scale_kernel_identity")
     ok = True
-    for i, (label, w, tg) in enumerate(maps):
-        m = {name: stats(rest[3 * i + j]) for j, (name, _f) in enumerate(BODIES)}
+    for label, w, tg in maps:
+        m = {name: stats(f"{label}/{name}") for name, _f in BODIES}
         m["bodies_of_planes"] = [wp.body(w, SRC, tg, p) for p in (0, 1)]
         m["chosen_no_slower_than_direct_plus_spread"] = m["chosen"]["median_us"] <= m["direct"]["median_us"] + res["spread"]["spread_us"]
         m["tiled_minus_direct_us"] = round(m["tiled"]["median_us"] - m["direct"]["median_us"], 1)
@@ -220,60 +186,14 @@ def trace_summary(trace_dir, plan):
     return res
 
 
-def run(cmd, limit, log):
-    """one GPU step under its own time limit; a failed step ends the run"""
-    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, capture_output=True, text=True)
-    with open(log, "w") as f:
-        f.write(r.stdout + "\n--- stderr ---\n" + r.stderr[-20000:])
-    if r.returncode:
-        sys.exit(f"{' '.join(cmd[:6])} ... ended with status {r.returncode}: see {log}")
-    return [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", choices=("calls", "trace"), default=None)
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--per", type=int, default=8, help="resident pictures per stream")
-    ap.add_argument("--distinct", type=int, default=2, help="distinct clips dealt over the streams")
+    add_common_arguments(ap, children=("calls", "trace"), reps=20, warmup=3, rounds=5, steps="calls,trace", out_dir="warp_bench_out", out="--out")
     ap.add_argument("--contents", default="natural")
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", default="calls,trace")
-    ap.add_argument("--step-timeout", type=int, default=300)
-    ap.add_argument("--out-dir", default="warp_bench_out")
-    ap.add_argument("--out", default=None, help="all measurements as one JSON file (profiles/warp_bench.json)")
     args = ap.parse_args()
     if args.child:
         return {"calls": child_calls, "trace": child_trace}[args.child](args)
-    os.makedirs(args.out_dir, exist_ok=True)
-    me = [sys.executable, os.path.abspath(__file__)]
-    common = ["--streams", str(args.streams), "--per", str(args.per), "--distinct", str(args.distinct), "--reps", str(args.reps), "--warmup", str(args.warmup),
-              "--rounds", str(args.rounds), "--contents", args.contents]
-    everything = {}
-    for step in args.steps.split(","):
-        print(f"# step {step}", flush=True)
-        if step == "calls":
-            res = json.loads(run(me + ["--child", step] + common, args.step_timeout, os.path.join(args.out_dir, step + ".log")))
-        elif step == "trace":
-            tdir = os.path.join(args.out_dir, "trace")
-            line = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tdir, "--"] + me + ["--child", "trace"] + common,
-                       args.step_timeout, os.path.join(args.out_dir, "trace.log"))
-            res = trace_summary(tdir, json.loads(line))
-            if "error" in res:
-                sys.exit(f"trace: {res['error']}")
-        else:
-            sys.exit(f"unknown step {step}")
-        everything[step] = res
-        line = json.dumps({step: res})
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, step + ".json"), "w") as f:
-            f.write(line + "\n")
-        if args.out:
-            with open(args.out, "w") as f:
-                json.dump(everything, f, indent=1)
-                f.write("\n")
+    drive(args, {"calls": ("calls", None), "trace": ("trace", trace_summary)}, [sys.executable, os.path.abspath(__file__)])
 
 
 if __name__ == "__main__":
