@@ -80,6 +80,14 @@ class HvqFilter(C.Structure):                   # a filter of hvq_filter_picture
     _fields_ = [("luma", HvqPlaneFilter), ("chroma", HvqPlaneFilter)]
 
 
+class HvqRankPlane(C.Structure):                # include/hvqm4_amd.h: a plane's rank operation (HVQ_RNK_*) and its radii
+    _fields_ = [("op", C.c_int32), ("rx", C.c_int32), ("ry", C.c_int32), ("pad", C.c_int32)]
+
+
+class HvqRank(C.Structure):                     # an entry of hvq_rank_pictures: luma for Y, chroma for U and V
+    _fields_ = [("luma", HvqRankPlane), ("chroma", HvqRankPlane)]
+
+
 class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
     _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
 
@@ -176,6 +184,10 @@ SYMBOLS = {
     "hvq_filter_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "hvq_filter_force_filter": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_rank_check": (C.c_int, [C.c_void_p]),
+    "hvq_rank_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "hvq_rank_force_general": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_warp_check": (C.c_int, [C.c_void_p]),
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),

@@ -641,6 +641,76 @@ class Context:
         check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_f, C.c_void_p), len(table), a_w, a_d, stream))
         return out
 
+    def rank_force_general(self, on: bool) -> bool:
+        """hvq_rank_force_general: every later rank_pictures of this context runs the planes that are copied through the min/max body
+        of the kernel instead of the copy body (False: the chosen one again) -> the setting before.  The values do not depend on it:
+        for tests that compare the two with =="""
+        return bool(check(lib().hvq_rank_force_general(self._h, int(bool(on)))))
+
+    def rank_pictures(self, sids, ordinals, rank, src=None, out=None):
+        """hvq_rank_pictures: resident pictures (sids[i], ordinals[i]) through rank filters -- erosion, dilation, the range, the 3 x 3
+        or 5 x 5 median: samples are selected, nothing is rounded (include/hvqm4_amd.h) -- into uint8 pictures of their own geometry IN
+        SLOT LAYOUT (Y | U | V), on torch's current stream, without a host synchronisation and without moving a picture.  `rank`: one
+        hvqm4_amd.rank.Rank, or a list of one per picture (equal ones share an entry of the call's table; more than 64 distinct ones:
+        ValueError).  -> when every geometry is the same one uint8 CUDA tensor [n, bytes], otherwise a list of n 1-D uint8 CUDA
+        tensors (`out`, if given: of that same form, contiguous, rows 16-byte aligned; it is overwritten whole and must not overlap a
+        source).  Whatever takes src= or ref.ptr takes a row of the result.  hvqm4_amd.rank builds the operations and gives the
+        expected bytes (of_picture).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
+        from . import rank as rk
+        from .checksums import sources
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if isinstance(rank, rk.Rank):
+            table, which = [rank], None
+        else:
+            if not isinstance(rank, (list, tuple)) or len(rank) != n:
+                raise ValueError(f"rank: one rank.Rank, or a list of {n}")
+            index, table, which = {}, [], []
+            for r in rank:
+                if not isinstance(r, rk.Rank):
+                    raise ValueError(f"rank: an entry is a rank.Rank, not {type(r).__name__}")
+                if r not in index:
+                    index[r] = len(table)
+                    table.append(r)
+                which.append(index[r])
+            if len(table) > rk.MAX_RANKS:
+                raise ValueError(f"{len(table)} distinct ranks: one call takes {rk.MAX_RANKS} at the most")
+        for r in table:
+            rk.check(r)                                                    # ValueError beyond the library's limits
+        streams = set(sids)
+        pb = {s: self.pic_bytes(s) for s in streams}                       # a call usually repeats few streams: each is looked at once
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        nb = [pb[s] for s in sids]
+        uniform = len({self._geometry(s) for s in streams}) <= 1
+        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
+        if not n:
+            return out
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
+        from ._lib import HvqRank
+        a_r = (HvqRank * len(table))(*[r.struct() for r in table])
+        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_rank_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_d, stream))
+        return out
+
+    def morph_pictures(self, sids, ordinals, steps, out=None):
+        """resident pictures (sids[i], ordinals[i]) through a list of rank steps (hvqm4_amd.rank.opening / closing, or any list of
+        rank.Rank), one rank_pictures a step on torch's current stream: the first from the resident pictures, every later one from the
+        result before it through src=.  The results between the steps alternate between two scratch tensors of the output's form; the
+        last lands in `out` (rank_pictures' rules; default: a new one).  No host synchronisation.  -> rank_pictures' return forms.
+        hvqm4_amd.rank.of_steps gives the expected bytes."""
+        from . import rank as rk
+        steps = rk.as_steps(steps)
+        n = len(sids)
+        cur = spare = None
+        for k, step in enumerate(steps):
+            dst = out if k == len(steps) - 1 else spare
+            if cur is None:
+                res = self.rank_pictures(sids, ordinals, step, out=dst)
+            else:
+                res = self.rank_pictures(sids, [-1] * n, step, src=[cur[i] for i in range(n)], out=dst)
+            spare, cur = cur, res
+        return cur
+
     def warp_force_direct(self, on) -> int:
         """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen
         one again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) -> the setting before.  The

@@ -675,4 +675,47 @@ _Static_assert(sizeof(HvqComposeJob) == 48, "HvqComposeJob must be 48 bytes");
 #endif
 
 
+/* one plane of one picture of the rank launch (hvq_rank.hip, hvq_rank_pictures): three jobs a picture, Y, U, V.  `src` and `dst` are
+ * planes of ny rows of nx samples, dense (pitch nx: a multiple of 4, as both addresses are).  The plane's operation and radii stand in
+ * the job itself: there is no table behind the jobs.  Grid row = picture, its three jobs one behind the other; a workgroup of
+ * HVQ_RK_LANES lanes takes a tile of one plane -- HVQ_RK_TW x HVQ_RK_TH targets in the min/max and median bodies, HVQ_RK_CTW x
+ * HVQ_RK_CTH in the copy body: tiles_x tiles side by side, `tiles` in all; the workgroups of a grid row walk the tiles of Y, then U, then
+ * V, those past them leave.  Every member is a dword or a qword (scalar loads); 48 bytes. */
+#define HVQ_RK_LANES  256u
+#define HVQ_RK_TW     64u           /* targets a tile is wide: 16 dwords, one store a lane */
+#define HVQ_RK_TH     16u           /* its rows: lane l owns dword l & 15 of row l >> 4 */
+#define HVQ_RK_CTW    256u          /* the copy body's tile: a wave moves 256 adjacent bytes of a row, a lane four rows 4 apart */
+#define HVQ_RK_CTH    16u
+#define HVQ_RK_MAX_R  15u           /* the largest radius: HVQ_RNK_MAX_RADIUS */
+#define HVQ_RK_HALO   16u           /* bytes staged left and right of a tile's 64: the radius rounded up to whole dwords */
+#define HVQ_RK_ROW_DWORDS ((HVQ_RK_TW + 2u * HVQ_RK_HALO) / 4u)   /* 24 */
+#define HVQ_RK_MAX_ROWS (HVQ_RK_TH + 2u * HVQ_RK_MAX_R)          /* 46 staged rows at the most */
+#define HVQ_RK_BUF    (HVQ_RK_MAX_ROWS * HVQ_RK_ROW_DWORDS)      /* dwords of one of the five LDS arrays */
+#define HVQ_RK_SORTED (HVQ_RK_TH * HVQ_RK_ROW_DWORDS)            /* dwords of one level of the medians' sorted columns */
+#define HVQ_RK_COPY   0u
+#define HVQ_RK_MINMAX 1u
+#define HVQ_RK_MED3   2u
+#define HVQ_RK_MED5   3u
+typedef struct HvqRankJob {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint32_t nx, ny;                   /* samples of the plane: nx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t body;                     /* HVQ_RK_COPY, HVQ_RK_MINMAX, HVQ_RK_MED3 or HVQ_RK_MED5 */
+    uint32_t op;                       /* HVQ_RNK_MIN, MAX or RANGE for the min/max body (a median of radius 0 runs it as MIN) */
+    uint32_t rx, ry;                   /* the radii, 0 .. HVQ_RK_MAX_R */
+} HvqRankJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqRankJob) == 48 && sizeof(HvqRankJob) % 16 == 0, "HvqRankJob must be 48 bytes: job tables are uploaded in 16-byte units");
+static_assert(HVQ_RK_TW * HVQ_RK_TH == HVQ_RK_LANES * 4u && HVQ_RK_TW == 64u, "a lane stores one dword of the tile");
+static_assert(HVQ_RK_CTW == 64u * 4u && HVQ_RK_CTH * 64u == HVQ_RK_LANES * 4u, "the copy body: 64 lanes side by side, four waves, four rows a lane");
+static_assert(HVQ_RK_HALO >= HVQ_RK_MAX_R + 1u && HVQ_RK_HALO % 4u == 0, "the staged row: whole dwords that hold the halo; an unaligned read takes the dword behind");
+static_assert(HVQ_RK_BUF <= 5u * HVQ_RK_LANES && HVQ_RK_MAX_ROWS * 16u <= 3u * HVQ_RK_LANES, "a lane takes five dwords of a staged array, three of a tile-wide one");
+static_assert(5u * HVQ_RK_SORTED <= 4u * HVQ_RK_BUF && HVQ_RK_SORTED <= 2u * HVQ_RK_LANES, "the sorted columns of the 5 x 5 median fit behind the staged rows");
+#else
+_Static_assert(sizeof(HvqRankJob) == 48, "HvqRankJob must be 48 bytes");
+#endif
+
+
 #endif

@@ -43,6 +43,7 @@
 #include "hvq_phash.h"
 #include "hvq_scale.h"
 #include "hvq_filter.h"
+#include "hvq_rank.h"
 #include "hvq_warp.h"
 #include "hvq_compose.h"
 
@@ -94,6 +95,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_hash_nearest(const uint64
 extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_filter.hip.  Weak for the same reason: hvq_filter_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_rank.hip.  Weak for the same reason: hvq_rank_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_rank(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
@@ -387,6 +390,7 @@ struct HvqContext {
     bool cp_force_general = false;     /* hvq_compose_force_general: every layer plane takes the general body of hvq_compose.hip */
     int wp_force = 0;                  /* hvq_warp_force_direct: 0 the chosen body of hvq_warp.hip, 1 the direct one, 2 the tiled one wherever LDS holds the box */
     bool fl_force_filter = false;      /* hvq_filter_force_filter: identity planes take the filter body of hvq_filter.hip, not the copy body */
+    bool rk_force_general = false;     /* hvq_rank_force_general: planes that are copied take the min/max body of hvq_rank.hip, not the copy body */
     bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
@@ -3112,6 +3116,74 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
     if (!hvq_launch_filter) return fail(HVQ_E_NOGPU, "this build of the library has no filter kernel (hvq_filter.hip is not linked)");
     return export_enqueue(c, up.data(), up.size(), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_filter(t, n, max_tiles, st); });
+}
+
+/* Rank filters on resident pictures in slot layout (include/hvqm4_amd.h: the specification): a member of the export chain like
+ * hvq_filter_pictures: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per
+ * plane, each with its operation and radii; one launch behind the job table on the caller's stream (export_enqueue).  Nothing but the
+ * destinations is written: no scratch memory, no memset. */
+static int rank_plane_check(const HvqRankPlane &p, const char *plane)
+{
+    if (p.op != HVQ_RNK_MIN && p.op != HVQ_RNK_MAX && p.op != HVQ_RNK_RANGE && p.op != HVQ_RNK_MEDIAN) return fail(HVQ_E_ARG, "%s rank: op %d", plane, p.op);
+    if (p.rx < 0 || p.rx > HVQ_RNK_MAX_RADIUS || p.ry < 0 || p.ry > HVQ_RNK_MAX_RADIUS)
+        return fail(HVQ_E_ARG, "%s rank: radii %d, %d outside 0 .. %d", plane, p.rx, p.ry, HVQ_RNK_MAX_RADIUS);
+    if (p.op == HVQ_RNK_MEDIAN && (p.rx != p.ry || p.rx > 2)) return fail(HVQ_E_ARG, "%s rank: a median of radii %d, %d (1 x 1, 3 x 3 or 5 x 5)", plane, p.rx, p.ry);
+    if (p.pad) return fail(HVQ_E_ARG, "%s rank: pad %d (0)", plane, p.pad);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_rank_check(const HvqRank *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = rank_plane_check(r->luma, "luma"); if (rc) return rc; }
+    return rank_plane_check(r->chroma, "chroma");
+}
+
+HVQ_EXPORT int hvq_rank_force_general(HvqContext *c, int on)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = c->rk_force_general ? 1 : 0;
+    c->rk_force_general = on != 0;
+    return was;
+}
+
+HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                 const HvqRank *ranks, int nranks, const int *which, void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_RNK_MAX_RADIUS == (int)HVQ_RK_MAX_R && HVQ_RNK_MIN == (int)HVQ_RK_OP_MIN && HVQ_RNK_MAX == (int)HVQ_RK_OP_MAX &&
+                  HVQ_RNK_RANGE == (int)HVQ_RK_OP_RANGE && HVQ_RNK_MEDIAN == (int)HVQ_RK_OP_MEDIAN, "the header's values are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !ranks))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    if (nranks < 1 || nranks > HVQ_RNK_MAX_RANKS) return fail(HVQ_E_ARG, "%d ranks: one call takes 1 .. %d", nranks, HVQ_RNK_MAX_RANKS);
+    for (int r = 0; r < nranks; ++r) { int rc = hvq_rank_check(ranks + r); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqRankJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nranks) return fail(HVQ_E_ARG, "picture %d: rank %d of %d", i, r, nranks);
+        const uint8_t *sp = a;
+        uint8_t *dp = (uint8_t *)dst[i];
+        uint32_t tiles = 0;
+        for (int p = 0; p < 3; ++p) {
+            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+            const HvqRankPlane &rp = p ? ranks[r].chroma : ranks[r].luma;
+            HvqRankJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_rk_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, (uint32_t)rp.op, (uint32_t)rp.rx, (uint32_t)rp.ry, c->rk_force_general);
+            tiles += j.tiles;
+            sp += (size_t)nx * ny;
+            dp += (size_t)nx * ny;
+        }
+        max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!hvq_launch_rank) return fail(HVQ_E_NOGPU, "this build of the library has no rank kernel (hvq_rank.hip is not linked)");
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqRankJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_rank(t, n, max_tiles, st); });
 }
 
 /* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain:

@@ -844,6 +844,59 @@ int     hvq_compose_pictures(HvqContext *ctx, int nlayers, const int *streams, c
                              const HvqComposeLayer *layers, int ntargets, const HvqComposeDst *dst, void *hip_stream);
 int     hvq_compose_force_general(HvqContext *ctx, int on);
 
+/* Resident pictures through RANK FILTERS into uint8 pictures of THEIR OWN geometry in slot layout, where they lie: for `n` pictures, of
+ * any streams, sizes and samplings, in one kernel launch on the caller's HIP stream and without a host synchronisation, each plane
+ * through the minimum (erosion), the maximum (dilation), their difference (the range, a morphological gradient) or the median of a
+ * rectangular window.  What hvq_filter_pictures cannot be: these select a sample, they are no sums.  Opening and closing are two calls
+ * through `src` (hvqm4_amd.rank builds the steps).  The result composes like hvq_scale_pictures': whatever takes `src` or `ref.ptr`
+ * takes it.  The values are exact by nature -- nothing is rounded -- and this text is the authority for them.
+ *   Planes.    Y goes through rank.luma, U and V through rank.chroma, each at its own resolution: Ny rows x Nx samples a.
+ *   Window.    cx(v) = min(max(v, 0), Nx - 1), cy likewise: the border replicates the edge sample (hvq_filter_pictures' clamps).
+ *              W(y, x) is the multiset of the (2 ry + 1)(2 rx + 1) samples a[cy(y + j - ry)][cx(x + i - rx)], j in [0, 2 ry], i in
+ *              [0, 2 rx]: a clamped coordinate counts as often as it occurs.
+ *   Values.    HVQ_RNK_MIN: min W.  HVQ_RNK_MAX: max W.  HVQ_RNK_RANGE: max W - min W, which lies in 0 .. 255 and needs no clamp.
+ *              HVQ_RNK_MEDIAN: the element of index (|W| - 1) / 2 of W sorted ascending.
+ *   Limits.    MIN, MAX, RANGE: rx and ry each 0 .. HVQ_RNK_MAX_RADIUS, independently.  MEDIAN: rx == ry in {0, 1, 2}: 1 x 1, 3 x 3 or
+ *              5 x 5.  pad is 0.
+ *   Known answers.  Radius 0 copies the plane under MIN, MAX and MEDIAN and gives all zeros under RANGE.  A flat plane stays flat, and
+ *              RANGE of a flat plane is 0.  A single 0 in a plane of 255 at (y, x) becomes under MIN exactly the rectangle [y - ry,
+ *              y + ry] x [x - rx, x + rx] cut at the plane, of zeros; the same holds for a 255 in zeros under MAX.  MAX(a) == 255 -
+ *              MIN(255 - a).  MEDIAN(255 - a) == 255 - MEDIAN(a).  A single outlier vanishes under MEDIAN 3 x 3.  MEDIAN 3 x 3 of {0, 0,
+ *              0; 0, 255, 255; 255, 255, 255} at its centre is 255 (five of the nine).  At a corner of the plane the corner sample
+ *              counts four times (3 x 3): {9, 1; 1, 1} has the median 1 at (0, 0) -- W = {9, 9, 9, 9, 1, 1, 1, 1, 1} -- and {9, 9; 1, 1}
+ *              has 9 there.
+ *   hvq_rank_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL record or, in either plane: an op outside the four values; a radius
+ *              outside 0 .. HVQ_RNK_MAX_RADIUS; MEDIAN with rx != ry or a radius above 2; a pad that is not 0.
+ *   The call.  Output i has the geometry of its source, in slot layout (Y | U | V tightly packed): dst[i] is a non-null DEVICE pointer,
+ *              a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  dst[i] must not overlap any source of the call: the
+ *              caller's business, not checked.  which[i] selects ranks[which[i]]; which == NULL: ranks[0] for all.  nranks is
+ *              1 .. HVQ_RNK_MAX_RANKS; every entry of the table is checked, used or not.
+ *   Bodies.    A plane that is copied (radius 0 under MIN, MAX or MEDIAN) takes the kernel's copy body, MIN / MAX / RANGE the min/max
+ *              body (windows by doubling: its cost grows with the logarithm of the radius), MEDIAN 3 x 3 and 5 x 5 an exchange network
+ *              each.  The values do not depend on it.  hvq_rank_force_general(ctx, 1) makes every later call of the context run the
+ *              planes that are copied through the min/max body at radius 0 (0: the chosen one again) and returns the setting before:
+ *              for tests that compare the two with ==.
+ *   HVQ_E_ARG for the whole call: what hvq_rank_check refuses; nranks outside 1 .. 64; a which[i] outside 0 .. nranks - 1; a null or
+ *              misaligned dst[i]; n above 65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no multiple
+ *              of 16; a NULL context, ranks or dst.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is
+ *              enqueued: a refused call leaves every destination untouched.  HVQ_E_NOGPU (after those checks) from a build without
+ *              the rank kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_scale_pictures'. */
+#define HVQ_RNK_MIN    0
+#define HVQ_RNK_MAX    1
+#define HVQ_RNK_RANGE  2
+#define HVQ_RNK_MEDIAN 3
+#define HVQ_RNK_MAX_RADIUS 15
+#define HVQ_RNK_MAX_RANKS  64
+typedef struct HvqRankPlane { int32_t op, rx, ry, pad; } HvqRankPlane;
+typedef struct HvqRank      { HvqRankPlane luma, chroma; } HvqRank;          /* chroma serves U and V, at their own resolution */
+int     hvq_rank_check(const HvqRank *r);
+int     hvq_rank_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                          const HvqRank *ranks, int nranks, const int *which, void *const *dst, void *hip_stream);
+int     hvq_rank_force_general(HvqContext *ctx, int on);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
