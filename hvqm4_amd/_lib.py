@@ -88,6 +88,14 @@ class HvqRank(C.Structure):                     # an entry of hvq_rank_pictures:
     _fields_ = [("luma", HvqRankPlane), ("chroma", HvqRankPlane)]
 
 
+class HvqTablePlane(C.Structure):               # include/hvqm4_amd.h: a plane's table kind (HVQ_TBL_*) and its parameters
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("pad", C.c_int32)]
+
+
+class HvqTableRule(C.Structure):                # an entry of hvq_histogram_tables: luma for Y, chroma for U and V
+    _fields_ = [("luma", HvqTablePlane), ("chroma", HvqTablePlane)]
+
+
 class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
     _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
 
@@ -188,6 +196,10 @@ SYMBOLS = {
     "hvq_rank_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "hvq_rank_force_general": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_map_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "hvq_table_check": (C.c_int, [C.c_void_p]),
+    "hvq_histogram_tables": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_check": (C.c_int, [C.c_void_p]),
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),

@@ -692,12 +692,13 @@ class Context:
         check(lib().hvq_rank_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_d, stream))
         return out
 
-    def morph_pictures(self, sids, ordinals, steps, out=None):
+    def morph_pictures(self, sids, ordinals, steps, out=None, src=None):
         """resident pictures (sids[i], ordinals[i]) through a list of rank steps (hvqm4_amd.rank.opening / closing, or any list of
         rank.Rank), one rank_pictures a step on torch's current stream: the first from the resident pictures, every later one from the
         result before it through src=.  The results between the steps alternate between two scratch tensors of the output's form; the
         last lands in `out` (rank_pictures' rules; default: a new one).  No host synchronisation.  -> rank_pictures' return forms.
-        hvqm4_amd.rank.of_steps gives the expected bytes."""
+        `src` as in rank_pictures: the first step then reads the caller's memory (a mask of map_pictures, say).  hvqm4_amd.rank.of_steps
+        gives the expected bytes."""
         from . import rank as rk
         steps = rk.as_steps(steps)
         n = len(sids)
@@ -705,11 +706,126 @@ class Context:
         for k, step in enumerate(steps):
             dst = out if k == len(steps) - 1 else spare
             if cur is None:
-                res = self.rank_pictures(sids, ordinals, step, out=dst)
+                res = self.rank_pictures(sids, ordinals, step, src=src, out=dst)
             else:
                 res = self.rank_pictures(sids, [-1] * n, step, src=[cur[i] for i in range(n)], out=dst)
             spare, cur = cur, res
         return cur
+
+    def map_pictures(self, sids, ordinals, tables, planes=7, src=None, out=None):
+        """hvq_map_pictures: resident pictures (sids[i], ordinals[i]) through lookup tables, out = table[plane][in], nothing rounded
+        (include/hvqm4_amd.h), into uint8 pictures of their own geometry IN SLOT LAYOUT (Y | U | V), on torch's current stream, without
+        a host synchronisation and without moving a picture.  `tables`: one hvqm4_amd.maps.Table, a list of one per picture (equal
+        ones share a record), or a uint8 CUDA tensor [m, 3, 256] with m 1 (for all) or n (one each), contiguous, 16-byte aligned: it
+        is read when the work runs, so an earlier call on the stream (histogram_tables) may write it, and the caller keeps it alive
+        until then.  `planes`: the mask of the planes that are looked up (1 Y, 2 U, 4 V); the others are copied.  Return forms and
+        `out` are rank_pictures', except that an `out` row may BE the `src` row of the same picture (in place).  hvqm4_amd.maps builds
+        tables and gives the expected bytes (of_picture).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
+        import torch
+        from . import maps
+        from .checksums import sources
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if isinstance(planes, bool) or not isinstance(planes, int) or not 1 <= planes <= 7:
+            raise ValueError(f"planes {planes!r}: a mask of the bits 0 .. 2, not 0")
+        which = None
+        if isinstance(tables, torch.Tensor):
+            if tables.dtype != torch.uint8 or tables.dim() != 3 or tuple(tables.shape[1:]) != (3, 256) or not tables.is_contiguous():
+                raise ValueError("tables must be a contiguous uint8 tensor of shape (m, 3, 256)")
+            if n and tables.shape[0] not in (1, n):
+                raise ValueError(f"{tables.shape[0]} tables for {n} pictures: 1, or one per picture")
+            if tables.data_ptr() & 15:
+                raise ValueError(f"tables: pointer {tables.data_ptr():#x} must be a multiple of 16")
+            if tables.device.type != "cuda":
+                raise ValueError(f"tables is on {tables.device}, not a GPU")
+            dev_tables = tables
+        else:
+            if isinstance(tables, maps.Table):
+                records = [tables]
+            else:
+                if not isinstance(tables, (list, tuple)) or len(tables) != n:
+                    raise ValueError(f"tables: one maps.Table, a list of {n}, or a uint8 CUDA tensor [m, 3, 256]")
+                index, records, which = {}, [], []
+                for t in tables:
+                    if not isinstance(t, maps.Table):
+                        raise ValueError(f"tables: an entry is a maps.Table, not {type(t).__name__}")
+                    if t not in index:
+                        index[t] = len(records)
+                        records.append(t)
+                    which.append(index[t])
+            dev_tables = None
+        streams = set(sids)
+        pb = {s: self.pic_bytes(s) for s in streams}
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        nb = [pb[s] for s in sids]
+        uniform = len({self._geometry(s) for s in streams}) <= 1
+        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
+        if not n:
+            return out
+        if dev_tables is None:
+            dev_tables = torch.from_numpy(maps.pack(records)).to(device)         # uploaded on the current stream, in front of the launch; torch frees it in stream order
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
+        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_map_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(dev_tables.data_ptr()), int(dev_tables.shape[0]), a_w,
+                                     planes, a_d, stream))
+        return out
+
+    def histogram_tables(self, hist, rules, out=None):
+        """hvq_histogram_tables: tables from the histogram records where they lie -- `hist` is picture_histograms' result without a
+        reference, an int32 CUDA tensor [n, 3, 256] -- in one launch on torch's current stream, without a host synchronisation ->
+        uint8 CUDA tensor [n, 3, 256] (`out`, if given: such a tensor, contiguous, 16-byte aligned; it is overwritten whole), which
+        map_pictures takes as it is.  `rules`: one hvqm4_amd.maps.Rule (equalize(), stretch(), otsu(), flat(c)) or a list of one per
+        record (more than 64 distinct ones: ValueError).  hvqm4_amd.maps.tables_of_records gives the expected tables."""
+        import torch
+        from . import maps
+        if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int32 or hist.dim() != 3 or tuple(hist.shape[1:]) != (3, 256) or not hist.is_contiguous():
+            raise ValueError("hist must be a contiguous int32 tensor of shape (n, 3, 256)")
+        n = int(hist.shape[0])
+        if n > 65535:
+            raise ValueError(f"{n} records: one call takes 65535 at the most")
+        if hist.data_ptr() & 15:
+            raise ValueError(f"hist: pointer {hist.data_ptr():#x} must be a multiple of 16")
+        if isinstance(rules, maps.Rule):
+            table, which = [rules], None
+        else:
+            if not isinstance(rules, (list, tuple)) or len(rules) != n:
+                raise ValueError(f"rules: one maps.Rule, or a list of {n}")
+            index, table, which = {}, [], []
+            for r in rules:
+                if not isinstance(r, maps.Rule):
+                    raise ValueError(f"rules: an entry is a maps.Rule, not {type(r).__name__}")
+                if r not in index:
+                    index[r] = len(table)
+                    table.append(r)
+                which.append(index[r])
+            if len(table) > maps.MAX_RULES:
+                raise ValueError(f"{len(table)} distinct rules: one call takes {maps.MAX_RULES} at the most")
+        for r in table:
+            maps.check(r)
+        if hist.device.type != "cuda":
+            raise ValueError(f"hist is on {hist.device}, not a GPU")
+        out = Context._out_tensor(out, (n, 3, 256), torch.uint8, device=hist.device, align=16)
+        if not n:
+            return out
+        stream = Context._launch_args(out.device, (), ())[2]
+        from ._lib import HvqTableRule
+        a_r = (HvqTableRule * len(table))(*[r.struct() for r in table])
+        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        check(lib().hvq_histogram_tables(self._h, n, C.c_void_p(hist.data_ptr()), C.cast(a_r, C.c_void_p), len(table), a_w, C.c_void_p(out.data_ptr()), stream))
+        return out
+
+    def equalize_pictures(self, sids, ordinals, rules=None, src=None, out=None):
+        """resident pictures (sids[i], ordinals[i]) through tables made of their own histograms: picture_histograms ->
+        histogram_tables(rules) -> map_pictures, three launches on torch's current stream, no host synchronisation; the histogram and
+        table tensors are scratch.  `rules`: histogram_tables' (default: hvqm4_amd.maps.equalize().luma_only(), equalisation of Y with
+        U and V as they are); maps.stretch() gives automatic levels, maps.otsu() a mask.  `src`, `out` and the return forms are
+        map_pictures'.  The expected bytes: maps.of_picture with maps.tables_of_records of histograms.of_picture."""
+        from . import maps
+        if rules is None:
+            rules = maps.equalize().luma_only()
+        hist = self.picture_histograms(sids, ordinals, src=src)
+        tables = self.histogram_tables(hist, rules)
+        return self.map_pictures(sids, ordinals, tables, src=src, out=out)      # torch frees the scratch in stream order
 
     def warp_force_direct(self, on) -> int:
         """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen

@@ -718,4 +718,44 @@ _Static_assert(sizeof(HvqRankJob) == 48, "HvqRankJob must be 48 bytes");
 #endif
 
 
+/* one plane of one picture of the map launch (hvq_map.hip, hvq_map_pictures): three jobs a picture, Y, U, V.  A point operation does not
+ * look at rows: `src` and `dst` are the plane's `dwords` dwords, dense.  `table` is the device address of the plane's 256 table bytes
+ * (a multiple of 16: record which[i], plane p); a plane that is copied (its bit of `planes` is clear) has body HVQ_MP_COPY and table 0.
+ * Grid row = picture, its three jobs one behind the other; a workgroup of HVQ_MP_LANES lanes takes a tile of HVQ_MP_TILE consecutive
+ * dwords of one plane, a lane HVQ_MP_PER dwords HVQ_MP_LANES apart: the workgroups of a grid row walk the tiles of Y, then U, then V, those
+ * past them leave.  Every member is a dword or a qword (scalar loads); 48 bytes. */
+#define HVQ_MP_LANES  256u
+#define HVQ_MP_PER    8u
+#define HVQ_MP_TILE   (HVQ_MP_LANES * HVQ_MP_PER)     /* 2048 dwords = 8 KiB of a plane: 32 bytes looked up for every table byte staged */
+#define HVQ_MP_COPY   0u
+#define HVQ_MP_LOOKUP 1u
+typedef struct HvqMapJob {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4; may equal src */
+    uint64_t table;                    /* device address of the plane's uint8 [256], a multiple of 16 (0 in the copy body) */
+    uint32_t dwords;                   /* dwords of the plane */
+    uint32_t tiles;                    /* ceil(dwords / HVQ_MP_TILE) */
+    uint32_t body;                     /* HVQ_MP_COPY or HVQ_MP_LOOKUP */
+    uint32_t pad[3];
+} HvqMapJob;
+
+/* one histogram record of the table launch (hvq_map.hip, hvq_histogram_tables): grid row = record, grid column = plane; a workgroup of
+ * HVQ_TB_LANES lanes, lane v holding bin v, writes the plane's 256 table bytes.  rule[0] serves Y, rule[1] U and V.  48 bytes. */
+#define HVQ_TB_LANES 256u
+typedef struct HvqTableJob {
+    uint64_t hist;                     /* device address of the record, uint32 [3][256], a multiple of 16 */
+    uint64_t out;                      /* device address of the table record, uint8 [3][256], a multiple of 16 */
+    struct { uint32_t kind, a, b, pad; } rule[2];
+} HvqTableJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqMapJob) == 48 && sizeof(HvqMapJob) % 16 == 0, "HvqMapJob must be 48 bytes: job tables are uploaded in 16-byte units");
+static_assert(sizeof(HvqTableJob) == 48 && sizeof(HvqTableJob) % 16 == 0, "HvqTableJob must be 48 bytes: job tables are uploaded in 16-byte units");
+static_assert(HVQ_MP_LANES == 256u && HVQ_TB_LANES == 256u, "a lane stages one table byte; lane v holds bin v");
+#else
+_Static_assert(sizeof(HvqMapJob) == 48, "HvqMapJob must be 48 bytes");
+_Static_assert(sizeof(HvqTableJob) == 48, "HvqTableJob must be 48 bytes");
+#endif
+
+
 #endif

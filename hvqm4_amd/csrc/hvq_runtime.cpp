@@ -44,6 +44,7 @@
 #include "hvq_scale.h"
 #include "hvq_filter.h"
 #include "hvq_rank.h"
+#include "hvq_map.h"
 #include "hvq_warp.h"
 #include "hvq_compose.h"
 
@@ -97,6 +98,9 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_de
 extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_rank.hip.  Weak for the same reason: hvq_rank_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_rank(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_map.hip.  Weak for the same reason: hvq_map_pictures and hvq_histogram_tables then refuse with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_map(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_tables(const void *jobs_dev, int nrecords, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
@@ -3184,6 +3188,100 @@ HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const
     if (!hvq_launch_rank) return fail(HVQ_E_NOGPU, "this build of the library has no rank kernel (hvq_rank.hip is not linked)");
     return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqRankJob), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_rank(t, n, max_tiles, st); });
+}
+
+/* Lookup tables on resident pictures in slot layout (include/hvqm4_amd.h: the specification): a member of the export chain like
+ * hvq_rank_pictures: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane,
+ * each with the device address of its 256 table bytes; one launch behind the job table on the caller's stream (export_enqueue): the
+ * tables are read when it runs.  Nothing but the destinations is written: no scratch memory, no memset. */
+HVQ_EXPORT int hvq_map_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                const uint8_t *tables, int ntables, const int *which, int planes, void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_MAP_TABLE_BYTES == 3 * 256, "a record is a table of 256 bytes per plane");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    if (!tables || ((uintptr_t)tables & 15u)) return fail(HVQ_E_ARG, "tables must be a non-null multiple of 16");
+    if (ntables < 1 || ntables > 65535) return fail(HVQ_E_ARG, "%d tables: one call takes 1 .. 65535", ntables);
+    if (!which && ntables != 1 && ntables != n) return fail(HVQ_E_ARG, "%d tables for %d pictures without `which` (1, or one per picture)", ntables, n);
+    if (planes < 1 || planes > 7) return fail(HVQ_E_ARG, "planes %d: a mask of the bits 0 .. 2, not 0", planes);
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqMapJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        const int r = which ? which[i] : ntables == 1 ? 0 : i;
+        if (r < 0 || r >= ntables) return fail(HVQ_E_ARG, "picture %d: table %d of %d", i, r, ntables);
+        const uint8_t *sp = a;
+        uint8_t *dp = (uint8_t *)dst[i];
+        uint32_t tiles = 0;
+        for (int p = 0; p < 3; ++p) {
+            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+            HvqMapJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_mp_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, (uint64_t)(uintptr_t)(tables + (size_t)r * HVQ_MAP_TABLE_BYTES + 256u * (size_t)p),
+                           nx, ny, (planes >> p) & 1);
+            tiles += j.tiles;
+            sp += (size_t)nx * ny;
+            dp += (size_t)nx * ny;
+        }
+        max_tiles = std::max(max_tiles, tiles);
+    }
+    if (!hvq_launch_map) return fail(HVQ_E_NOGPU, "this build of the library has no map kernel (hvq_map.hip is not linked)");
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqMapJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_map(t, n, max_tiles, st); });
+}
+
+/* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job
+ * table through export_enqueue like the chain's members, so it is ordered behind an hvq_picture_histograms on the same stream. */
+static int table_plane_check(const HvqTablePlane &p, const char *plane)
+{
+    if (p.kind < HVQ_TBL_IDENTITY || p.kind > HVQ_TBL_OTSU) return fail(HVQ_E_ARG, "%s table: kind %d", plane, p.kind);
+    if (p.pad) return fail(HVQ_E_ARG, "%s table: pad %d (0)", plane, p.pad);
+    if (p.kind == HVQ_TBL_FLAT) {
+        if (p.a < 0 || p.a > 255 || p.b) return fail(HVQ_E_ARG, "%s table: FLAT with a %d, b %d (a in 0 .. 255, b 0)", plane, p.a, p.b);
+    } else if (p.kind == HVQ_TBL_STRETCH) {
+        if (p.a < 0 || p.a > 499 || p.b < 0 || p.b > 499) return fail(HVQ_E_ARG, "%s table: STRETCH with clips %d, %d outside 0 .. 499", plane, p.a, p.b);
+    } else if (p.a || p.b) {
+        return fail(HVQ_E_ARG, "%s table: kind %d takes no a, b (%d, %d)", plane, p.kind, p.a, p.b);
+    }
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_table_check(const HvqTableRule *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = table_plane_check(r->luma, "luma"); if (rc) return rc; }
+    return table_plane_check(r->chroma, "chroma");
+}
+
+HVQ_EXPORT int hvq_histogram_tables(HvqContext *c, int n, const uint32_t *hist, const HvqTableRule *rules, int nrules, const int *which,
+                                    uint8_t *tables, void *hip_stream)
+{
+    static_assert(HVQ_TBL_IDENTITY == (int)HVQ_TB_IDENTITY && HVQ_TBL_FLAT == (int)HVQ_TB_FLAT && HVQ_TBL_EQUALIZE == (int)HVQ_TB_EQUALIZE &&
+                  HVQ_TBL_STRETCH == (int)HVQ_TB_STRETCH && HVQ_TBL_OTSU == (int)HVQ_TB_OTSU, "the header's values are the kernel's");
+    if (!c || n < 0) return fail(HVQ_E_ARG, "bad arguments");
+    if (n > 65535) return fail(HVQ_E_ARG, "%d records: one call takes 65535 at the most", n);
+    if (!n) return HVQ_OK;
+    if (!hist || ((uintptr_t)hist & 15u) || !tables || ((uintptr_t)tables & 15u)) return fail(HVQ_E_ARG, "hist and tables must be non-null multiples of 16");
+    if (!rules || nrules < 1 || nrules > HVQ_TBL_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", rules ? nrules : 0, HVQ_TBL_MAX_RULES);
+    for (int r = 0; r < nrules; ++r) { int rc = hvq_table_check(rules + r); if (rc) return rc; }
+    std::vector<HvqTableJob> jobs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nrules) return fail(HVQ_E_ARG, "record %d: rule %d of %d", i, r, nrules);
+        HvqTableJob &j = jobs[(size_t)i];
+        j.hist = (uint64_t)(uintptr_t)(hist + (size_t)i * 3u * HVQ_HIST_BINS);
+        j.out = (uint64_t)(uintptr_t)(tables + (size_t)i * HVQ_MAP_TABLE_BYTES);
+        const HvqTablePlane *pl[2] = { &rules[r].luma, &rules[r].chroma };
+        for (int k = 0; k < 2; ++k) { j.rule[k].kind = (uint32_t)pl[k]->kind; j.rule[k].a = (uint32_t)pl[k]->a; j.rule[k].b = (uint32_t)pl[k]->b; j.rule[k].pad = 0; }
+    }
+    if (!hvq_launch_tables) return fail(HVQ_E_NOGPU, "this build of the library has no table kernel (hvq_map.hip is not linked)");
+    HIPCHK(hipSetDevice(c->device));
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqTableJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_tables(t, n, st); });
 }
 
 /* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain:

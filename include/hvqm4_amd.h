@@ -897,6 +897,78 @@ int     hvq_rank_pictures(HvqContext *ctx, int n, const int *streams, const int 
                           const HvqRank *ranks, int nranks, const int *which, void *const *dst, void *hip_stream);
 int     hvq_rank_force_general(HvqContext *ctx, int on);
 
+/* Resident pictures through LOOKUP TABLES -- a point operation, out = table[in] -- into uint8 pictures of THEIR OWN geometry in slot
+ * layout, where they lie: for `n` pictures, of any streams, sizes and samplings, in one kernel launch on the caller's HIP stream and
+ * without a host synchronisation.  Equalisation, levels, gamma, inversion, posterising and binarisation are tables (hvqm4_amd.maps
+ * builds them; hvq_histogram_tables below builds the ones that depend on the picture, on the GPU).  The result composes like
+ * hvq_rank_pictures': whatever takes `src` or `ref.ptr` takes it.  This text is the authority for the bytes.
+ *   Values.    Plane p (0 Y, 1 U, 2 V) of output i is T[p][a] for every sample a of plane p of the source, T = table which[i]: a record
+ *              of uint8 [3][256], HVQ_MAP_TABLE_BYTES bytes.  Nothing is rounded.
+ *   Known answers.  The identity table copies.  T[v] = 255 - v inverts.  Applying a table that is a permutation and then the table of
+ *              its inverse permutation gives the source back.  A constant table gives a flat plane.
+ *   Tables.    `tables` is a DEVICE pointer, a non-null multiple of 16: `ntables` records, dense.  They are read when the work runs on
+ *              `hip_stream`, not at the call: an earlier launch on that stream may write them (hvq_histogram_tables).  ntables is
+ *              1 .. 65535.  `which` is a HOST array: picture i takes record which[i].  which == NULL: ntables == 1 (every picture takes
+ *              record 0) or ntables == n (picture i takes record i); anything else is HVQ_E_ARG.  Every byte value is a valid entry: the
+ *              contents are not checked.
+ *   planes.    A mask of the bits 0 .. 2 (Y, U, V).  A plane whose bit is clear is copied, not looked up (the kernel's copy body).  0 and
+ *              values above 7 are HVQ_E_ARG.
+ *   The call.  Output i has the geometry of its source, in slot layout (Y | U | V tightly packed): dst[i] is a non-null DEVICE pointer,
+ *              a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  dst[i] MAY EQUAL src[i] exactly (in place on the
+ *              caller's memory): a lane reads only the dwords that it later writes.  Any other overlap of a destination with a source
+ *              or another destination is the caller's business, not checked.
+ *   Kernel.    A tile is HVQ_MP_TILE = 2048 consecutive dwords (8 KiB) of a plane; its workgroup stages the plane's 256 table bytes
+ *              once.
+ *   HVQ_E_ARG for the whole call: null or misaligned tables; ntables outside 1 .. 65535; which == NULL with ntables other than 1 or n;
+ *              a which[i] outside 0 .. ntables - 1; planes outside 1 .. 7; a null or misaligned dst[i]; n above 65535; a bad stream or
+ *              ordinal; a src[i] with an ordinal other than -1 or that is no multiple of 16; a NULL context or dst.  n == 0 is HVQ_OK
+ *              and does nothing.  Every argument is checked before anything is enqueued: a refused call leaves every destination
+ *              untouched.  HVQ_E_NOGPU (after those checks) from a build without the map kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_rank_pictures'. */
+#define HVQ_MAP_TABLE_BYTES 768                     /* uint8 [3 planes Y, U, V][256] */
+int     hvq_map_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                         const uint8_t *tables, int ntables, const int *which, int planes, void *const *dst, void *hip_stream);
+
+/* TABLES FROM HISTOGRAM RECORDS, on the GPU: `hist` is `n` records exactly as hvq_picture_histograms writes them in HVQ_HIST_VALUES mode
+ * (DEVICE memory, uint32 [3][256], 3072 bytes each, dense), `tables` `n` records of HVQ_MAP_TABLE_BYTES bytes in DEVICE memory; both
+ * non-null multiples of 16.  One launch on the caller's stream, ordered behind whatever that stream holds, a member of the export chain;
+ * every byte of `tables` is written, nothing else.  Record i goes through rules[which[i]] (which == NULL: rules[0] for all): luma for
+ * plane Y, chroma for U and for V, each from its own histogram.  The entries are exact integers.  With h the plane's bins, N = sum h,
+ * C(v) = h[0] + .. + h[v], and x_k (k from 1) the k-th smallest sample, i. e. the smallest v with C(v) >= k; `//` floors:
+ *   HVQ_TBL_IDENTITY  lut[v] = v.
+ *   HVQ_TBL_FLAT      lut[v] = a.
+ *   N == 0            the identity, for each of the three kinds below.
+ *   HVQ_TBL_EQUALIZE  C_min = the count of the smallest occurring value, D = N - C_min.  lut[v] = (2 * 255 * max(C(v) - C_min, 0) + D) //
+ *                     (2 D); the identity when D == 0.  (hvqm4_amd.histograms.equalize_lut.)
+ *   HVQ_TBL_STRETCH   a = clip_lo, b = clip_hi, per mille of the samples.  lo = x_k with k = max(1, ceil(a N / 1000)); hi = x_k with
+ *                     k = max(1, ceil((1000 - b) N / 1000)) (the rank rule of histograms.percentile).  The identity when hi <= lo;
+ *                     otherwise lut[v] = 0 for v <= lo, 255 for v >= hi, and (2 * 255 * (v - lo) + (hi - lo)) // (2 (hi - lo)) between.
+ *   HVQ_TBL_OTSU      with n0 = C(t), n1 = N - n0, s0 = sum of v h[v] over v <= t, s1 the same over v > t and d = s0 n1 - s1 n0: t is the
+ *                     t in 0 .. 254 with n0 > 0 and n1 > 0 that maximises d^2 / (n0 n1), the smallest such t on a tie, and 0 when there
+ *                     is none (a single value).  Two scores compare exactly as d_a^2 (n0 n1)_b against d_b^2 (n0 n1)_a, in 192 bits.
+ *                     lut[v] = 255 if v > t, else 0.  (histograms.otsu.)
+ *   A record with N above 2^26 (no plane the library opens has more samples): the contents of its tables are unspecified; the call
+ *   still writes only its bytes and computes in unsigned arithmetic that wraps.
+ *   hvq_table_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL record or, in either plane: a kind outside the five; FLAT with a
+ *   outside 0 .. 255; STRETCH with a or b outside 0 .. 499; a pad that is not 0; an a or b that is not 0 where the kind takes none (b
+ *   under FLAT; both under IDENTITY, EQUALIZE and OTSU).
+ *   HVQ_E_ARG for the whole call: what hvq_table_check refuses, in any entry, used or not; nrules outside 1 .. HVQ_TBL_MAX_RULES; a
+ *   which[i] outside 0 .. nrules - 1; null or misaligned hist / tables; NULL rules; n above 65535; a NULL context.  n == 0 is HVQ_OK and
+ *   does nothing.  Everything is checked before anything is enqueued.  HVQ_E_NOGPU (after those checks) from a build without the kernel. */
+#define HVQ_TBL_IDENTITY 0
+#define HVQ_TBL_FLAT     1   /* a = the value */
+#define HVQ_TBL_EQUALIZE 2
+#define HVQ_TBL_STRETCH  3   /* a = clip_lo, b = clip_hi, per mille of the samples, each 0 .. 499 */
+#define HVQ_TBL_OTSU     4
+#define HVQ_TBL_MAX_RULES 64
+typedef struct HvqTablePlane { int32_t kind, a, b, pad; } HvqTablePlane;
+typedef struct HvqTableRule  { HvqTablePlane luma, chroma; } HvqTableRule;   /* chroma serves U and V, each from its own histogram */
+int     hvq_table_check(const HvqTableRule *r);
+int     hvq_histogram_tables(HvqContext *ctx, int n, const uint32_t *hist, const HvqTableRule *rules, int nrules, const int *which,
+                             uint8_t *tables, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
