@@ -254,6 +254,65 @@ class Context:
         return out, device, where
 
     @staticmethod
+    def _slot_frame(ctx, sids, ordinals, src, out):
+        """what the calls that write pictures of the sources' own geometry share (filter, rank, map), after their own checks: the
+        sources and _slot_outputs -> (ptrs, out, device, where)"""
+        from .checksums import sources
+        streams = set(sids)
+        pb = {s: ctx.pic_bytes(s) for s in streams}                        # a call usually repeats few streams: each is looked at once
+        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
+        uniform = len({ctx._geometry(s) for s in streams}) <= 1
+        return (ptrs,) + Context._slot_outputs(out, [pb[s] for s in sids], uniform, "geometries")
+
+    @staticmethod
+    def _table_which(arg, n, cls, name, kind, most=None, nouns=None, also=""):
+        """one `cls` for all n pictures (or records), or a list of n -> (table, which): equal entries share an entry of `table`, which
+        `which` indexes per picture (None: the one for all).  For the messages: name, the argument's; kind, the class's; also, what
+        else the argument may be; and `most` distinct entries (None: any number) called `nouns`"""
+        if isinstance(arg, cls):
+            return [arg], None
+        if not isinstance(arg, (list, tuple)) or len(arg) != n:
+            raise ValueError(f"{name}: one {kind}, {'' if also else 'or '}a list of {n}{also}")
+        index, table, which = {}, [], []
+        for e in arg:
+            if not isinstance(e, cls):
+                raise ValueError(f"{name}: an entry is a {kind}, not {type(e).__name__}")
+            if e not in index:
+                index[e] = len(table)
+                table.append(e)
+            which.append(index[e])
+        if most is not None and len(table) > most:
+            raise ValueError(f"{len(table)} distinct {nouns}: one call takes {most} at the most")
+        return table, which
+
+    @staticmethod
+    def _which_array(which, n):
+        """_table_which's `which` -> int[n], or None"""
+        return None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+
+    @staticmethod
+    def _target_shapes(geoms, sids, wanted, one, shape):
+        """the target shapes of a call (scale, warp).  A call usually repeats few: each distinct (source geometry, *what is wanted of
+        picture i) is looked at once, by shape(*key) -> a tuple.  geoms: _geometry per stream; wanted: lists of one entry per
+        picture; one: every list repeats one entry.  -> (shapes, column): the tuples by key, and column(j) = element j of picture i's
+        tuple for every i (broadcast: the bare element where all pictures share it)"""
+        n = len(sids)
+        if n and one and len(set(geoms.values())) == 1:
+            keys = [(geoms[sids[0]],) + tuple(v[0] for v in wanted)] * n
+            distinct = keys[:1]
+        else:
+            keys = list(zip(map(geoms.__getitem__, sids), *wanted))
+            distinct = set(keys)
+        shapes = {key: shape(*key) for key in distinct}
+
+        def column(j, broadcast=False):
+            if len(shapes) == 1:
+                v = shapes[keys[0]][j]
+                return v if broadcast else [v] * n
+            return [shapes[k][j] for k in keys]
+        return shapes, column
+
+    @staticmethod
     def _ref_array(refs):
         """metrics.references' result -> HvqMetricsRef[n], or None"""
         from .metrics import HvqMetricsRef
@@ -562,31 +621,21 @@ class Context:
             raise ValueError("size: every picture needs a target size")
         samplings, one_sampling = sc.per_picture(sampling, n, 2, "sampling")
         crops, one_crop = sc.per_picture(crop, n, 4, "crop")
-        # a call usually repeats few shapes: each distinct (source geometry, size, sampling, crop) is looked at once
-        geoms = {s: self._geometry(s) for s in streams}
-        if n and one_size and one_sampling and one_crop and len(set(geoms.values())) == 1:
-            keys = [(geoms[sids[0]], sizes[0], samplings[0], crops[0])] * n
-            distinct = keys[:1]
-        else:
-            keys = list(zip(map(geoms.__getitem__, sids), sizes, samplings, crops))
-            distinct = set(keys)
-        shapes = {}
-        for key in distinct:
-            g, sz, sm, cr = key
+        def shape(g, sz, sm, cr):
             dst = sz + (sm or g[2:])
             sc.plane_sizes(g, dst, cr)                                    # ValueError beyond the library's limits
-            shapes[key] = (dst, sc.nbytes(*dst), dst + (cr or (0, 0, 0, 0)))
+            return dst, sc.nbytes(*dst), dst + (cr or (0, 0, 0, 0))
+        geoms = {s: self._geometry(s) for s in streams}
+        shapes, column = Context._target_shapes(geoms, sids, (sizes, samplings, crops), one_size and one_sampling and one_crop, shape)
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
-        dst_geoms = {v[0] for v in shapes.values()}
-        uniform = len(dst_geoms) == 1
-        nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
-        out, device, where = Context._slot_outputs(out, nb, uniform, "target geometries")
+        uniform = len({v[0] for v in shapes.values()}) == 1
+        out, device, where = Context._slot_outputs(out, column(1), uniform, "target geometries")
         if not n:
             return out
         a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         a_d = np.empty(n, dtype=_SCALE_DST)                                  # HvqScaleDst[n]
         a_d["ptr"] = where
-        a_d["rest"] = shapes[keys[0]][2] if len(shapes) == 1 else [shapes[k][2] for k in keys]
+        a_d["rest"] = column(2, broadcast=True)
         check(lib().hvq_scale_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(a_d.ctypes.data), stream))
         return out
 
@@ -606,37 +655,17 @@ class Context:
         takes a row of the result.  hvqm4_amd.filters builds the filters and gives the expected bytes (of_picture).  `src` as in
         picture_checksums.  Ordering and slot safety are export()'s."""
         from . import filters as fl
-        from .checksums import sources
         n = Context._pictures(self._geom, sids, ordinals, limit=True)
-        if isinstance(filt, fl.Filter):
-            table, which = [filt], None
-        else:
-            if not isinstance(filt, (list, tuple)) or len(filt) != n:
-                raise ValueError(f"filt: one filters.Filter, or a list of {n}")
-            index, table, which = {}, [], []
-            for f in filt:
-                if not isinstance(f, fl.Filter):
-                    raise ValueError(f"filt: an entry is a filters.Filter, not {type(f).__name__}")
-                if f not in index:
-                    index[f] = len(table)
-                    table.append(f)
-                which.append(index[f])
-            if len(table) > fl.MAX_FILTERS:
-                raise ValueError(f"{len(table)} distinct filters: one call takes {fl.MAX_FILTERS} at the most")
+        table, which = Context._table_which(filt, n, fl.Filter, "filt", "filters.Filter", fl.MAX_FILTERS, "filters")
         for f in table:
             fl.check(f)                                                    # ValueError beyond the library's limits
-        streams = set(sids)
-        pb = {s: self.pic_bytes(s) for s in streams}                       # a call usually repeats few streams: each is looked at once
-        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
-        nb = [pb[s] for s in sids]
-        uniform = len({self._geometry(s) for s in streams}) <= 1
-        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
+        ptrs, out, device, where = Context._slot_frame(self, sids, ordinals, src, out)
         if not n:
             return out
         a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         from ._lib import HvqFilter
         a_f = (HvqFilter * len(table))(*[f.to_struct() for f in table])
-        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_w = Context._which_array(which, n)
         a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
         check(lib().hvq_filter_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_f, C.c_void_p), len(table), a_w, a_d, stream))
         return out
@@ -657,37 +686,17 @@ class Context:
         source).  Whatever takes src= or ref.ptr takes a row of the result.  hvqm4_amd.rank builds the operations and gives the
         expected bytes (of_picture).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
         from . import rank as rk
-        from .checksums import sources
         n = Context._pictures(self._geom, sids, ordinals, limit=True)
-        if isinstance(rank, rk.Rank):
-            table, which = [rank], None
-        else:
-            if not isinstance(rank, (list, tuple)) or len(rank) != n:
-                raise ValueError(f"rank: one rank.Rank, or a list of {n}")
-            index, table, which = {}, [], []
-            for r in rank:
-                if not isinstance(r, rk.Rank):
-                    raise ValueError(f"rank: an entry is a rank.Rank, not {type(r).__name__}")
-                if r not in index:
-                    index[r] = len(table)
-                    table.append(r)
-                which.append(index[r])
-            if len(table) > rk.MAX_RANKS:
-                raise ValueError(f"{len(table)} distinct ranks: one call takes {rk.MAX_RANKS} at the most")
+        table, which = Context._table_which(rank, n, rk.Rank, "rank", "rank.Rank", rk.MAX_RANKS, "ranks")
         for r in table:
             rk.check(r)                                                    # ValueError beyond the library's limits
-        streams = set(sids)
-        pb = {s: self.pic_bytes(s) for s in streams}                       # a call usually repeats few streams: each is looked at once
-        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
-        nb = [pb[s] for s in sids]
-        uniform = len({self._geometry(s) for s in streams}) <= 1
-        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
+        ptrs, out, device, where = Context._slot_frame(self, sids, ordinals, src, out)
         if not n:
             return out
         a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
         from ._lib import HvqRank
         a_r = (HvqRank * len(table))(*[r.struct() for r in table])
-        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_w = Context._which_array(which, n)
         a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
         check(lib().hvq_rank_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_d, stream))
         return out
@@ -723,7 +732,6 @@ class Context:
         tables and gives the expected bytes (of_picture).  `src` as in picture_checksums.  Ordering and slot safety are export()'s."""
         import torch
         from . import maps
-        from .checksums import sources
         n = Context._pictures(self._geom, sids, ordinals, limit=True)
         if isinstance(planes, bool) or not isinstance(planes, int) or not 1 <= planes <= 7:
             raise ValueError(f"planes {planes!r}: a mask of the bits 0 .. 2, not 0")
@@ -739,32 +747,15 @@ class Context:
                 raise ValueError(f"tables is on {tables.device}, not a GPU")
             dev_tables = tables
         else:
-            if isinstance(tables, maps.Table):
-                records = [tables]
-            else:
-                if not isinstance(tables, (list, tuple)) or len(tables) != n:
-                    raise ValueError(f"tables: one maps.Table, a list of {n}, or a uint8 CUDA tensor [m, 3, 256]")
-                index, records, which = {}, [], []
-                for t in tables:
-                    if not isinstance(t, maps.Table):
-                        raise ValueError(f"tables: an entry is a maps.Table, not {type(t).__name__}")
-                    if t not in index:
-                        index[t] = len(records)
-                        records.append(t)
-                    which.append(index[t])
+            records, which = Context._table_which(tables, n, maps.Table, "tables", "maps.Table", also=", or a uint8 CUDA tensor [m, 3, 256]")
             dev_tables = None
-        streams = set(sids)
-        pb = {s: self.pic_bytes(s) for s in streams}
-        ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
-        nb = [pb[s] for s in sids]
-        uniform = len({self._geometry(s) for s in streams}) <= 1
-        out, device, where = Context._slot_outputs(out, nb, uniform, "geometries")
+        ptrs, out, device, where = Context._slot_frame(self, sids, ordinals, src, out)
         if not n:
             return out
         if dev_tables is None:
             dev_tables = torch.from_numpy(maps.pack(records)).to(device)         # uploaded on the current stream, in front of the launch; torch frees it in stream order
         a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
-        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_w = Context._which_array(which, n)
         a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
         check(lib().hvq_map_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(dev_tables.data_ptr()), int(dev_tables.shape[0]), a_w,
                                      planes, a_d, stream))
@@ -785,21 +776,7 @@ class Context:
             raise ValueError(f"{n} records: one call takes 65535 at the most")
         if hist.data_ptr() & 15:
             raise ValueError(f"hist: pointer {hist.data_ptr():#x} must be a multiple of 16")
-        if isinstance(rules, maps.Rule):
-            table, which = [rules], None
-        else:
-            if not isinstance(rules, (list, tuple)) or len(rules) != n:
-                raise ValueError(f"rules: one maps.Rule, or a list of {n}")
-            index, table, which = {}, [], []
-            for r in rules:
-                if not isinstance(r, maps.Rule):
-                    raise ValueError(f"rules: an entry is a maps.Rule, not {type(r).__name__}")
-                if r not in index:
-                    index[r] = len(table)
-                    table.append(r)
-                which.append(index[r])
-            if len(table) > maps.MAX_RULES:
-                raise ValueError(f"{len(table)} distinct rules: one call takes {maps.MAX_RULES} at the most")
+        table, which = Context._table_which(rules, n, maps.Rule, "rules", "maps.Rule", maps.MAX_RULES, "rules")
         for r in table:
             maps.check(r)
         if hist.device.type != "cuda":
@@ -810,7 +787,7 @@ class Context:
         stream = Context._launch_args(out.device, (), ())[2]
         from ._lib import HvqTableRule
         a_r = (HvqTableRule * len(table))(*[r.struct() for r in table])
-        a_w = None if which is None else C.cast((C.c_int * n)(*which), C.c_void_p)
+        a_w = Context._which_array(which, n)
         check(lib().hvq_histogram_tables(self._h, n, C.c_void_p(hist.data_ptr()), C.cast(a_r, C.c_void_p), len(table), a_w, C.c_void_p(out.data_ptr()), stream))
         return out
 
@@ -859,27 +836,19 @@ class Context:
                 wp.check(w)                                                # ValueError beyond the library's limits
         sizes, one_size = sc.per_picture(size, n, 2, "size")
         samplings, one_sampling = sc.per_picture(sampling, n, 2, "sampling")
-        geoms = {s: self._geometry(s) for s in streams}
-        shapes = {}                                                        # a call usually repeats few shapes: each is looked at once
-        if n and one_size and one_sampling and len(set(geoms.values())) == 1:
-            keys = [(geoms[sids[0]], sizes[0], samplings[0])] * n
-            distinct = keys[:1]
-        else:
-            keys = [(geoms[s], sz, sm) for s, sz, sm in zip(sids, sizes, samplings)]
-            distinct = set(keys)
-        for key in distinct:
-            g, sz, sm = key
+        def shape(g, sz, sm):
             dst = (sz or g[:2]) + (sm or g[2:])
             if dst[2:] not in sc.SAMPLINGS:
                 raise ValueError(f"sampling {dst[2:]}: one of {sc.SAMPLINGS}")
             if dst[0] < 8 or dst[1] < 8 or dst[0] % 8 or dst[1] % 8 or dst[0] > 8192 or dst[1] > 8192:
                 raise ValueError(f"target {dst[0]}x{dst[1]}: multiples of 8 up to 8192")
-            shapes[key] = (dst, sc.nbytes(*dst))
+            return dst, sc.nbytes(*dst)
+        geoms = {s: self._geometry(s) for s in streams}
+        shapes, column = Context._target_shapes(geoms, sids, (sizes, samplings), one_size and one_sampling, shape)
         pb = {s: self.pic_bytes(s) for s in streams}
         ptrs = sources(src, ordinals, lambda i: pb[sids[i]])
         uniform = len({v[0] for v in shapes.values()}) <= 1
-        nb = [shapes[keys[0]][1]] * n if len(shapes) == 1 else [shapes[k][1] for k in keys]
-        out, device, where = Context._slot_outputs(out, nb, uniform, "target geometries")
+        out, device, where = Context._slot_outputs(out, column(1), uniform, "target geometries")
         if not n:
             return out
         a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
@@ -888,7 +857,7 @@ class Context:
         a_w["fill"] = warp.fill + (0,) if warps is None else [w.fill + (0,) for w in warps]
         a_d = np.empty(n, dtype=_WARP_DST)                                   # HvqWarpDst[n]
         a_d["ptr"] = where
-        a_d["rest"] = shapes[keys[0]][0] if len(shapes) == 1 else [shapes[k][0] for k in keys]
+        a_d["rest"] = column(0, broadcast=True)
         check(lib().hvq_warp_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.c_void_p(a_w.ctypes.data), C.c_void_p(a_d.ctypes.data), stream))
         return out
 

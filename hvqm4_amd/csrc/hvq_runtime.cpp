@@ -2479,6 +2479,87 @@ static int export_enqueue(HvqContext *c, const void *jobs, size_t bytes, void *h
     return HVQ_OK;
 }
 
+/* ---- The frame of the calls that write uint8 pictures in slot layout, Y | U | V ("The slot-layout frame"): scale,
+ * filter, warp, compose, rank, map.  Everything here inlines into the entry point's loop: no allocation, no indirect call ---- */
+
+/* "%d pictures": the most one launch's grid takes */
+static int count_check(int n, const char *noun)
+{
+    if (n > 65535) return fail(HVQ_E_ARG, "%d %s: one call takes 65535 at the most", n, noun);
+    return HVQ_OK;
+}
+
+/* destination (or target) i of a call: the kernels store 16 bytes at a time */
+static int slot_pointer_check(const char *noun, int i, const void *ptr)
+{
+    if (!ptr || ((uintptr_t)ptr & 15u)) return fail(HVQ_E_ARG, "%s %d: the pointer must be a non-null multiple of 16", noun, i);
+    return HVQ_OK;
+}
+
+/* A call usually repeats few target shapes: the geometry check (a parser's tables) is kept from the target before. */
+struct TargetSeen {
+    int width = 0, height = 0, h_samp = 0, v_samp = 0;
+    int check(int w, int h, int hs, int vs)
+    {
+        if (w == width && h == height && hs == h_samp && vs == v_samp) return HVQ_OK;
+        { int rc = geometry_supported(w, h, hs, vs); if (rc) return rc; }
+        width = w; height = h; h_samp = hs; v_samp = vs;
+        return HVQ_OK;
+    }
+};
+
+/* a picture in slot layout as the plane walk sees it: luma size and the chroma planes' shifts, of a stream or of a target */
+struct SlotShape { int w, h, xs, ys; };
+static inline SlotShape slot_shape(const Stream &s) { return { s.w, s.h, s.wshift, s.hshift }; }
+static inline SlotShape slot_shape(int width, int height, int h_samp, int v_samp) { return { width, height, h_samp == 2, v_samp == 2 }; }
+
+/* The three planes of one picture: `job(p, so, to, nx, ny, mx, my)` gets plane p's offset and size in a picture of shape `s` and in
+ * one of shape `t`, and returns the plane's tiles, or a negative code, which ends the walk.  -> the picture's tiles, or that code.
+ * Always inline: an entry point's loop over 65535 pictures calls nothing but what its job calls. */
+template <class Job>
+__attribute__((always_inline)) static inline int64_t plane_walk(const SlotShape &s, const SlotShape &t, Job job)
+{
+    size_t so = 0, to = 0;
+    int64_t tiles = 0;
+    for (int p = 0; p < 3; ++p) {
+        const uint32_t nx = (uint32_t)(s.w >> (p ? s.xs : 0)), ny = (uint32_t)(s.h >> (p ? s.ys : 0));
+        const uint32_t mx = (uint32_t)(t.w >> (p ? t.xs : 0)), my = (uint32_t)(t.h >> (p ? t.ys : 0));
+        const int64_t r = job(p, so, to, nx, ny, mx, my);
+        if (r < 0) return r;
+        tiles += r;
+        so += (size_t)nx * ny;
+        to += (size_t)mx * my;
+    }
+    return tiles;
+}
+
+/* one shape on both sides: `job(p, off, nx, ny)` */
+template <class Job>
+__attribute__((always_inline)) static inline int64_t plane_walk(const SlotShape &s, Job job)
+{
+    return plane_walk(s, s, [&](int p, size_t off, size_t, uint32_t nx, uint32_t ny, uint32_t, uint32_t) { return job(p, off, nx, ny); });
+}
+
+/* The tail: `count` pictures of at most `max_tiles` tiles go to `launch` (a weak symbol: null where the kernel's file is not linked)
+ * behind the upload of the table */
+typedef hipError_t SlotLaunch(const void *tab_dev, int count, uint32_t max_tiles, hipStream_t stream);
+static int slot_enqueue(HvqContext *c, SlotLaunch *launch, const char *kernel, const char *file, const void *table, size_t bytes, int count,
+                        uint32_t max_tiles, void *hip_stream)
+{
+    if (!launch) return fail(HVQ_E_NOGPU, "this build of the library has no %s kernel (%s is not linked)", kernel, file);
+    return export_enqueue(c, table, bytes, hip_stream, [=](const void *t, hipStream_t st) { return launch(t, count, max_tiles, st); });
+}
+
+/* the hvq_*_force_* switches of the tests: -> the state before; `states` 3 where 2 is a state of its own (warp) */
+template <class T>
+static int force_switch(HvqContext *c, T HvqContext::*flag, int on, int states = 2)
+{
+    if (!c) return fail(HVQ_E_ARG, "bad arguments");
+    const int was = (int)(c->*flag);
+    c->*flag = (T)(states == 3 && on == 2 ? 2 : on != 0);
+    return was;
+}
+
 HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, int format,
                                    const HvqExportDst *dst, void *hip_stream)
 {
@@ -2924,10 +3005,7 @@ HVQ_EXPORT int hvq_hash_nearest(HvqContext *c, const uint64_t *q, int nq, int q_
     return HVQ_OK;
 }
 
-/* Scaled copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a tenth member of the export chain:
- * chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane; one launch
- * behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no
- * memset. */
+/* Scaled copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame") */
 HVQ_EXPORT int64_t hvq_scale_bytes(int width, int height, int h_samp, int v_samp)
 {
     { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
@@ -2943,13 +3021,7 @@ HVQ_EXPORT int hvq_scale_body(int nx, int ny, int mx, int my)
     return (int)hvq_sc_body((uint32_t)nx, (uint32_t)ny, (uint32_t)mx, (uint32_t)my);
 }
 
-HVQ_EXPORT int hvq_scale_force_direct(HvqContext *c, int on)
-{
-    if (!c) return fail(HVQ_E_ARG, "bad arguments");
-    const int was = c->sc_force_direct ? 1 : 0;
-    c->sc_force_direct = on != 0;
-    return was;
-}
+HVQ_EXPORT int hvq_scale_force_direct(HvqContext *c, int on) { return force_switch(c, &HvqContext::sc_force_direct, on); }
 
 HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                   const HvqScaleDst *dst, void *hip_stream)
@@ -2957,13 +3029,13 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
     static_assert(HVQ_SCALE_DIRECT == (int)HVQ_SC_DIRECT && HVQ_SCALE_TILED == (int)HVQ_SC_TILED && HVQ_SCALE_MAX_RATIO == (int)HVQ_SC_MAX_RATIO,
                   "the header's names are the kernel's");
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqScaleJob> jobs((size_t)n * 3u);
     uint32_t max_tiles = 0;
-    /* a call usually repeats few shapes: the geometry check (a parser's tables) and the multipliers of a plane are kept from the picture before */
-    HvqScaleDst seen{};
+    /* a call usually repeats few shapes: the geometry check and the multipliers of a plane are kept from the picture before */
+    TargetSeen seen;
     HvqScaleJob last[3];
     memset(last, 0, sizeof last);
     for (int i = 0; i < n; ++i) {
@@ -2971,12 +3043,8 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqScaleDst &d = dst[i];
-        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
-        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
-            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
-            if (rc) return rc;
-            seen = d;
-        }
+        { int rc = slot_pointer_check("destination", i, d.ptr); if (rc) return rc; }
+        { int rc = seen.check(d.width, d.height, d.h_samp, d.v_samp); if (rc) return rc; }
         int cx = d.crop_x, cy = d.crop_y, cw = d.crop_w, ch = d.crop_h;
         if (cw == 0) {
             if (cx || cy || ch) return fail(HVQ_E_ARG, "destination %d: crop_w == 0 means the whole picture and takes the other three as 0", i);
@@ -2987,39 +3055,32 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
         if (((cx | cw) & ((1 << s.wshift) - 1)) || ((cy | ch) & ((1 << s.hshift) - 1)))
             return fail(HVQ_E_ARG, "destination %d: the crop %d, %d, %d x %d does not lie on the chroma samples of stream %d", i, cx, cy, cw, ch, streams[i]);
         if (cw < 8 || ch < 8) return fail(HVQ_E_ARG, "destination %d: a cropped source of %d x %d is below 8 x 8", i, cw, ch);
-        const int dws = d.h_samp == 2, dhs = d.v_samp == 2;
-        const uint8_t *sp = a;
-        uint8_t *dp = (uint8_t *)d.ptr;
-        for (int p = 0; p < 3; ++p) {
+        const int64_t tiles = plane_walk(slot_shape(s), slot_shape(d.width, d.height, d.h_samp, d.v_samp),
+                                         [&](int p, size_t so, size_t to, uint32_t pitch, uint32_t, uint32_t mx, uint32_t my) -> int64_t {
             const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0;
-            const uint32_t pitch = (uint32_t)(s.w >> xs);
             const uint32_t nx = (uint32_t)(cw >> xs), ny = (uint32_t)(ch >> ys);
-            const uint32_t mx = (uint32_t)(d.width >> (p ? dws : 0)), my = (uint32_t)(d.height >> (p ? dhs : 0));
             if (nx > HVQ_SC_MAX_RATIO * mx || ny > HVQ_SC_MAX_RATIO * my)
                 return fail(HVQ_E_ARG, "destination %d, plane %d: %u x %u -> %u x %u is a reduction beyond %u", i, p, nx, ny, mx, my, HVQ_SC_MAX_RATIO);
             HvqScaleJob &j = jobs[(size_t)i * 3u + (size_t)p];
-            const uint64_t from = (uint64_t)(uintptr_t)(sp + (size_t)(cy >> ys) * pitch + (size_t)(cx >> xs));
+            const uint64_t from = (uint64_t)(uintptr_t)(a + so + (size_t)(cy >> ys) * pitch + (size_t)(cx >> xs));
+            const uint64_t to_ptr = (uint64_t)(uintptr_t)((uint8_t *)d.ptr + to);
             HvqScaleJob &l = last[p];
             if (l.nx == nx && l.ny == ny && l.mx == mx && l.my == my && ((l.body & HVQ_SC_TILED) == 0) == (c->sc_force_direct || hvq_sc_body(nx, ny, mx, my) == HVQ_SC_DIRECT)) {
                 j = l;
-                j.src = from; j.dst = (uint64_t)(uintptr_t)dp; j.pitch = pitch;
+                j.src = from; j.dst = to_ptr; j.pitch = pitch;
             } else {
-                j = l = hvq_sc_job(from, pitch, nx, ny, (uint64_t)(uintptr_t)dp, mx, my, c->sc_force_direct);
+                j = l = hvq_sc_job(from, pitch, nx, ny, to_ptr, mx, my, c->sc_force_direct);
             }
-            sp += (size_t)pitch * (size_t)(s.h >> ys);
-            dp += (size_t)mx * my;
-        }
-        max_tiles = std::max(max_tiles, jobs[(size_t)i * 3u].tiles + jobs[(size_t)i * 3u + 1u].tiles + jobs[(size_t)i * 3u + 2u].tiles);
+            return j.tiles;
+        });
+        if (tiles < 0) return (int)tiles;
+        max_tiles = std::max(max_tiles, (uint32_t)tiles);
     }
-    if (!hvq_launch_scale) return fail(HVQ_E_NOGPU, "this build of the library has no scale kernel (hvq_scale.hip is not linked)");
-    return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqScaleJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) { return hvq_launch_scale(tab, n, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_scale, "scale", "hvq_scale.hip", jobs.data(), jobs.size() * sizeof(HvqScaleJob), n, max_tiles, hip_stream);
 }
 
-/* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): an eleventh member of the export
- * chain: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane, and
- * behind them the table of the planes' filters with the taps widened to dwords; one launch behind that upload on the caller's stream
- * (export_enqueue).  Nothing but the destinations is written: no scratch memory, no memset. */
+/* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):
+ * behind the jobs goes the table of the planes' filters with the taps widened to dwords */
 static int filter_plane_check(const HvqPlaneFilter &p, const char *plane)
 {
     if (p.terms != 1 && p.terms != 2) return fail(HVQ_E_ARG, "%s filter: %d terms (1 or 2)", plane, p.terms);
@@ -3066,13 +3127,7 @@ static HvqFilterPlaneDev filter_plane_dev(const HvqPlaneFilter &p)
     return d;
 }
 
-HVQ_EXPORT int hvq_filter_force_filter(HvqContext *c, int on)
-{
-    if (!c) return fail(HVQ_E_ARG, "bad arguments");
-    const int was = c->fl_force_filter ? 1 : 0;
-    c->fl_force_filter = on != 0;
-    return was;
-}
+HVQ_EXPORT int hvq_filter_force_filter(HvqContext *c, int on) { return force_switch(c, &HvqContext::fl_force_filter, on); }
 
 HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                    const HvqFilter *filters, int nfilters, const int *which, void *const *dst, void *hip_stream)
@@ -3080,7 +3135,7 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
     static_assert(HVQ_FLT_MAX_RADIUS == (int)HVQ_FL_MAX_R && HVQ_FLT_MAX_TAPS == 2 * HVQ_FLT_MAX_RADIUS + 1 && HVQ_FLT_MAX_TAPS <= 32,
                   "the header's limits are the kernel's");
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !filters))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (nfilters < 1 || nfilters > HVQ_FLT_MAX_FILTERS) return fail(HVQ_E_ARG, "%d filters: one call takes 1 .. %d", nfilters, HVQ_FLT_MAX_FILTERS);
     for (int f = 0; f < nfilters; ++f) { int rc = hvq_filter_check(filters + f); if (rc) return rc; }
@@ -3100,32 +3155,21 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
         const uint8_t *a = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
-        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
         const int f = which ? which[i] : 0;
         if (f < 0 || f >= nfilters) return fail(HVQ_E_ARG, "picture %d: filter %d of %d", i, f, nfilters);
-        const uint8_t *sp = a;
-        uint8_t *dp = (uint8_t *)dst[i];
-        uint32_t tiles = 0;
-        for (int p = 0; p < 3; ++p) {
-            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+        uint8_t *const b = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
             const uint32_t pf = (uint32_t)(2 * f + (p ? 1 : 0));
             HvqFilterJob &j = jobs[(size_t)i * 3u + (size_t)p];
-            j = hvq_fl_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, pf, copy[pf]);
-            tiles += j.tiles;
-            sp += (size_t)nx * ny;
-            dp += (size_t)nx * ny;
-        }
-        max_tiles = std::max(max_tiles, tiles);
+            j = hvq_fl_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)(b + off), nx, ny, pf, copy[pf]);
+            return j.tiles;
+        }));
     }
-    if (!hvq_launch_filter) return fail(HVQ_E_NOGPU, "this build of the library has no filter kernel (hvq_filter.hip is not linked)");
-    return export_enqueue(c, up.data(), up.size(), hip_stream,
-                          [=](const void *t, hipStream_t st) { return hvq_launch_filter(t, n, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_filter, "filter", "hvq_filter.hip", up.data(), up.size(), n, max_tiles, hip_stream);
 }
 
-/* Rank filters on resident pictures in slot layout (include/hvqm4_amd.h: the specification): a member of the export chain like
- * hvq_filter_pictures: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per
- * plane, each with its operation and radii; one launch behind the job table on the caller's stream (export_enqueue).  Nothing but the
- * destinations is written: no scratch memory, no memset. */
+/* Rank filters on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame") */
 static int rank_plane_check(const HvqRankPlane &p, const char *plane)
 {
     if (p.op != HVQ_RNK_MIN && p.op != HVQ_RNK_MAX && p.op != HVQ_RNK_RANGE && p.op != HVQ_RNK_MEDIAN) return fail(HVQ_E_ARG, "%s rank: op %d", plane, p.op);
@@ -3143,13 +3187,7 @@ HVQ_EXPORT int hvq_rank_check(const HvqRank *r)
     return rank_plane_check(r->chroma, "chroma");
 }
 
-HVQ_EXPORT int hvq_rank_force_general(HvqContext *c, int on)
-{
-    if (!c) return fail(HVQ_E_ARG, "bad arguments");
-    const int was = c->rk_force_general ? 1 : 0;
-    c->rk_force_general = on != 0;
-    return was;
-}
+HVQ_EXPORT int hvq_rank_force_general(HvqContext *c, int on) { return force_switch(c, &HvqContext::rk_force_general, on); }
 
 HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                  const HvqRank *ranks, int nranks, const int *which, void *const *dst, void *hip_stream)
@@ -3157,7 +3195,7 @@ HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const
     static_assert(HVQ_RNK_MAX_RADIUS == (int)HVQ_RK_MAX_R && HVQ_RNK_MIN == (int)HVQ_RK_OP_MIN && HVQ_RNK_MAX == (int)HVQ_RK_OP_MAX &&
                   HVQ_RNK_RANGE == (int)HVQ_RK_OP_RANGE && HVQ_RNK_MEDIAN == (int)HVQ_RK_OP_MEDIAN, "the header's values are the kernel's");
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !ranks))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (nranks < 1 || nranks > HVQ_RNK_MAX_RANKS) return fail(HVQ_E_ARG, "%d ranks: one call takes 1 .. %d", nranks, HVQ_RNK_MAX_RANKS);
     for (int r = 0; r < nranks; ++r) { int rc = hvq_rank_check(ranks + r); if (rc) return rc; }
@@ -3168,38 +3206,28 @@ HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const
         const uint8_t *a = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
-        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
         const int r = which ? which[i] : 0;
         if (r < 0 || r >= nranks) return fail(HVQ_E_ARG, "picture %d: rank %d of %d", i, r, nranks);
-        const uint8_t *sp = a;
-        uint8_t *dp = (uint8_t *)dst[i];
-        uint32_t tiles = 0;
-        for (int p = 0; p < 3; ++p) {
-            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+        uint8_t *const b = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
             const HvqRankPlane &rp = p ? ranks[r].chroma : ranks[r].luma;
             HvqRankJob &j = jobs[(size_t)i * 3u + (size_t)p];
-            j = hvq_rk_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, (uint32_t)rp.op, (uint32_t)rp.rx, (uint32_t)rp.ry, c->rk_force_general);
-            tiles += j.tiles;
-            sp += (size_t)nx * ny;
-            dp += (size_t)nx * ny;
-        }
-        max_tiles = std::max(max_tiles, tiles);
+            j = hvq_rk_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)(b + off), nx, ny, (uint32_t)rp.op, (uint32_t)rp.rx, (uint32_t)rp.ry, c->rk_force_general);
+            return j.tiles;
+        }));
     }
-    if (!hvq_launch_rank) return fail(HVQ_E_NOGPU, "this build of the library has no rank kernel (hvq_rank.hip is not linked)");
-    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqRankJob), hip_stream,
-                          [=](const void *t, hipStream_t st) { return hvq_launch_rank(t, n, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_rank, "rank", "hvq_rank.hip", jobs.data(), jobs.size() * sizeof(HvqRankJob), n, max_tiles, hip_stream);
 }
 
-/* Lookup tables on resident pictures in slot layout (include/hvqm4_amd.h: the specification): a member of the export chain like
- * hvq_rank_pictures: chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane,
- * each with the device address of its 256 table bytes; one launch behind the job table on the caller's stream (export_enqueue): the
- * tables are read when it runs.  Nothing but the destinations is written: no scratch memory, no memset. */
+/* Lookup tables on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):
+ * a job holds the device address of its 256 table bytes, which are read when the launch runs */
 HVQ_EXPORT int hvq_map_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                 const uint8_t *tables, int ntables, const int *which, int planes, void *const *dst, void *hip_stream)
 {
     static_assert(HVQ_MAP_TABLE_BYTES == 3 * 256, "a record is a table of 256 bytes per plane");
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (!tables || ((uintptr_t)tables & 15u)) return fail(HVQ_E_ARG, "tables must be a non-null multiple of 16");
     if (ntables < 1 || ntables > 65535) return fail(HVQ_E_ARG, "%d tables: one call takes 1 .. 65535", ntables);
@@ -3212,26 +3240,18 @@ HVQ_EXPORT int hvq_map_pictures(HvqContext *c, int n, const int *streams, const 
         const uint8_t *a = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
-        if (!dst[i] || ((uintptr_t)dst[i] & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
         const int r = which ? which[i] : ntables == 1 ? 0 : i;
         if (r < 0 || r >= ntables) return fail(HVQ_E_ARG, "picture %d: table %d of %d", i, r, ntables);
-        const uint8_t *sp = a;
-        uint8_t *dp = (uint8_t *)dst[i];
-        uint32_t tiles = 0;
-        for (int p = 0; p < 3; ++p) {
-            const uint32_t nx = (uint32_t)(s.w >> (p ? s.wshift : 0)), ny = (uint32_t)(s.h >> (p ? s.hshift : 0));
+        uint8_t *const b = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
             HvqMapJob &j = jobs[(size_t)i * 3u + (size_t)p];
-            j = hvq_mp_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, (uint64_t)(uintptr_t)(tables + (size_t)r * HVQ_MAP_TABLE_BYTES + 256u * (size_t)p),
-                           nx, ny, (planes >> p) & 1);
-            tiles += j.tiles;
-            sp += (size_t)nx * ny;
-            dp += (size_t)nx * ny;
-        }
-        max_tiles = std::max(max_tiles, tiles);
+            j = hvq_mp_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)(b + off),
+                           (uint64_t)(uintptr_t)(tables + (size_t)r * HVQ_MAP_TABLE_BYTES + 256u * (size_t)p), nx, ny, (planes >> p) & 1);
+            return j.tiles;
+        }));
     }
-    if (!hvq_launch_map) return fail(HVQ_E_NOGPU, "this build of the library has no map kernel (hvq_map.hip is not linked)");
-    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqMapJob), hip_stream,
-                          [=](const void *t, hipStream_t st) { return hvq_launch_map(t, n, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_map, "map", "hvq_map.hip", jobs.data(), jobs.size() * sizeof(HvqMapJob), n, max_tiles, hip_stream);
 }
 
 /* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job
@@ -3263,7 +3283,7 @@ HVQ_EXPORT int hvq_histogram_tables(HvqContext *c, int n, const uint32_t *hist, 
     static_assert(HVQ_TBL_IDENTITY == (int)HVQ_TB_IDENTITY && HVQ_TBL_FLAT == (int)HVQ_TB_FLAT && HVQ_TBL_EQUALIZE == (int)HVQ_TB_EQUALIZE &&
                   HVQ_TBL_STRETCH == (int)HVQ_TB_STRETCH && HVQ_TBL_OTSU == (int)HVQ_TB_OTSU, "the header's values are the kernel's");
     if (!c || n < 0) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d records: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "records"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (!hist || ((uintptr_t)hist & 15u) || !tables || ((uintptr_t)tables & 15u)) return fail(HVQ_E_ARG, "hist and tables must be non-null multiples of 16");
     if (!rules || nrules < 1 || nrules > HVQ_TBL_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", rules ? nrules : 0, HVQ_TBL_MAX_RULES);
@@ -3284,10 +3304,7 @@ HVQ_EXPORT int hvq_histogram_tables(HvqContext *c, int n, const uint32_t *hist, 
                           [=](const void *t, hipStream_t st) { return hvq_launch_tables(t, n, st); });
 }
 
-/* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification): a twelfth member of the export chain:
- * chain_begin over the resident pictures, picture_source with `src` per picture.  Three jobs a picture, one per plane, each with the
- * plane's own inverse map; one launch behind the job table on the caller's stream (export_enqueue).  Nothing but the destinations is
- * written: no scratch memory, no memset. */
+/* Warped copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame") */
 HVQ_EXPORT int hvq_warp_check(const HvqWarp *w)
 {
     if (!w) return fail(HVQ_E_ARG, "bad arguments");
@@ -3309,13 +3326,7 @@ HVQ_EXPORT int hvq_warp_body(const HvqWarp *w, int dst_h, int dst_v, int src_h, 
     return (int)hvq_wp_job(0, 0, (uint32_t)nx, (uint32_t)ny, 8, 8, m, w->border, 0, dst_h, dst_v, src_h, src_v, 0).body;
 }
 
-HVQ_EXPORT int hvq_warp_force_direct(HvqContext *c, int on)
-{
-    if (!c) return fail(HVQ_E_ARG, "bad arguments");
-    const int was = c->wp_force;
-    c->wp_force = on == 2 ? 2 : on != 0;
-    return was;
-}
+HVQ_EXPORT int hvq_warp_force_direct(HvqContext *c, int on) { return force_switch(c, &HvqContext::wp_force, on, 3); }
 
 HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
                                  const HvqWarp *warps, const HvqWarpDst *dst, void *hip_stream)
@@ -3323,51 +3334,37 @@ HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const
     static_assert(HVQ_WARP_DIRECT == (int)HVQ_WP_DIRECT && HVQ_WARP_TILED == (int)HVQ_WP_TILED && HVQ_WARP_MAX_SCALE == HVQ_WP_MAX_M,
                   "the header's names are the kernel's");
     if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !warps))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
     for (int i = 0; i < n; ++i) { int rc = hvq_warp_check(warps + i); if (rc) return rc; }
     { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqWarpJob> jobs((size_t)n * 3u);
     uint32_t max_tiles = 0;
-    HvqWarpDst seen{};                                  /* a call usually repeats few shapes: the geometry check (a parser's tables) is kept from the picture before */
+    TargetSeen seen;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const HvqWarpDst &d = dst[i];
-        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "destination %d: the pointer must be a non-null multiple of 16", i);
-        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
-            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
-            if (rc) return rc;
-            seen = d;
-        }
+        { int rc = slot_pointer_check("destination", i, d.ptr); if (rc) return rc; }
+        { int rc = seen.check(d.width, d.height, d.h_samp, d.v_samp); if (rc) return rc; }
         const HvqWarp &w = warps[i];
         const int32_t m[6] = { w.m00, w.m01, w.m10, w.m11, w.t0, w.t1 };
-        const int dws = d.h_samp == 2, dhs = d.v_samp == 2;
-        const uint8_t *sp = a;
-        uint8_t *dp = (uint8_t *)d.ptr;
-        uint32_t tiles = 0;
-        for (int p = 0; p < 3; ++p) {
-            const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0, xd = p ? dws : 0, yd = p ? dhs : 0;
-            const uint32_t nx = (uint32_t)(s.w >> xs), ny = (uint32_t)(s.h >> ys);
-            const uint32_t mx = (uint32_t)(d.width >> xd), my = (uint32_t)(d.height >> yd);
+        const SlotShape from = slot_shape(s), to = slot_shape(d.width, d.height, d.h_samp, d.v_samp);
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(from, to, [&](int p, size_t so, size_t dof, uint32_t nx, uint32_t ny, uint32_t mx, uint32_t my) {
+            const int xs = p ? from.xs : 0, ys = p ? from.ys : 0, xd = p ? to.xs : 0, yd = p ? to.ys : 0;
             HvqWarpJob &j = jobs[(size_t)i * 3u + (size_t)p];
-            j = hvq_wp_job((uint64_t)(uintptr_t)sp, (uint64_t)(uintptr_t)dp, nx, ny, mx, my, m, w.border, w.fill[p], 1 << xd, 1 << yd, 1 << xs, 1 << ys, c->wp_force);
-            tiles += j.tiles;
-            sp += (size_t)nx * ny;
-            dp += (size_t)mx * my;
-        }
-        max_tiles = std::max(max_tiles, tiles);
+            j = hvq_wp_job((uint64_t)(uintptr_t)(a + so), (uint64_t)(uintptr_t)((uint8_t *)d.ptr + dof), nx, ny, mx, my, m, w.border, w.fill[p],
+                           1 << xd, 1 << yd, 1 << xs, 1 << ys, c->wp_force);
+            return j.tiles;
+        }));
     }
-    if (!hvq_launch_warp) return fail(HVQ_E_NOGPU, "this build of the library has no warp kernel (hvq_warp.hip is not linked)");
-    return export_enqueue(c, jobs.data(), (size_t)n * 3u * sizeof(HvqWarpJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) { return hvq_launch_warp(tab, n, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_warp, "warp", "hvq_warp.hip", jobs.data(), jobs.size() * sizeof(HvqWarpJob), n, max_tiles, hip_stream);
 }
 
-/* Pictures composed of layers of resident pictures, in slot layout (include/hvqm4_amd.h: the specification): a thirteenth member of the
- * export chain: chain_begin over the flat layer sources, picture_source with `src` per layer.  Three jobs a target, one per plane, and
- * behind them three records a layer, the rectangles of both sides in samples of the plane; one launch behind that upload on the caller's
- * stream (export_enqueue).  Nothing but the destinations is written: no scratch memory, no memset. */
+/* Pictures composed of layers of resident pictures, in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The
+ * slot-layout frame"): the chain's pictures are the flat layer sources; behind three jobs a target go three records a layer, the
+ * rectangles of both sides in samples of the plane */
 HVQ_EXPORT int hvq_compose_check(const HvqComposeLayer *l)
 {
     if (!l) return fail(HVQ_E_ARG, "bad arguments");
@@ -3379,13 +3376,7 @@ HVQ_EXPORT int hvq_compose_check(const HvqComposeLayer *l)
     return HVQ_OK;
 }
 
-HVQ_EXPORT int hvq_compose_force_general(HvqContext *c, int on)
-{
-    if (!c) return fail(HVQ_E_ARG, "bad arguments");
-    const int was = c->cp_force_general ? 1 : 0;
-    c->cp_force_general = on != 0;
-    return was;
-}
+HVQ_EXPORT int hvq_compose_force_general(HvqContext *c, int on) { return force_switch(c, &HvqContext::cp_force_general, on); }
 
 HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *streams, const int *ordinals, const void *const *src,
                                     const HvqComposeLayer *layers, int ntargets, const HvqComposeDst *dst, void *hip_stream)
@@ -3393,19 +3384,15 @@ HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *strea
     static_assert(HVQ_CMP_PUT == (int)HVQ_CP_PUT && HVQ_CMP_ADD == (int)HVQ_CP_ADD && HVQ_CMP_MAX_GAIN == HVQ_CP_MAX_GAIN && HVQ_CMP_MAX_SHIFT < 31,
                   "the header's names are the kernel's");
     if (!c || nlayers < 0 || ntargets < 0 || (nlayers && (!streams || !ordinals || !layers)) || (ntargets && !dst)) return fail(HVQ_E_ARG, "bad arguments");
-    if (ntargets > 65535) return fail(HVQ_E_ARG, "%d targets: one call takes 65535 at the most", ntargets);
+    { int rc = count_check(ntargets, "targets"); if (rc) return rc; }
     if (nlayers > HVQ_CMP_MAX_TOTAL) return fail(HVQ_E_ARG, "%d layers: one call takes %d at the most", nlayers, HVQ_CMP_MAX_TOTAL);
     if (!ntargets) return HVQ_OK;
     for (int l = 0; l < nlayers; ++l) { int rc = hvq_compose_check(layers + l); if (rc) return rc; }
-    HvqComposeDst seen{};                               /* a call usually repeats few shapes: the geometry check (a parser's tables) is kept from the target before */
+    TargetSeen seen;
     for (int t = 0; t < ntargets; ++t) {
         const HvqComposeDst &d = dst[t];
-        if (!d.ptr || ((uintptr_t)d.ptr & 15u)) return fail(HVQ_E_ARG, "target %d: the pointer must be a non-null multiple of 16", t);
-        if (d.width != seen.width || d.height != seen.height || d.h_samp != seen.h_samp || d.v_samp != seen.v_samp) {
-            int rc = geometry_supported(d.width, d.height, d.h_samp, d.v_samp);
-            if (rc) return rc;
-            seen = d;
-        }
+        { int rc = slot_pointer_check("target", t, d.ptr); if (rc) return rc; }
+        { int rc = seen.check(d.width, d.height, d.h_samp, d.v_samp); if (rc) return rc; }
         if (d.shift < 0 || d.shift > HVQ_CMP_MAX_SHIFT) return fail(HVQ_E_ARG, "target %d: shift %d outside 0 .. %d", t, d.shift, HVQ_CMP_MAX_SHIFT);
         for (int p = 0; p < 3; ++p)
             if (d.bias[p] < -255 || d.bias[p] > 255) return fail(HVQ_E_ARG, "target %d: bias %d outside -255 .. 255", t, d.bias[p]);
@@ -3428,14 +3415,12 @@ HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *strea
             return fail(HVQ_E_ARG, "layer %d: the rectangle %d, %d, %d x %d leaves the %d x %d source", l, sx, sy, w, h, s.w, s.h);
         if (((sx | w | L.dx) & ((1 << s.wshift) - 1)) || ((sy | h | L.dy) & ((1 << s.hshift) - 1)))
             return fail(HVQ_E_ARG, "layer %d: %d, %d, %d x %d -> %d, %d does not lie on the chroma samples of stream %d", l, sx, sy, w, h, L.dx, L.dy, streams[l]);
-        const uint8_t *sp = a;
-        for (int p = 0; p < 3; ++p) {
+        plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
             const int xs = p ? s.wshift : 0, ys = p ? s.hshift : 0;
-            const uint32_t nx = (uint32_t)(s.w >> xs), ny = (uint32_t)(s.h >> ys);
-            recs[(size_t)l * 3u + (size_t)p] = hvq_cp_rec((uint64_t)(uintptr_t)sp, nx, ny, sx >> xs, sy >> ys, w >> xs, h >> ys, L.dx >> xs, L.dy >> ys,
+            recs[(size_t)l * 3u + (size_t)p] = hvq_cp_rec((uint64_t)(uintptr_t)(a + off), nx, ny, sx >> xs, sy >> ys, w >> xs, h >> ys, L.dx >> xs, L.dy >> ys,
                                                           L.weight[p], (uint32_t)L.mode, c->cp_force_general);
-            sp += (size_t)nx * ny;
-        }
+            return 0;
+        });
     }
     uint32_t max_tiles = 0;
     for (int t = 0; t < ntargets; ++t) {
@@ -3454,20 +3439,13 @@ HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *strea
         }
         for (int p = 0; p < 3; ++p)
             if (gain[p] > HVQ_CMP_MAX_GAIN) return fail(HVQ_E_ARG, "target %d, plane %d: a gain of %lld (at most %d)", t, p, (long long)gain[p], HVQ_CMP_MAX_GAIN);
-        uint8_t *dp = (uint8_t *)d.ptr;
-        uint32_t tiles = 0;
-        for (int p = 0; p < 3; ++p) {
-            const uint32_t mx = (uint32_t)(d.width >> (p ? dws : 0)), my = (uint32_t)(d.height >> (p ? dhs : 0));
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(d.width, d.height, d.h_samp, d.v_samp), [&](int p, size_t off, uint32_t mx, uint32_t my) {
             HvqComposeJob &j = jobs[(size_t)t * 3u + (size_t)p];
-            j = hvq_cp_job((uint64_t)(uintptr_t)dp, mx, my, (uint32_t)d.first, (uint32_t)d.count, d.shift, d.bias[p], (uint32_t)p);
-            tiles += j.tiles;
-            dp += (size_t)mx * my;
-        }
-        max_tiles = std::max(max_tiles, tiles);
+            j = hvq_cp_job((uint64_t)(uintptr_t)((uint8_t *)d.ptr + off), mx, my, (uint32_t)d.first, (uint32_t)d.count, d.shift, d.bias[p], (uint32_t)p);
+            return j.tiles;
+        }));
     }
-    if (!hvq_launch_compose) return fail(HVQ_E_NOGPU, "this build of the library has no compose kernel (hvq_compose.hip is not linked)");
-    return export_enqueue(c, up.data(), up.size(), hip_stream,
-                          [=](const void *tab, hipStream_t st) { return hvq_launch_compose(tab, ntargets, max_tiles, st); });
+    return slot_enqueue(c, hvq_launch_compose, "compose", "hvq_compose.hip", up.data(), up.size(), ntargets, max_tiles, hip_stream);
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

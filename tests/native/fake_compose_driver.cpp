@@ -25,19 +25,12 @@
  * Caller-side resources (a stream, outputs, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_compose_driver"
-#include "fake_driver_common.h"
+#include "fake_slot_driver.h"
 
 #include <fstream>
 #include <sstream>
 
 extern "C" void fake_compose_counts(uint64_t out[2], int reset);
-
-struct Geom { int w, h, hs, vs; };
-static const size_t GUARD = 256;
-static const uint8_t SENTINEL = 0xA5;
-
-static Geom geom_of(const Clip &c) { return Geom{ c.info.width, c.info.height, c.info.h_samp, c.info.v_samp }; }
-static size_t bytes_of(Geom g) { return (size_t)g.w * g.h + 2u * (size_t)(g.w >> (g.hs == 2)) * (size_t)(g.h >> (g.vs == 2)); }
 
 struct Source { int sid, k; const void *src; };
 struct Call { std::string label; std::vector<uint8_t *> room; std::vector<Geom> geoms; };
@@ -53,14 +46,9 @@ static Call call_compose(HvqContext *ctx, const std::vector<Source> &pics, const
     Call c{ label, {}, {} };
     for (HvqComposeDst &d : dst) {
         const Geom t{ d.width, d.height, d.h_samp, d.v_samp };
-        const size_t nb = bytes_of(t);
-        void *o = nullptr;
-        HIP(hipMalloc(&o, nb + 2u * GUARD));
-        std::vector<uint8_t> fill(nb + 2u * GUARD, SENTINEL);
-        HIP(hipMemcpy(o, fill.data(), fill.size(), hipMemcpyHostToDevice));
-        c.room.push_back((uint8_t *)o);
+        c.room.push_back(guarded_room(bytes_of(t)));
         c.geoms.push_back(t);
-        d.ptr = (uint8_t *)o + GUARD;
+        d.ptr = c.room.back() + GUARD;
     }
     CHECK(hvq_compose_pictures(ctx, (int)layers.size(), sids.data(), ords.data(), src.data(), layers.data(), (int)dst.size(), dst.data(), caller));
     return c;
@@ -71,44 +59,15 @@ static void write_call(Call *c)
 {
     for (size_t i = 0; i < c->room.size(); ++i) {
         const Geom t = c->geoms[i];
-        const size_t nb = bytes_of(t);
-        std::vector<uint8_t> host(nb + 2u * GUARD);
-        HIP(hipMemcpy(host.data(), c->room[i], host.size(), hipMemcpyDeviceToHost));
-        int guard = 1;
-        for (size_t g = 0; g < GUARD; ++g) guard &= host[g] == SENTINEL && host[GUARD + nb + g] == SENTINEL;
-        fprintf(g_res, "P %s %zu %d %d %d %d %u %d\n", c->label.c_str(), i, t.w, t.h, t.hs, t.vs, crc32_of(host.data() + GUARD, nb), guard);
+        const ReadBack r = read_room(c->room[i], bytes_of(t));
+        fprintf(g_res, "P %s %zu %d %d %d %d %u %d\n", c->label.c_str(), i, t.w, t.h, t.hs, t.vs, r.crc, r.guard);
         HIP(hipFree(c->room[i]));
     }
     c->room.clear();
 }
 
-static void *made(Geom g, const std::string &f, int k, size_t offset, const uint8_t *pic, std::vector<void *> *keep)
+static void scenario_script(HvqContext *&ctx, hipStream_t caller)
 {
-    const size_t pb = bytes_of(g);
-    std::vector<uint8_t> host(pb);
-    if (f == "inv") for (size_t i = 0; i < pb; ++i) host[i] = (uint8_t)(255 - pic[i]);
-    else if (f == "synth") for (size_t i = 0; i < pb; ++i) host[i] = (uint8_t)(((uint32_t)((uint32_t)(i + (size_t)k) * 2654435761u)) >> 13);
-    else if (f == "flat") memset(host.data(), k, pb);
-    else if (f == "check") {
-        size_t at = 0;
-        for (int p = 0; p < 3; ++p) {
-            const size_t pw = (size_t)(p ? g.w >> (g.hs == 2) : g.w), ph = (size_t)(p ? g.h >> (g.vs == 2) : g.h);
-            for (size_t y = 0; y < ph; ++y)
-                for (size_t x = 0; x < pw; ++x) host[at++] = (uint8_t)(((x + y + (size_t)k) & 1u) ? 255 : 0);
-        }
-    } else { fprintf(stderr, DRIVER_NAME ": form %s\n", f.c_str()); exit(2); }
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return (uint8_t *)d + offset;
-}
-
-static void scenario_script()
-{
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     struct Str { int sid; Geom g; const Clip *c; };
     std::vector<Str> streams;
     std::vector<Source> pics;
@@ -138,9 +97,7 @@ static void scenario_script()
         } else if (cmd == "MEM") {
             int s, k; std::string form; size_t off; in >> s >> form >> k >> off;
             const Str &st = streams[(size_t)s];
-            std::vector<uint8_t> host;
-            if (form == "inv") { host.resize(bytes_of(st.g)); CHECK(hvq_read_picture(ctx, st.sid, k, host.data(), host.size())); }
-            pics.push_back(Source{ st.sid, -1, made(st.g, form, k, off, host.data(), &keep) });
+            pics.push_back(Source{ st.sid, -1, uploaded(form == "inv" ? inverted(ctx, st.sid, k) : filled(st.g, form, k), off, &keep) });
         } else if (cmd == "OUT") {
             int s, c, t; in >> s >> c >> t;
             pics.push_back(Source{ streams[(size_t)s].sid, -1, calls[(size_t)c].room[(size_t)t] + GUARD });
@@ -173,8 +130,6 @@ static void scenario_script()
     HIP(hipStreamSynchronize(nullptr));
     for (Call &c : calls) write_call(&c);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 static HvqComposeLayer layer(int mode, int wt, int dx = 0, int dy = 0) { return HvqComposeLayer{ mode, 0, 0, 0, 0, dx, dy, { wt, wt, wt } }; }
@@ -199,11 +154,8 @@ static Call call_mean(HvqContext *ctx, int sid, Geom g, int n, int from, hipStre
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the outputs are those of the pictures as they were.  Then the composed pictures straight into a second call as its sources (`diff`:
  * target k = out k - out (k + 1) mod n + 128), and a context destroyed with a call still queued. */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -234,12 +186,12 @@ static void scenario_reuse()
     Call d = call_mean(ctx, sa, ga, n, 2 * n, caller, "reuse/late");
     Call f = call_mean(ctx, se, geom_of(e), (int)e.pics.size(), 0, caller, "reuse/destroy");
     hvq_context_destroy(ctx);
+    ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&g);
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
 struct Args {
@@ -252,11 +204,8 @@ struct Args {
     bool null_sids = false, null_ords = false, null_src = true, null_layers = false, null_dst = false;
 };
 
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int sa = decode(ctx, a), se = decode(ctx, e);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -381,8 +330,6 @@ static void scenario_refused()
     }
     HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
@@ -392,9 +339,9 @@ int main(int argc, char **argv)
     g_out = argv[2]; g_golden = argv[3];
     g_res = fopen((g_out + "/results.txt").c_str(), "w");
     if (!g_res) { fprintf(stderr, "fake_compose_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "script") scenario_script();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
+    if (sc == "script") run_scenario(scenario_script);
+    else if (sc == "reuse") run_scenario(scenario_reuse);
+    else if (sc == "refused") run_scenario(scenario_refused);
     else { fprintf(stderr, "fake_compose_driver: unknown scenario %s\n", sc.c_str()); return 2; }
     fake_drain_all();
     fclose(g_res);

@@ -23,20 +23,16 @@
  * Caller-side resources (a stream, outputs, picture memory, tables) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_map_driver"
-#include "fake_driver_common.h"
+#include "fake_slot_driver.h"
 
 #include <fstream>
 #include <sstream>
-
-struct Geom { int w, h, hs, vs; };
 
 static std::vector<std::string> g_names;             /* the rules of rules.txt in their order */
 static std::vector<HvqTableRule> g_rules;
 static std::vector<uint8_t> g_tables;                /* tables.bin */
 static uint8_t *g_tables_dev;                        /* ... in device memory */
 static int g_ntables;
-static const size_t GUARD = 256;
-static const uint8_t SENTINEL = 0xA5;
 
 static std::vector<uint8_t> slurp(const std::string &path)
 {
@@ -66,38 +62,17 @@ static void load_inputs()
     HIP(hipMemcpy(g_tables_dev, g_tables.data(), g_tables.size(), hipMemcpyHostToDevice));
 }
 
-static Geom geom_of(const Clip &c) { return Geom{ c.info.width, c.info.height, c.info.h_samp, c.info.v_samp }; }
-static size_t bytes_of(Geom g) { return (size_t)g.w * g.h + 2u * (size_t)(g.w >> (g.hs == 2)) * (size_t)(g.h >> (g.vs == 2)); }
+/* Item::entry: the record of the call's tables */
 
-/* one picture of a call and what the test is told about it; room: an allocation with guards that holds the source (in place), or NULL */
-struct Item { int sid, k; const void *src; std::string source, form; int kk; Geom g; int table; uint8_t *room; };
-
-static Item resident(int sid, const Clip &c, int k, int table) { return Item{ sid, k, nullptr, c.name, "pic", k, geom_of(c), table, nullptr }; }
-
-static Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep, int table)
+/* the caller's memory filled by the rule synth, between guards; inplace: the call writes where it reads */
+static Item made_guarded(int sid, Geom g, bool inplace, int k, int table)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, (uint8_t *)d + offset, c.name, "inv", k, geom_of(c), table, nullptr };
+    uint8_t *room = guarded_room(bytes_of(g));
+    const std::vector<uint8_t> host = filled(g, "synth", k);
+    HIP(hipMemcpy(room + GUARD, host.data(), host.size(), hipMemcpyHostToDevice));
+    return Item{ { sid, -1, room + GUARD, "synth", inplace ? "inplace" : "synth", k, g }, table };
 }
-
-/* the caller's memory filled by the rule the test knows, between guards; inplace: the call writes where it reads */
-static Item made(int sid, Geom g, bool inplace, int k, int table)
-{
-    const size_t pb = bytes_of(g);
-    std::vector<uint8_t> host(pb + 2u * GUARD, SENTINEL);
-    for (size_t i = 0; i < pb; ++i) host[GUARD + i] = (uint8_t)(((uint32_t)((uint32_t)(i + (size_t)k) * 2654435761u)) >> 13);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, host.size()));
-    HIP(hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice));
-    return Item{ sid, -1, (uint8_t *)d + GUARD, "synth", inplace ? "inplace" : "synth", k, g, table, (uint8_t *)d };
-}
+static uint8_t *room_of(const Item &made) { return (uint8_t *)made.src - GUARD; }
 
 struct Call { std::vector<uint8_t *> room; std::vector<Item> items; std::string label, prefix; int planes; };
 
@@ -112,15 +87,9 @@ static Call call_map(HvqContext *ctx, const std::vector<Item> &items, const uint
     std::vector<void *> dst;
     Call c{ {}, items, label, prefix, planes };
     for (const Item &p : items) {
-        sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); which.push_back(p.table);
-        if (p.form == "inplace") { c.room.push_back(p.room); dst.push_back(p.room + GUARD); continue; }
-        const size_t nb = bytes_of(p.g);
-        void *o = nullptr;
-        HIP(hipMalloc(&o, nb + 2u * GUARD));
-        std::vector<uint8_t> fill(nb + 2u * GUARD, SENTINEL);
-        HIP(hipMemcpy(o, fill.data(), fill.size(), hipMemcpyHostToDevice));
-        c.room.push_back((uint8_t *)o);
-        dst.push_back((uint8_t *)o + GUARD);
+        sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); which.push_back(p.entry);
+        c.room.push_back(p.form == "inplace" ? room_of(p) : guarded_room(bytes_of(p.g)));
+        dst.push_back(c.room.back() + GUARD);
     }
     CHECK(hvq_map_pictures(ctx, n, sids.data(), ords.data(), src.data(), tables, ntables, use_which ? which.data() : nullptr, planes, dst.data(), caller));
     return c;
@@ -131,14 +100,10 @@ static void write_call(Call *c, bool free_rooms = true)
 {
     for (size_t i = 0; i < c->items.size(); ++i) {
         const Item &p = c->items[i];
-        const size_t nb = bytes_of(p.g);
-        std::vector<uint8_t> host(nb + 2u * GUARD);
-        HIP(hipMemcpy(host.data(), c->room[i], host.size(), hipMemcpyDeviceToHost));
-        int guard = 1;
-        for (size_t g = 0; g < GUARD; ++g) guard &= host[g] == SENTINEL && host[GUARD + nb + g] == SENTINEL;
-        const std::string table = c->prefix == "r:" ? "r:" + g_names[(size_t)p.table] : c->prefix + std::to_string(p.table);
+        const ReadBack r = read_room(c->room[i], bytes_of(p.g));
+        const std::string table = c->prefix == "r:" ? "r:" + g_names[(size_t)p.entry] : c->prefix + std::to_string(p.entry);
         fprintf(g_res, "P %s %s %s %d %d %d %d %d %s %d %u %d\n", c->label.c_str(), p.source.c_str(), p.form.c_str(), p.kk, p.g.w, p.g.h, p.g.hs, p.g.vs,
-                table.c_str(), c->planes, crc32_of(host.data() + GUARD, nb), guard);
+                table.c_str(), c->planes, r.crc, r.guard);
         if (free_rooms) HIP(hipFree(c->room[i]));
     }
     if (free_rooms) c->room.clear();
@@ -154,11 +119,8 @@ static void write_bin(const char *label, const uint8_t *dev, size_t bytes)
 }
 
 /* every table of the file on the last picture of clips of the three samplings, of a ragged one and of two with tile seams inside */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<Item> v;
     for (const char *nm : { "crossplane420_64x48", "crossplane422_13_64x48", "crossplane444_48x64", "ragged24x40", "wide296x160", "i16" }) {
         const Clip &c = clip(nm);
@@ -167,24 +129,19 @@ static void scenario_goldens()
     }
     Call a = call_map(ctx, v, g_tables_dev, g_ntables, true, 7, caller, "goldens/all");
     Call b = call_map(ctx, { resident(v[1].sid, clip("crossplane420_64x48"), v[1].k, 0) }, g_tables_dev + HVQ_MAP_TABLE_BYTES, 1, false, 7, caller, "goldens/one");
-    b.items[0].table = 1;                                            /* a table of one: record 1 of the file */
+    b.items[0].entry = 1;                                            /* a table of one: record 1 of the file */
     fprintf(g_res, "R goldens/n0 %d\n", hvq_map_pictures(ctx, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* pictures in the caller's memory, at the start of an allocation and 16 bytes into one, mixed with resident ones; made pictures of the
  * smallest geometry in the three samplings, of 72 x 24, of 136 x 40, of planes just past a tile (136 x 64; the 108 x 76 chroma of 216 x
  * 152: a tile and four dwords) and of rows of 8192, into memory of their
  * own and in place; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48");
     const int sa = decode(ctx, a);
     std::vector<void *> keep;
@@ -199,29 +156,24 @@ static void scenario_memory()
             const int sid = hvq_stream_open(ctx, g.w, g.h, g.hs, g.vs, 1, 3);
             CHECK(sid);
             for (int t = 0; t < 4; ++t) {
-                items.push_back(made(sid, g, false, t + g.w, (t + g.h) % g_ntables));
-                items.push_back(made(sid, g, true, t + g.w + 7, (t + g.h + 1) % g_ntables));
+                items.push_back(made_guarded(sid, g, false, t + g.w, (t + g.h) % g_ntables));
+                items.push_back(made_guarded(sid, g, true, t + g.w + 7, (t + g.h + 1) % g_ntables));
             }
         }
         Call c = call_map(ctx, items, g_tables_dev, g_ntables, true, 7, pass ? nullptr : caller, pass ? "memory/nullstream" : "memory");
         HIP(hipStreamSynchronize(pass ? nullptr : caller));
         write_call(&c, false);
         for (size_t i = 0; i < c.items.size(); ++i) {
-            if (c.items[i].form == "synth") HIP(hipFree(c.items[i].room));       /* the source of a made picture that was not in place */
+            if (c.items[i].form == "synth") HIP(hipFree(room_of(c.items[i])));       /* the source of a made picture that was not in place */
             HIP(hipFree(c.room[i]));
         }
     }
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* one launch, many shapes: 300 pictures of eight clips, the tables of the file in turn; the same call twice */
-static void scenario_many()
+static void scenario_many(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const char *names[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8", "i16", "natural128x96" };
     std::vector<std::pair<int, const Clip *>> sc;
     for (const char *nm : names) sc.push_back({ decode(ctx, clip(nm)), &clip(nm) });
@@ -235,16 +187,11 @@ static void scenario_many()
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* each mask 1 .. 7 on pictures of the three samplings */
-static void scenario_planes()
+static void scenario_planes(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<Item> v;
     int t = 0;
     for (const char *nm : { "crossplane420_64x48", "crossplane422_13_64x48", "crossplane444_48x64", "wide296x160" }) {
@@ -257,17 +204,12 @@ static void scenario_planes()
     for (int planes = 1; planes <= 7; ++planes) calls.push_back(call_map(ctx, v, g_tables_dev, g_ntables, true, planes, caller, ("planes/" + std::to_string(planes)).c_str()));
     HIP(hipStreamSynchronize(caller));
     for (Call &c : calls) write_call(&c);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* records.bin through every rule of the file (record i of the call: record i / nrules of the file through rule i % nrules), read back into
  * tables_out.bin; then, nothing waited for in between, one 8 x 8 picture per table through it: n tables for n pictures without `which` */
-static void scenario_tables()
+static void scenario_tables(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const std::vector<uint8_t> rec = slurp(g_out + "/records.bin");
     const size_t rb = 3u * HVQ_HIST_BINS * sizeof(uint32_t);
     if (rec.empty() || rec.size() % rb) { fprintf(stderr, DRIVER_NAME ": no records in %s/records.bin\n", g_out.c_str()); exit(2); }
@@ -288,7 +230,7 @@ static void scenario_tables()
     const int sid = hvq_stream_open(ctx, g.w, g.h, g.hs, g.vs, 1, 3);
     CHECK(sid);
     std::vector<Item> items;
-    for (int i = 0; i < n; ++i) items.push_back(made(sid, g, false, i, i));
+    for (int i = 0; i < n; ++i) items.push_back(made_guarded(sid, g, false, i, i));
     Call c = call_map(ctx, items, room + GUARD, n, false, 7, caller, "tables/map", "o");
     fprintf(g_res, "R tables/n0 %d\n", hvq_histogram_tables(ctx, 0, nullptr, nullptr, 0, nullptr, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
@@ -298,21 +240,16 @@ static void scenario_tables()
     fprintf(g_res, "S tables/guards %zu %zu\n", same, 2u * GUARD);
     write_bin("tables_out", room + GUARD, tb);
     write_call(&c);
-    for (const Item &p : items) HIP(hipFree(p.room));
+    for (const Item &p : items) HIP(hipFree(room_of(p)));
     HIP(hipFree(hist));
     HIP(hipFree(room));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* histograms -> tables -> map on one stream, nothing waited for in between; then flushes that hand the slots of the pictures to later
  * ones before anything has run (late schedule): the outputs are those of the pictures as they were.  HVQ_E_STATE for a picture whose
  * slot is gone and for one that is queued; the chain again on the later pictures; a context destroyed with a chain still queued */
-static void scenario_chain()
+static void scenario_chain(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size(), ne = (int)e.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -355,19 +292,16 @@ static void scenario_chain()
     Call d = chain(sa, a, 2 * n, n, "chain/late", true);
     Call f = chain(se, e, 0, ne, "chain/destroy", false);
     hvq_context_destroy(ctx);
+    ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&d);
     write_call(&f);
     for (void *p : keep) HIP(hipFree(p));
-    HIP(hipStreamDestroy(caller));
 }
 
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a;
     const int sa = decode(ctx, a);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -476,8 +410,6 @@ static void scenario_refused()
     }
     HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
@@ -488,13 +420,13 @@ int main(int argc, char **argv)
     load_inputs();
     g_res = fopen((g_out + "/results.txt").c_str(), "w");
     if (!g_res) { fprintf(stderr, "fake_map_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "many") scenario_many();
-    else if (sc == "planes") scenario_planes();
-    else if (sc == "tables") scenario_tables();
-    else if (sc == "chain") scenario_chain();
-    else if (sc == "refused") scenario_refused();
+    if (sc == "goldens") run_scenario(scenario_goldens);
+    else if (sc == "memory") run_scenario(scenario_memory);
+    else if (sc == "many") run_scenario(scenario_many);
+    else if (sc == "planes") run_scenario(scenario_planes);
+    else if (sc == "tables") run_scenario(scenario_tables);
+    else if (sc == "chain") run_scenario(scenario_chain);
+    else if (sc == "refused") run_scenario(scenario_refused);
     else { fprintf(stderr, "fake_map_driver: unknown scenario %s\n", sc.c_str()); return 2; }
     fake_drain_all();
     HIP(hipFree(g_tables_dev));

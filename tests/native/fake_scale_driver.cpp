@@ -17,74 +17,45 @@
  * Caller-side resources (a stream, outputs, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_scale_driver"
-#include "fake_driver_common.h"
+#include "fake_slot_driver.h"
 
-struct Geom { int w, h, hs, vs; };
 struct Crop { int x, y, w, h; };
 
-static const size_t GUARD = 256;
-static const uint8_t SENTINEL = 0xA5;
+/* one picture of a call and what the test is told about it: Picture::g is the source geometry */
+struct ScaleItem : Picture { Geom to; Crop crop; };
 
-static Geom geom_of(const Clip &c) { return Geom{ c.info.width, c.info.height, c.info.h_samp, c.info.v_samp }; }
+static ScaleItem resident(int sid, const Clip &c, int k, Geom to, Crop crop = Crop{ 0, 0, 0, 0 }) { return ScaleItem{ resident_picture(sid, c, k), to, crop }; }
 
-/* one picture of a call and what the test is told about it */
-struct Item { int sid, k; const void *src; std::string source, form; int kk; Geom from, to; Crop crop; };
-
-static Item resident(int sid, const Clip &c, int k, Geom to, Crop crop = Crop{ 0, 0, 0, 0 })
+static ScaleItem in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep, Geom to, Crop crop = Crop{ 0, 0, 0, 0 })
 {
-    return Item{ sid, k, nullptr, c.name, "pic", k, geom_of(c), to, crop };
+    return ScaleItem{ inverted_picture(ctx, sid, c, k, offset, keep), to, crop };
 }
 
-/* the caller's memory: picture k of stream sid read back, every byte inverted, in device memory at `offset` bytes into an allocation */
-static Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep, Geom to, Crop crop = Crop{ 0, 0, 0, 0 })
+/* the kit's rules, and tie: 2 x 2 blocks { 0, 0, 0, k } (4:4:4) */
+static ScaleItem made(int sid, Geom from, const char *form, int k, std::vector<void *> *keep, Geom to, Crop crop = Crop{ 0, 0, 0, 0 })
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, (uint8_t *)d + offset, c.name, "inv", k, geom_of(c), to, crop };
+    if (std::string(form) != "tie") return ScaleItem{ made_picture(sid, from, form, k, keep), to, crop };
+    std::vector<uint8_t> host(bytes_of(from));
+    for (size_t i = 0; i < host.size(); ++i) { const size_t x = i % (size_t)from.w, y = i / (size_t)from.w; host[i] = (uint8_t)((x & 1u) && (y & 1u) ? k : 0); }
+    return ScaleItem{ { sid, -1, uploaded(host, 0, keep), "synth", form, k, from }, to, crop };
 }
 
-/* the caller's memory filled by a rule the test knows; the stream `sid` carries its geometry */
-static Item made(int sid, Geom from, const char *form, int k, std::vector<void *> *keep, Geom to, Crop crop = Crop{ 0, 0, 0, 0 })
-{
-    const size_t pb = (size_t)hvq_scale_bytes(from.w, from.h, from.hs, from.vs);
-    std::vector<uint8_t> host(pb);
-    const std::string f = form;
-    if (f == "synth") for (size_t i = 0; i < pb; ++i) host[i] = (uint8_t)(((uint32_t)((uint32_t)(i + (size_t)k) * 2654435761u)) >> 13);
-    else if (f == "flat") memset(host.data(), k, pb);
-    else for (size_t i = 0; i < pb; ++i) { const size_t x = i % (size_t)from.w, y = i / (size_t)from.w; host[i] = (uint8_t)((x & 1u) && (y & 1u) ? k : 0); }   /* tie: 4:4:4 */
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb));
-    keep->push_back(d);
-    HIP(hipMemcpy(d, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, d, "synth", form, k, from, to, crop };
-}
-
-struct Call { std::vector<uint8_t *> out; std::vector<Item> items; std::string label; };
+struct Call { std::vector<uint8_t *> out; std::vector<ScaleItem> items; std::string label; };
 
 /* queue one call on `caller`; every output is its own allocation filled with the sentinel, GUARD bytes longer than the picture */
-static Call call_scale(HvqContext *ctx, const std::vector<Item> &items, bool null_src, hipStream_t caller, const char *label)
+static Call call_scale(HvqContext *ctx, const std::vector<ScaleItem> &items, bool null_src, hipStream_t caller, const char *label)
 {
     const int n = (int)items.size();
     std::vector<int> sids, ords;
     std::vector<const void *> src;
     std::vector<HvqScaleDst> dst;
     Call c{ {}, items, label };
-    for (const Item &p : items) {
+    for (const ScaleItem &p : items) {
         sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src);
         const int64_t nb = hvq_scale_bytes(p.to.w, p.to.h, p.to.hs, p.to.vs);
         CHECK(nb);
-        void *o = nullptr;
-        HIP(hipMalloc(&o, (size_t)nb + GUARD));
-        std::vector<uint8_t> fill((size_t)nb + GUARD, SENTINEL);
-        HIP(hipMemcpy(o, fill.data(), fill.size(), hipMemcpyHostToDevice));
-        c.out.push_back((uint8_t *)o);
-        dst.push_back(HvqScaleDst{ o, p.to.w, p.to.h, p.to.hs, p.to.vs, p.crop.x, p.crop.y, p.crop.w, p.crop.h });
+        c.out.push_back(guarded_room((size_t)nb, 0));
+        dst.push_back(HvqScaleDst{ c.out.back(), p.to.w, p.to.h, p.to.hs, p.to.vs, p.crop.x, p.crop.y, p.crop.w, p.crop.h });
     }
     CHECK(hvq_scale_pictures(ctx, n, sids.data(), ords.data(), null_src ? nullptr : src.data(), dst.data(), caller));
     return c;
@@ -94,14 +65,11 @@ static Call call_scale(HvqContext *ctx, const std::vector<Item> &items, bool nul
 static void write_call(Call *c, bool release = true)
 {
     for (size_t i = 0; i < c->items.size(); ++i) {
-        const Item &p = c->items[i];
+        const ScaleItem &p = c->items[i];
         const size_t nb = (size_t)hvq_scale_bytes(p.to.w, p.to.h, p.to.hs, p.to.vs);
-        std::vector<uint8_t> host(nb + GUARD);
-        HIP(hipMemcpy(host.data(), c->out[i], host.size(), hipMemcpyDeviceToHost));
-        int guard = 1;
-        for (size_t g = 0; g < GUARD; ++g) guard &= host[nb + g] == SENTINEL;
-        fprintf(g_res, "P %s %s %s %d %d %d %d %d %d %d %d %d %d %d %d %d %u %d\n", c->label.c_str(), p.source.c_str(), p.form.c_str(), p.kk, p.from.w, p.from.h, p.from.hs,
-                p.from.vs, p.to.w, p.to.h, p.to.hs, p.to.vs, p.crop.x, p.crop.y, p.crop.w, p.crop.h, crc32_of(host.data(), nb), guard);
+        const ReadBack r = read_room(c->out[i], nb, 0);
+        fprintf(g_res, "P %s %s %s %d %d %d %d %d %d %d %d %d %d %d %d %d %u %d\n", c->label.c_str(), p.source.c_str(), p.form.c_str(), p.kk, p.g.w, p.g.h, p.g.hs,
+                p.g.vs, p.to.w, p.to.h, p.to.hs, p.to.vs, p.crop.x, p.crop.y, p.crop.w, p.crop.h, r.crc, r.guard);
         if (release) HIP(hipFree(c->out[i]));
     }
     if (release) c->out.clear();
@@ -109,7 +77,7 @@ static void write_call(Call *c, bool release = true)
 
 /* the shapes of tests/test_gpu_scale.py on resident pictures: identity in every sampling, ratios 2 and 4, ratios that are no integers with
  * tile seams inside the picture, enlargement, sampling conversion at the same and at half size, crops */
-static std::vector<Item> shapes(HvqContext *ctx, std::map<std::string, int> *sids)
+static std::vector<ScaleItem> shapes(HvqContext *ctx, std::map<std::string, int> *sids)
 {
     auto sid = [&](const char *nm) {
         auto it = sids->find(nm);
@@ -117,7 +85,7 @@ static std::vector<Item> shapes(HvqContext *ctx, std::map<std::string, int> *sid
         return (*sids)[nm] = decode(ctx, clip(nm));
     };
     auto last = [&](const char *nm) { return (int)clip(nm).pics.size() - 1; };
-    std::vector<Item> v;
+    std::vector<ScaleItem> v;
     for (const char *nm : { "crossplane420_64x48", "crossplane422_13_64x48", "crossplane444_48x64" }) v.push_back(resident(sid(nm), clip(nm), last(nm), geom_of(clip(nm))));
     for (int k = 0; k < 2; ++k) {
         v.push_back(resident(sid("natural128x96"), clip("natural128x96"), k, Geom{ 64, 48, 2, 2 }));
@@ -143,36 +111,28 @@ static std::vector<Item> shapes(HvqContext *ctx, std::map<std::string, int> *sid
     return v;
 }
 
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::map<std::string, int> sids;
-    const std::vector<Item> v = shapes(ctx, &sids);
+    const std::vector<ScaleItem> v = shapes(ctx, &sids);
     Call a = call_scale(ctx, v, true, caller, "goldens/all");
     Call b = call_scale(ctx, { v[7] }, false, caller, "goldens/one");
     fprintf(g_res, "R goldens/n0 %d\n", hvq_scale_pictures(ctx, 0, nullptr, nullptr, nullptr, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* pictures in the caller's memory, at the start of an allocation and 16 bytes into one, mixed with resident ones; the tie pictures; the
  * 32x limit in both directions; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     const int st = hvq_stream_open(ctx, 16, 16, 1, 1, 1, 3), sl = hvq_stream_open(ctx, 256, 256, 2, 2, 1, 3);
     CHECK(st); CHECK(sl);
     std::vector<void *> keep;
-    std::vector<Item> items;
+    std::vector<ScaleItem> items;
     for (int k = 0; k < (int)a.pics.size(); ++k) {
         items.push_back(in_memory(ctx, sa, a, k, k & 1 ? 16 : 0, &keep, Geom{ 40, 24, 2, 2 }));
         items.push_back(resident(sa, a, k, Geom{ 40, 24, 2, 2 }));
@@ -190,16 +150,11 @@ static void scenario_memory()
     write_call(&c);
     write_call(&d);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* 8192 x 2064 -> 256 x 72: cells beyond 32 bits */
-static void scenario_cells64()
+static void scenario_cells64(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Geom big{ 8192, 2064, 2, 2 };
     const int sid = hvq_stream_open(ctx, big.w, big.h, big.hs, big.vs, 1, 3);
     CHECK(sid);
@@ -208,20 +163,15 @@ static void scenario_cells64()
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* one launch, many shapes: 300 pictures of eight clips, the targets, samplings and crops mixed; the same call twice */
-static void scenario_many()
+static void scenario_many(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const char *names[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8", "i16", "natural128x96" };
     std::vector<std::pair<int, const Clip *>> sc;
     for (const char *nm : names) sc.push_back({ decode(ctx, clip(nm)), &clip(nm) });
-    std::vector<Item> items;
+    std::vector<ScaleItem> items;
     auto r8 = [](int v) { return std::max(8, (v + 8) / 16 * 8); };
     for (int i = 0; i < 300; ++i) {
         const auto &s = sc[(size_t)i % sc.size()];
@@ -241,18 +191,13 @@ static void scenario_many()
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* the forced direct body and the chosen one on the same pictures */
-static void scenario_body()
+static void scenario_body(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::map<std::string, int> sids;
-    std::vector<Item> v = shapes(ctx, &sids);
+    std::vector<ScaleItem> v = shapes(ctx, &sids);
     std::vector<void *> keep;
     const int sl = hvq_stream_open(ctx, 256, 256, 2, 2, 1, 3);
     CHECK(sl);
@@ -271,23 +216,18 @@ static void scenario_body()
     write_call(&b);
     write_call(&c);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the outputs are those of the pictures as they were.  Then the scaled pictures straight into a second call as its sources, nothing
  * waited for in between (what a consumer of src= does), and a context destroyed with a call still queued */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
     const Geom half{ 40, 24, 2, 2 };
-    std::vector<Item> items;
+    std::vector<ScaleItem> items;
     for (int k = 0; k < n; ++k) items.push_back(resident(sa, a, k, half));
     Call c = call_scale(ctx, items, false, caller, "reuse");
     for (int pass = 0; pass < 2; ++pass) {                      /* 2 n later pictures into a ring of n + 3 slots: every slot of the first pass is rewritten */
@@ -301,12 +241,12 @@ static void scenario_reuse()
     /* the first call's outputs as the sources of a second one: a stream of their geometry carries them */
     const int carrier = hvq_stream_open(ctx, half.w, half.h, half.hs, half.vs, 1, 3);
     CHECK(carrier);
-    std::vector<Item> chain;
-    for (int k = 0; k < n; ++k) chain.push_back(Item{ carrier, -1, c.out[(size_t)k], a.name, "scaled", k, half, Geom{ 16, 16, 1, 1 }, Crop{ 0, 0, 0, 0 } });
+    std::vector<ScaleItem> chain;
+    for (int k = 0; k < n; ++k) chain.push_back(ScaleItem{ { carrier, -1, c.out[(size_t)k], a.name, "scaled", k, half }, Geom{ 16, 16, 1, 1 }, Crop{ 0, 0, 0, 0 } });
     Call g = call_scale(ctx, chain, false, caller, "reuse/chain");
-    std::vector<Item> late_call, late, other;
+    std::vector<ScaleItem> late_call, late, other;
     for (int k = 0; k < n; ++k) {
-        Item p = resident(sa, a, 2 * n + k, half);
+        ScaleItem p = resident(sa, a, 2 * n + k, half);
         late_call.push_back(p);
         p.kk = k;                                               /* reported as the clip's pictures: the third pass decodes the same clip */
         late.push_back(p);
@@ -316,19 +256,16 @@ static void scenario_reuse()
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(resident(se, e, k, Geom{ 32, 24, 2, 2 }));
     Call f = call_scale(ctx, other, false, caller, "reuse/destroy");
     hvq_context_destroy(ctx);
+    ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&g);
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a;
     const int sa = decode(ctx, a);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -396,8 +333,6 @@ static void scenario_refused()
     write_call(&c);
     HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
@@ -407,13 +342,13 @@ int main(int argc, char **argv)
     g_out = argv[2]; g_golden = argv[3];
     g_res = fopen((g_out + "/results.txt").c_str(), "w");
     if (!g_res) { fprintf(stderr, "fake_scale_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "cells64") scenario_cells64();
-    else if (sc == "many") scenario_many();
-    else if (sc == "body") scenario_body();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
+    if (sc == "goldens") run_scenario(scenario_goldens);
+    else if (sc == "memory") run_scenario(scenario_memory);
+    else if (sc == "cells64") run_scenario(scenario_cells64);
+    else if (sc == "many") run_scenario(scenario_many);
+    else if (sc == "body") run_scenario(scenario_body);
+    else if (sc == "reuse") run_scenario(scenario_reuse);
+    else if (sc == "refused") run_scenario(scenario_refused);
     else { fprintf(stderr, "fake_scale_driver: unknown scenario %s\n", sc.c_str()); return 2; }
     fake_drain_all();
     fclose(g_res);

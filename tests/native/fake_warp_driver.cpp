@@ -22,18 +22,14 @@
  * Caller-side resources (a stream, outputs, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_warp_driver"
-#include "fake_driver_common.h"
+#include "fake_slot_driver.h"
 
 #include <fstream>
 #include <sstream>
 
-struct Geom { int w, h, hs, vs; };
-
 static std::vector<std::string> g_names;             /* the warps of warps.txt in their order */
 static std::vector<HvqWarp> g_warps;
 static std::vector<Geom> g_targets;                  /* and the target geometries they are meant for */
-static const size_t GUARD = 256;
-static const uint8_t SENTINEL = 0xA5;
 
 static void load_warps()
 {
@@ -67,51 +63,7 @@ static Geom target_of(Geom g, int warp)
     return o;
 }
 
-static Geom geom_of(const Clip &c) { return Geom{ c.info.width, c.info.height, c.info.h_samp, c.info.v_samp }; }
-static size_t bytes_of(Geom g) { return (size_t)g.w * g.h + 2u * (size_t)(g.w >> (g.hs == 2)) * (size_t)(g.h >> (g.vs == 2)); }
-
-/* one picture of a call and what the test is told about it */
-struct Item { int sid, k; const void *src; std::string source, form; int kk; Geom g; int warp; };
-
-static Item resident(int sid, const Clip &c, int k, int warp) { return Item{ sid, k, nullptr, c.name, "pic", k, geom_of(c), warp }; }
-
-/* the caller's memory: picture k of stream sid read back, every byte inverted, in device memory at `offset` bytes into an allocation */
-static Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep, int warp)
-{
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, (uint8_t *)d + offset, c.name, "inv", k, geom_of(c), warp };
-}
-
-/* the caller's memory filled by a rule the test knows; the stream `sid` carries its geometry */
-static Item made(int sid, Geom g, const char *form, int k, std::vector<void *> *keep, int warp)
-{
-    const size_t pb = bytes_of(g);
-    std::vector<uint8_t> host(pb);
-    const std::string f = form;
-    if (f == "synth") for (size_t i = 0; i < pb; ++i) host[i] = (uint8_t)(((uint32_t)((uint32_t)(i + (size_t)k) * 2654435761u)) >> 13);
-    else if (f == "flat") memset(host.data(), k, pb);
-    else {                                                               /* check */
-        size_t at = 0;
-        for (int p = 0; p < 3; ++p) {
-            const size_t pw = (size_t)(p ? g.w >> (g.hs == 2) : g.w), ph = (size_t)(p ? g.h >> (g.vs == 2) : g.h);
-            for (size_t y = 0; y < ph; ++y)
-                for (size_t x = 0; x < pw; ++x) host[at++] = (uint8_t)(((x + y + (size_t)k) & 1u) ? 255 : 0);
-        }
-    }
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb));
-    keep->push_back(d);
-    HIP(hipMemcpy(d, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, d, "synth", form, k, g, warp };
-}
-
+/* Item::entry: the warp of warps.txt */
 struct Call { std::vector<uint8_t *> room; std::vector<Item> items; std::string label; };
 
 /* queue one call on `caller`; every output is its own allocation filled with the sentinel, GUARD bytes before and behind the picture */
@@ -124,15 +76,10 @@ static Call call_warp(HvqContext *ctx, const std::vector<Item> &items, bool null
     std::vector<HvqWarpDst> dst;
     Call c{ {}, items, label };
     for (const Item &p : items) {
-        sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); warps.push_back(g_warps[(size_t)p.warp]);
-        const Geom t = target_of(p.g, p.warp);
-        const size_t nb = bytes_of(t);
-        void *o = nullptr;
-        HIP(hipMalloc(&o, nb + 2u * GUARD));
-        std::vector<uint8_t> fill(nb + 2u * GUARD, SENTINEL);
-        HIP(hipMemcpy(o, fill.data(), fill.size(), hipMemcpyHostToDevice));
-        c.room.push_back((uint8_t *)o);
-        dst.push_back(HvqWarpDst{ (uint8_t *)o + GUARD, t.w, t.h, t.hs, t.vs });
+        sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); warps.push_back(g_warps[(size_t)p.entry]);
+        const Geom t = target_of(p.g, p.entry);
+        c.room.push_back(guarded_room(bytes_of(t)));
+        dst.push_back(HvqWarpDst{ c.room.back() + GUARD, t.w, t.h, t.hs, t.vs });
     }
     CHECK(hvq_warp_pictures(ctx, n, sids.data(), ords.data(), null_src ? nullptr : src.data(), warps.data(), dst.data(), caller));
     return c;
@@ -143,25 +90,18 @@ static void write_call(Call *c)
 {
     for (size_t i = 0; i < c->items.size(); ++i) {
         const Item &p = c->items[i];
-        const Geom t = target_of(p.g, p.warp);
-        const size_t nb = bytes_of(t);
-        std::vector<uint8_t> host(nb + 2u * GUARD);
-        HIP(hipMemcpy(host.data(), c->room[i], host.size(), hipMemcpyDeviceToHost));
-        int guard = 1;
-        for (size_t g = 0; g < GUARD; ++g) guard &= host[g] == SENTINEL && host[GUARD + nb + g] == SENTINEL;
+        const Geom t = target_of(p.g, p.entry);
+        const ReadBack r = read_room(c->room[i], bytes_of(t));
         fprintf(g_res, "P %s %s %s %d %d %d %d %d %s %d %d %d %d %u %d\n", c->label.c_str(), p.source.c_str(), p.form.c_str(), p.kk, p.g.w, p.g.h, p.g.hs, p.g.vs,
-                g_names[(size_t)p.warp].c_str(), t.w, t.h, t.hs, t.vs, crc32_of(host.data() + GUARD, nb), guard);
+                g_names[(size_t)p.entry].c_str(), t.w, t.h, t.hs, t.vs, r.crc, r.guard);
         HIP(hipFree(c->room[i]));
     }
     c->room.clear();
 }
 
 /* every warp of the file on the last picture of clips of the three samplings, of a ragged one and of two with tile seams inside */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<Item> v;
     for (const char *nm : { "crossplane420_64x48", "crossplane422_13_64x48", "crossplane444_48x64", "ragged24x40", "wide296x160", "i16" }) {
         const Clip &c = clip(nm);
@@ -174,18 +114,13 @@ static void scenario_goldens()
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* pictures in the caller's memory, at the start of an allocation and 16 bytes into one, mixed with resident ones; made pictures of the
  * smallest geometry in the three samplings, of 72 x 24 and of 136 x 40, random, flat and the 0 / 255 checkerboard, through every warp;
  * the longest and the highest plane; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48");
     const int sa = decode(ctx, a);
     std::vector<void *> keep;
@@ -214,16 +149,11 @@ static void scenario_memory()
     write_call(&c);
     write_call(&d);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* one launch, many shapes: 300 pictures of eight clips, the warps of the file in turn; the same call twice */
-static void scenario_many()
+static void scenario_many(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const char *names[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8", "i16", "natural128x96" };
     std::vector<std::pair<int, const Clip *>> sc;
     for (const char *nm : names) sc.push_back({ decode(ctx, clip(nm)), &clip(nm) });
@@ -237,16 +167,11 @@ static void scenario_many()
     HIP(hipStreamSynchronize(caller));
     write_call(&a);
     write_call(&b);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every warp under the chosen body, under the forced direct body and under the tiled body wherever LDS holds the box */
-static void scenario_body()
+static void scenario_body(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<Item> v;
     for (const char *nm : { "crossplane420_64x48", "crossplane444_48x64", "wide296x160", "ragged24x40", "yuv422_296x160" }) {
         const Clip &c = clip(nm);
@@ -265,18 +190,13 @@ static void scenario_body()
     write_call(&b);
     write_call(&d);
     write_call(&c);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the outputs are those of the pictures as they were.  Then the warped pictures straight into a second call as its sources, nothing
  * waited for in between (what a consumer of src= does), and a context destroyed with a call still queued.  The warps keep the geometry. */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -293,7 +213,7 @@ static void scenario_reuse()
         fprintf(g_res, "R reuse/evicted %d\n", hvq_warp_pictures(ctx, 1, &sa, &items[0].k, nullptr, &g_warps[(size_t)f0], &d, caller));
     }
     std::vector<Item> chain;
-    for (int k = 0; k < n; ++k) chain.push_back(Item{ sa, -1, c.room[(size_t)k] + GUARD, a.name, "warped:" + g_names[(size_t)f0], k, geom_of(a), f1 });
+    for (int k = 0; k < n; ++k) chain.push_back(Item{ { sa, -1, c.room[(size_t)k] + GUARD, a.name, "warped:" + g_names[(size_t)f0], k, geom_of(a) }, f1 });
     Call g = call_warp(ctx, chain, false, caller, "reuse/chain");
     std::vector<Item> late_call, late, other;
     for (int k = 0; k < n; ++k) {
@@ -307,19 +227,16 @@ static void scenario_reuse()
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(resident(se, e, k, f1));
     Call f = call_warp(ctx, other, false, caller, "reuse/destroy");
     hvq_context_destroy(ctx);
+    ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&g);
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a;
     const int sa = decode(ctx, a);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -401,8 +318,6 @@ static void scenario_refused()
     }
     HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
@@ -413,12 +328,12 @@ int main(int argc, char **argv)
     load_warps();
     g_res = fopen((g_out + "/results.txt").c_str(), "w");
     if (!g_res) { fprintf(stderr, "fake_warp_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "many") scenario_many();
-    else if (sc == "body") scenario_body();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
+    if (sc == "goldens") run_scenario(scenario_goldens);
+    else if (sc == "memory") run_scenario(scenario_memory);
+    else if (sc == "many") run_scenario(scenario_many);
+    else if (sc == "body") run_scenario(scenario_body);
+    else if (sc == "reuse") run_scenario(scenario_reuse);
+    else if (sc == "refused") run_scenario(scenario_refused);
     else { fprintf(stderr, "fake_warp_driver: unknown scenario %s\n", sc.c_str()); return 2; }
     fake_drain_all();
     fclose(g_res);

@@ -654,7 +654,8 @@ def test_the_existing_fake_builds_link_without_the_compose_body():
     text = open(os.path.join(fd.CSRC, "hvq_runtime.cpp")).read()
     decl = [l for l in text.splitlines() if "hvq_launch_compose(" in l and l.startswith("extern")]
     assert len(decl) == 1 and "__attribute__((weak))" in decl[0]
-    assert "if (!hvq_launch_compose) return fail(HVQ_E_NOGPU" in text
+    # the call hands the symbol to the tail the slot-layout calls share, which refuses a null one before anything is enqueued
+    assert "return slot_enqueue(c, hvq_launch_compose, " in text and "if (!launch) return fail(HVQ_E_NOGPU" in text
     for kind in fd.BUILDS:                                                       # the plain driver of tests/test_fake_device.py: built there, or here
         exe = fd.build_driver(kind, "fake", "fake_driver", fd.CXX_SOURCES, fd.__file__)
         assert os.path.exists(exe)
