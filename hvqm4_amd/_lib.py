@@ -96,6 +96,14 @@ class HvqTableRule(C.Structure):                # an entry of hvq_histogram_tabl
     _fields_ = [("luma", HvqTablePlane), ("chroma", HvqTablePlane)]
 
 
+class HvqLabelRule(C.Structure):               # include/hvqm4_amd.h: the foreground window of a plane and the neighbourhood (4 or 8)
+    _fields_ = [("plane", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("connectivity", C.c_int32)]
+
+
+class HvqSelect(C.Structure):                   # an entry of hvq_select_components: inclusive ranges of area, box width and box height
+    _fields_ = [(n, C.c_uint32) for n in ("area_min", "area_max", "w_min", "w_max", "h_min", "h_max", "invert", "pad")]
+
+
 class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
     _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
 
@@ -200,6 +208,12 @@ SYMBOLS = {
                                    C.c_void_p]),
     "hvq_table_check": (C.c_int, [C.c_void_p]),
     "hvq_histogram_tables": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_label_check": (C.c_int, [C.c_void_p]),
+    "hvq_label_bytes": (C.c_int64, [C.c_int] * 5),
+    "hvq_label_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_void_p]),
+    "hvq_select_components": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "hvq_warp_check": (C.c_int, [C.c_void_p]),
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),

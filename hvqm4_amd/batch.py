@@ -804,6 +804,112 @@ class Context:
         tables = self.histogram_tables(hist, rules)
         return self.map_pictures(sids, ordinals, tables, src=src, out=out)      # torch frees the scratch in stream order
 
+    def label_pictures(self, sids, ordinals, rules=None, which=None, cap=1024, src=None, labels=None, comps=None):
+        """hvq_label_pictures: the connected components of one plane of the resident pictures (sids[i], ordinals[i]) -- which samples
+        are foreground, the neighbourhood and the numbering are include/hvqm4_amd.h's --, on torch's current stream, without a host
+        synchronisation and without moving a picture.  `rules`: one hvqm4_amd.labels.Rule (default labels.rule(): the 255s of Y under
+        the 8-neighbourhood, an Otsu mask), a list of one per picture (equal ones share an entry; more than 64 distinct ones:
+        ValueError), or a list of distinct rules together with `which`, one index per picture.  -> (labels, comps): lists of n CUDA
+        tensors, labels[i] int32 [Ny, Nx] of the rule's plane (0 background, k component k), comps[i] int64 [cap + 1, 8] (row 0: K,
+        stored, F, status; row k: area, x0, y0, x1, y1, first, sum_x, sum_y; rows beyond `stored` keep what they held).  `labels` /
+        `comps`, if given: such lists, contiguous, 16-byte aligned; `cap` is then the comps' room.  hvqm4_amd.labels gives the expected
+        values (of_picture) and reads the records (records, centroids, boxes, largest).  `src` as in picture_checksums.  Ordering and
+        slot safety are export()'s."""
+        import torch
+        from . import labels as lb
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if which is not None:
+            table = [rules] if isinstance(rules, lb.Rule) else list(rules or ())
+            if not table or len(table) > lb.MAX_RULES:
+                raise ValueError(f"{len(table)} rules: one call takes 1 .. {lb.MAX_RULES}")
+            which = [int(k) for k in which]
+            if len(which) != n or any(not 0 <= k < len(table) for k in which):
+                raise ValueError(f"which: {n} indices into the {len(table)} rules")
+        else:
+            table, which = Context._table_which(lb.Rule() if rules is None else rules, n, lb.Rule, "rules", "labels.Rule", lb.MAX_RULES, "rules")
+        for r in table:
+            lb.check(r)
+        if isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap <= lb.MAX_CAP:
+            raise ValueError(f"cap {cap!r} outside 0 .. {lb.MAX_CAP}")
+        from .checksums import sources
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        shapes = [lb.plane_shape(self._geometry(sids[i]), table[which[i] if which else 0].plane) for i in range(n)]
+
+        def taken(given, name, shape, dtype):
+            if given is None:
+                return [torch.empty(shape(i), dtype=dtype, device="cuda") for i in range(n)]
+
+            def one(i, t):
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape(i)) or not t.is_contiguous():
+                    raise ValueError(f"{name}[{i}] must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape(i))}")
+                if t.data_ptr() & 15:
+                    raise ValueError(f"{name}[{i}]: pointer {t.data_ptr():#x} must be a multiple of 16")
+            try:
+                return Context._out_list(given, n, one)
+            except ValueError as e:
+                raise ValueError(str(e).replace("out", name)) from None
+        labels = taken(labels, "labels", lambda i: shapes[i], torch.int32)
+        comps = taken(comps, "comps", lambda i: (cap + 1, 8), torch.int64)
+        if not n:
+            return labels, comps
+        a_s, a_o, stream = Context._launch_args(labels[0].device, sids, ordinals)
+        from ._lib import HvqLabelRule
+        a_r = (HvqLabelRule * len(table))(*[r.struct() for r in table])
+        a_w = Context._which_array(which, n)
+        a_l = Context._ptr_array([t.data_ptr() for t in labels])
+        a_c = Context._ptr_array([t.data_ptr() for t in comps])
+        check(lib().hvq_label_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_l, a_c, cap, stream))
+        return labels, comps
+
+    def select_components(self, sids, labels, comps, select, which=None, out=None):
+        """hvq_select_components: label maps and record tables of the Y planes (label_pictures' results under a rule with plane 0) back
+        into uint8 pictures IN SLOT LAYOUT of the geometries of sids[i]: Y 255 where the sample's component has a record and its
+        area, box width and box height lie in `select`'s ranges, else 0 (invert swaps the two), U and V 128.  `select`: one
+        hvqm4_amd.labels.Select (labels.select(area=50): the specks below 50 samples go), a list of one per picture, or a list of
+        distinct ones together with `which`.  labels and comps are read when the work runs on torch's current stream: label ->
+        select needs no host synchronisation.  Return forms and `out` are rank_pictures'; whatever takes src= takes a row of the
+        result.  hvqm4_amd.labels.of_select gives the expected bytes."""
+        import torch
+        from . import labels as lb
+        n = Context._pictures(self._geom, sids, [0] * len(sids), limit=True)
+        if which is not None:
+            table = [select] if isinstance(select, lb.Select) else list(select or ())
+            if not table or len(table) > lb.MAX_SELECTS:
+                raise ValueError(f"{len(table)} selections: one call takes 1 .. {lb.MAX_SELECTS}")
+            which = [int(k) for k in which]
+            if len(which) != n or any(not 0 <= k < len(table) for k in which):
+                raise ValueError(f"which: {n} indices into the {len(table)} selections")
+        else:
+            table, which = Context._table_which(select, n, lb.Select, "select", "labels.Select", lb.MAX_SELECTS, "selections")
+        for e in table:
+            lb.check_select(e)
+        if not isinstance(labels, (list, tuple)) or not isinstance(comps, (list, tuple)) or len(labels) != n or len(comps) != n:
+            raise ValueError(f"labels and comps must be lists of {n} tensors")
+        cap = int(comps[0].shape[0]) - 1 if n else 0
+        for i in range(n):
+            w, h = self._geometry(sids[i])[:2]
+            t, c = labels[i], comps[i]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (h, w) or not t.is_contiguous() or t.data_ptr() & 15:
+                raise ValueError(f"labels[{i}] must be a contiguous, 16-byte aligned int32 tensor of shape ({h}, {w})")
+            if not isinstance(c, torch.Tensor) or c.dtype != torch.int64 or tuple(c.shape) != (cap + 1, 8) or not c.is_contiguous() or c.data_ptr() & 15:
+                raise ValueError(f"comps[{i}] must be a contiguous, 16-byte aligned int64 tensor of shape ({cap + 1}, 8)")
+            if t.device.type != "cuda" or c.device.type != "cuda":
+                raise ValueError(f"labels[{i}] / comps[{i}] are not on a GPU")
+        pb = [self.pic_bytes(s) for s in sids]
+        uniform = len({self._geometry(s) for s in set(sids)}) <= 1
+        out, device, where = Context._slot_outputs(out, pb, uniform, "geometries")
+        if not n:
+            return out
+        a_s, _a_o, stream = Context._launch_args(device, sids, ())
+        from ._lib import HvqSelect
+        a_e = (HvqSelect * len(table))(*[e.struct() for e in table])
+        a_w = Context._which_array(which, n)
+        a_l = Context._ptr_array([t.data_ptr() for t in labels])
+        a_c = Context._ptr_array([t.data_ptr() for t in comps])
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_select_components(self._h, n, a_s, a_l, a_c, cap, C.cast(a_e, C.c_void_p), len(table), a_w, a_d, stream))
+        return out
+
     def warp_force_direct(self, on) -> int:
         """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen
         one again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) -> the setting before.  The

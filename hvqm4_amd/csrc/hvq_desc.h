@@ -757,5 +757,51 @@ _Static_assert(sizeof(HvqMapJob) == 48, "HvqMapJob must be 48 bytes");
 _Static_assert(sizeof(HvqTableJob) == 48, "HvqTableJob must be 48 bytes");
 #endif
 
+/* one picture of the label launches (hvq_label.hip, hvq_label_pictures): the plane of the picture's rule, its label map and its record
+ * table.  Grid row = picture in every launch.  A tile is HVQ_LB_TX x HVQ_LB_TY samples, a workgroup of HVQ_LB_LANES lanes labels it in
+ * LDS, a lane four samples of a row (one dword of the plane, sixteen bytes of the map).  `seams` counts the samples on the upper row of
+ * the tile rows 1 .. and on the left column of the tile columns 1 ..: one lane each in the seam launch.  `chunks` counts the units of
+ * HVQ_LB_LANES x 4 consecutive samples of the plane: a workgroup each in the launches that walk the map.  64 bytes. */
+#define HVQ_LB_LANES 256u
+#define HVQ_LB_TX    64u
+#define HVQ_LB_TY    16u
+#define HVQ_LB_TILE  (HVQ_LB_TX * HVQ_LB_TY)        /* 1024 samples: 4 KiB of parents in LDS */
+#define HVQ_LB_CHUNK (HVQ_LB_LANES * 4u)            /* samples of a workgroup of the launches that walk the map */
+#define HVQ_LB_SPAN  (HVQ_LB_LANES * 16u)           /* samples of one round of the numbering workgroup */
+#define HVQ_LB_NUMBERED 0x80000000u                 /* a map entry that holds a component's number, not a parent */
+typedef struct HvqLabelJob {
+    uint64_t src;                      /* device address of the plane, a multiple of 4 */
+    uint64_t labels;                   /* device address of uint32 [ny][nx], a multiple of 16 */
+    uint64_t comps;                    /* device address of uint64 [cap + 1][8], a multiple of 16 */
+    uint32_t nx, ny;                   /* the plane; nx is a multiple of 4, nx ny <= 2^26 */
+    uint32_t tx, ty;                   /* tiles across and down */
+    uint32_t seams;                    /* (ty - 1) nx + (tx - 1) ny */
+    uint32_t chunks;                   /* ceil(nx ny / HVQ_LB_CHUNK) */
+    uint32_t lo, hi;                   /* foreground: lo <= a <= hi */
+    uint32_t conn;                     /* 4 or 8 */
+    uint32_t cap;                      /* records the table has room for */
+} HvqLabelJob;
+
+/* one plane of one picture of the select launch (hvq_label.hip, hvq_select_components): three jobs a picture, Y, U, V, tiles and lanes
+ * as in the map launch (HVQ_MP_*).  Y has body HVQ_SL_SELECT and reads `labels` and `comps`; U and V have HVQ_SL_FILL (128) and both 0.
+ * 80 bytes. */
+#define HVQ_SL_FILL   0u
+#define HVQ_SL_SELECT 1u
+typedef struct HvqSelectJob {
+    uint64_t labels;                   /* device address of uint32 [dwords * 4], a multiple of 16 */
+    uint64_t comps;                    /* device address of uint64 [cap + 1][8], a multiple of 16 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint32_t dwords, tiles, body, cap;
+    uint32_t area_min, area_max, w_min, w_max, h_min, h_max, invert;
+    uint32_t pad[3];
+} HvqSelectJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqLabelJob) == 64 && sizeof(HvqSelectJob) == 80, "job tables are uploaded in 16-byte units");
+static_assert(HVQ_LB_TX * HVQ_LB_TY == HVQ_LB_LANES * 4u && HVQ_LB_TX % 4u == 0u, "a lane labels four samples of a tile row");
+#else
+_Static_assert(sizeof(HvqLabelJob) == 64 && sizeof(HvqSelectJob) == 80, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

@@ -45,6 +45,7 @@
 #include "hvq_filter.h"
 #include "hvq_rank.h"
 #include "hvq_map.h"
+#include "hvq_label.h"
 #include "hvq_warp.h"
 #include "hvq_compose.h"
 
@@ -101,6 +102,10 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_rank(const void *jobs_dev
 /* hvq_map.hip.  Weak for the same reason: hvq_map_pictures and hvq_histogram_tables then refuse with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_map(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_tables(const void *jobs_dev, int nrecords, hipStream_t stream);
+/* hvq_label.hip.  Weak for the same reason: hvq_label_pictures and hvq_select_components then refuse with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_label(const void *jobs_dev, int npics, uint32_t max_tiles, uint32_t max_seams, uint32_t max_chunks,
+                                                             hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_select(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
@@ -3252,6 +3257,102 @@ HVQ_EXPORT int hvq_map_pictures(HvqContext *c, int n, const int *streams, const 
         }));
     }
     return slot_enqueue(c, hvq_launch_map, "map", "hvq_map.hip", jobs.data(), jobs.size() * sizeof(HvqMapJob), n, max_tiles, hip_stream);
+}
+
+/* Connected components of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Labels").  The launches of a call
+ * go behind ONE job table; the label map is the only working memory. */
+HVQ_EXPORT int hvq_label_check(const HvqLabelRule *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    if (r->plane < 0 || r->plane > 2) return fail(HVQ_E_ARG, "label rule: plane %d (0 Y, 1 U, 2 V)", r->plane);
+    if (r->lo < 0 || r->lo > r->hi || r->hi > 255) return fail(HVQ_E_ARG, "label rule: window %d .. %d (0 <= lo <= hi <= 255)", r->lo, r->hi);
+    if (r->connectivity != 4 && r->connectivity != 8) return fail(HVQ_E_ARG, "label rule: connectivity %d (4 or 8)", r->connectivity);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int64_t hvq_label_bytes(int width, int height, int h_samp, int v_samp, int plane)
+{
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
+    if (plane < 0 || plane > 2) return fail(HVQ_E_ARG, "plane %d (0 Y, 1 U, 2 V)", plane);
+    const SlotShape s = slot_shape(width, height, h_samp, v_samp);
+    return 4 * (int64_t)(s.w >> (plane ? s.xs : 0)) * (int64_t)(s.h >> (plane ? s.ys : 0));
+}
+
+HVQ_EXPORT int hvq_label_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                  const HvqLabelRule *rules, int nrules, const int *which, uint32_t *const *labels, uint64_t *const *comps,
+                                  int cap, void *hip_stream)
+{
+    static_assert(HVQ_LBL_INCOMPLETE == (int)HVQ_LB_INCOMPLETE, "the header's value is the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !labels || !comps || !rules))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nrules < 1 || nrules > HVQ_LBL_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", nrules, HVQ_LBL_MAX_RULES);
+    for (int r = 0; r < nrules; ++r) { int rc = hvq_label_check(rules + r); if (rc) return rc; }
+    if (cap < 0 || cap > HVQ_LBL_MAX_CAP) return fail(HVQ_E_ARG, "cap %d outside 0 .. %d", cap, HVQ_LBL_MAX_CAP);
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqLabelJob> jobs((size_t)n);
+    uint32_t max_tiles = 0, max_seams = 0, max_chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("label map", i, labels[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("record table", i, comps[i]); if (rc) return rc; }
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nrules) return fail(HVQ_E_ARG, "picture %d: rule %d of %d", i, r, nrules);
+        const HvqLabelRule &rule = rules[r];
+        HvqLabelJob &j = jobs[(size_t)i];
+        plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            if (p == rule.plane)
+                j = hvq_lb_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)labels[i], (uint64_t)(uintptr_t)comps[i], nx, ny,
+                               (uint32_t)rule.lo, (uint32_t)rule.hi, (uint32_t)rule.connectivity, (uint32_t)cap);
+            return 0;
+        });
+        max_tiles = std::max(max_tiles, j.tx * j.ty);
+        max_seams = std::max(max_seams, j.seams);
+        max_chunks = std::max(max_chunks, j.chunks);
+    }
+    if (!hvq_launch_label) return fail(HVQ_E_NOGPU, "this build of the library has no label kernels (hvq_label.hip is not linked)");
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqLabelJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_label(t, n, max_tiles, max_seams, max_chunks, st); });
+}
+
+/* Labels and records back into mask pictures in slot layout.  No picture is looked up: the stream gives the geometry; the launch goes
+ * behind its job table through export_enqueue, so it is ordered behind an hvq_label_pictures on the same stream. */
+HVQ_EXPORT int hvq_select_components(HvqContext *c, int n, const int *streams, const uint32_t *const *labels, const uint64_t *const *comps,
+                                     int cap, const HvqSelect *sel, int nsel, const int *which, void *const *dst, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !labels || !comps || !sel || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nsel < 1 || nsel > HVQ_SEL_MAX) return fail(HVQ_E_ARG, "%d selections: one call takes 1 .. %d", nsel, HVQ_SEL_MAX);
+    for (int k = 0; k < nsel; ++k) {
+        const HvqSelect &e = sel[k];
+        if (e.area_min > e.area_max || e.w_min > e.w_max || e.h_min > e.h_max) return fail(HVQ_E_ARG, "selection %d: a range with min above max", k);
+        if (e.invert > 1u || e.pad) return fail(HVQ_E_ARG, "selection %d: invert %u, pad %u (0 or 1; 0)", k, e.invert, e.pad);
+    }
+    if (cap < 0 || cap > HVQ_LBL_MAX_CAP) return fail(HVQ_E_ARG, "cap %d outside 0 .. %d", cap, HVQ_LBL_MAX_CAP);
+    std::vector<HvqSelectJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0 || (size_t)streams[i] >= c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("label map", i, labels[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("record table", i, comps[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
+        const int k = which ? which[i] : 0;
+        if (k < 0 || k >= nsel) return fail(HVQ_E_ARG, "picture %d: selection %d of %d", i, k, nsel);
+        const uint32_t range[6] = { sel[k].area_min, sel[k].area_max, sel[k].w_min, sel[k].w_max, sel[k].h_min, sel[k].h_max };
+        uint8_t *const b = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            HvqSelectJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_sl_job((uint64_t)(uintptr_t)labels[i], (uint64_t)(uintptr_t)comps[i], (uint64_t)(uintptr_t)(b + off), nx, ny, (uint32_t)cap, p == 0,
+                           range, sel[k].invert);
+            return j.tiles;
+        }));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    return slot_enqueue(c, hvq_launch_select, "select", "hvq_label.hip", jobs.data(), jobs.size() * sizeof(HvqSelectJob), n, max_tiles, hip_stream);
 }
 
 /* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job

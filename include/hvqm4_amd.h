@@ -969,6 +969,78 @@ int     hvq_table_check(const HvqTableRule *r);
 int     hvq_histogram_tables(HvqContext *ctx, int n, const uint32_t *hist, const HvqTableRule *rules, int nrules, const int *which,
                              uint8_t *tables, void *hip_stream);
 
+/* CONNECTED COMPONENTS of resident pictures, where they lie: the foreground of ONE plane of each of `n` pictures, of any streams, sizes
+ * and samplings, becomes a label map and a table of records, on the caller's HIP stream and without a host synchronisation.  It is the
+ * step behind a mask (hvq_histogram_tables' OTSU, hvq_map_pictures, hvq_rank_pictures): how many blobs, where, how large.  This text is
+ * the authority for the values.
+ *   Foreground. Picture i goes through rules[which[i]] (which == NULL: rules[0] for all).  A sample a of plane rule.plane (0 Y, 1 U, 2 V;
+ *              Nx x Ny samples at the plane's own resolution) is foreground when lo <= a <= hi.  lo = hi = 255 reads an Otsu mask.
+ *   Components. The classes of the foreground under the 4-neighbourhood (left, right, above, below) or the 8-neighbourhood (the diagonals
+ *              too) inside the plane: nothing wraps, nothing is replicated.  A component's FIRST SAMPLE is its sample of the smallest
+ *              raster index y Nx + x.  Components are numbered 1 .. K in ascending order of their first samples (what a raster scan
+ *              with a flood fill gives, and scipy.ndimage.label with the cross / the full 3 x 3 structure).
+ *   labels[i]  a DEVICE pointer, a non-null multiple of 16: uint32 [Ny][Nx], dense, hvq_label_bytes bytes.  0 for background, k for a
+ *              sample of component k.  Every element is written, whatever K and cap are; nothing outside is written.  While the work
+ *              runs the map holds working values.
+ *   comps[i]   a DEVICE pointer, a non-null multiple of 16: uint64 [cap + 1][8].  All values are below 2^63.
+ *              Row 0 is {K, stored = min(K, cap), F = the number of foreground samples, status, 0, 0, 0, 0}.
+ *              Row k, 1 <= k <= stored, is {area, x0, y0, x1, y1, first, sum_x, sum_y}: the number of samples, the bounding box
+ *              (inclusive), the raster index of the first sample, and the exact sums of the samples' coordinates (the centroid is
+ *              sum / area; a plane has at most 2^26 samples, nothing overflows).  Rows beyond `stored` are not touched.
+ *              cap is 0 .. HVQ_LBL_MAX_CAP.
+ *   status     0.  Every loop of the kernels has a bound that follows from the plane's size (a parent chain descends strictly, so it is
+ *              no longer than the plane); a lane that reaches its bound stores HVQ_LBL_INCOMPLETE and leaves, and the values of that
+ *              picture are then unspecified.  It does not happen unless something else writes the map while the work runs.
+ *   Known answers.  An empty mask: K = 0, F = 0, labels all 0.  A full plane: K = 1, area Nx Ny, box (0, 0, Nx - 1, Ny - 1), first 0,
+ *              sum_x = Ny Nx (Nx - 1) / 2, sum_y = Nx Ny (Ny - 1) / 2.  A 0 / 255 checkerboard under 4: K = the number of white
+ *              samples, every area 1, label k at the k-th white sample in raster order; under 8: K = 1.  {255, 0; 0, 255}: K = 2
+ *              under 4, K = 1 under 8.  A "U" whose arms start on row 0 is one component, label 1 on both arms.  The areas add up to F.
+ *   hvq_label_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL rule, a plane outside 0 .. 2, a window that is not 0 <= lo <= hi <= 255,
+ *              a connectivity other than 4 or 8.
+ *   hvq_label_bytes (host only): 4 Nx Ny of that plane of such a picture; HVQ_E_GEOMETRY, or HVQ_E_ARG for the plane.
+ *   The call.  Several launches behind one job table: a tile of HVQ_LB_TX x HVQ_LB_TY = 64 x 16 samples is labelled in LDS, the tiles'
+ *              seams join by lock-free unions on the map, which is the parent array, the roots are numbered in raster order, and the
+ *              records gather by 64-bit integer atomics: the values do not depend on the order of arrival.  No scratch memory.
+ *   HVQ_E_ARG for the whole call: what hvq_label_check refuses, in any entry, used or not; nrules outside 1 .. HVQ_LBL_MAX_RULES; a
+ *              which[i] outside 0 .. nrules - 1; cap outside 0 .. HVQ_LBL_MAX_CAP; a null or misaligned labels[i] or comps[i]; n above
+ *              65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no multiple of 16; a NULL context,
+ *              rules, labels or comps.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a
+ *              refused call leaves every output untouched.  HVQ_E_NOGPU (after those checks) from a build without the label kernels.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_rank_pictures'. */
+#define HVQ_LBL_MAX_RULES 64
+#define HVQ_LBL_MAX_CAP   (1 << 20)
+#define HVQ_LBL_INCOMPLETE 1
+typedef struct HvqLabelRule { int32_t plane, lo, hi, connectivity; } HvqLabelRule;
+int     hvq_label_check(const HvqLabelRule *r);
+int64_t hvq_label_bytes(int width, int height, int h_samp, int v_samp, int plane);   /* 4 * Nx * Ny of that plane */
+int     hvq_label_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                           const HvqLabelRule *rules, int nrules, const int *which,
+                           uint32_t *const *labels, uint64_t *const *comps, int cap, void *hip_stream);
+
+/* LABELS BACK INTO PICTURES: output i is a uint8 picture in slot layout (Y | U | V) of the geometry of streams[i] -- the stream gives
+ * the geometry only, no picture is looked up --, so the result composes with whatever takes `src`.  One launch of the map kernel's shape
+ * on the caller's stream, a member of the export chain.
+ *   Values.    With k the label of a Y sample and S = sel[which[i]] (which == NULL: sel[0] for all): the sample is SELECTED when
+ *              1 <= k <= stored and area_min <= area <= area_max, w_min <= x1 - x0 + 1 <= w_max and h_min <= y1 - y0 + 1 <= h_max
+ *              hold for record k.  The background and the labels without a record (k > stored) are not selected.  Y is 255 where
+ *              selected, else 0; invert = 1 swaps the two, after that rule.  U and V are filled with 128.
+ *              area_min alone is area opening: "remove the specks below N samples".
+ *   Inputs.    labels[i] and comps[i] are hvq_label_pictures' outputs for the Y plane (a rule with plane 0) of a picture of that
+ *              geometry, with the same cap.  They are read when the work runs: label -> select on one stream needs no host
+ *              synchronisation.
+ *   The call.  dst[i] is a non-null DEVICE pointer, a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written,
+ *              each once; nothing outside them.
+ *   HVQ_E_ARG for the whole call: nsel outside 1 .. HVQ_SEL_MAX; in any entry, used or not, a min above its max, an invert other than
+ *              0 or 1, a pad that is not 0; a which[i] outside 0 .. nsel - 1; cap outside 0 .. HVQ_LBL_MAX_CAP; a null or misaligned
+ *              labels[i], comps[i] or dst[i]; n above 65535; a bad stream; a NULL context, labels, comps, sel or dst.  n == 0 is HVQ_OK
+ *              and does nothing.  Every argument is checked before anything is enqueued.  HVQ_E_NOGPU (after those checks) from a
+ *              build without the kernel. */
+#define HVQ_SEL_MAX 64
+typedef struct HvqSelect { uint32_t area_min, area_max, w_min, w_max, h_min, h_max, invert, pad; } HvqSelect;
+int     hvq_select_components(HvqContext *ctx, int n, const int *streams, const uint32_t *const *labels, const uint64_t *const *comps,
+                              int cap, const HvqSelect *sel, int nsel, const int *which, void *const *dst, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
