@@ -104,6 +104,14 @@ class HvqSelect(C.Structure):                   # an entry of hvq_select_compone
     _fields_ = [(n, C.c_uint32) for n in ("area_min", "area_max", "w_min", "w_max", "h_min", "h_max", "invert", "pad")]
 
 
+class HvqDistanceRule(C.Structure):            # include/hvqm4_amd.h: the foreground window of a plane, the metric (HVQ_DST_*) and the border rule
+    _fields_ = [(n, C.c_int32) for n in ("plane", "lo", "hi", "metric", "border")] + [("pad", C.c_int32 * 3)]
+
+
+class HvqDistanceMask(C.Structure):            # an entry of hvq_distance_mask: the mode (HVQ_DSM_*), an inclusive range of distances, invert
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "lo", "hi", "invert")] + [("pad", C.c_uint32 * 4)]
+
+
 class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
     _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
 
@@ -214,6 +222,12 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int, C.c_void_p]),
     "hvq_select_components": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "hvq_distance_check": (C.c_int, [C.c_void_p]),
+    "hvq_distance_bytes": (C.c_int64, [C.c_int] * 5),
+    "hvq_distance_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "hvq_distance_mask_check": (C.c_int, [C.c_void_p]),
+    "hvq_distance_mask": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_check": (C.c_int, [C.c_void_p]),
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),

@@ -910,6 +910,117 @@ class Context:
         check(lib().hvq_select_components(self._h, n, a_s, a_l, a_c, cap, C.cast(a_e, C.c_void_p), len(table), a_w, a_d, stream))
         return out
 
+    @staticmethod
+    def _explicit_table(entries, which, n, cls, most, nouns):
+        """a list of distinct `cls` together with `which`, one index per picture -> (table, which) after their checks"""
+        table = [entries] if isinstance(entries, cls) else list(entries or ())
+        if not table or len(table) > most:
+            raise ValueError(f"{len(table)} {nouns}: one call takes 1 .. {most}")
+        which = [int(k) for k in which]
+        if len(which) != n or any(not 0 <= k < len(table) for k in which):
+            raise ValueError(f"which: {n} indices into the {len(table)} {nouns}")
+        return table, which
+
+    def distance_pictures(self, sids, ordinals, rules=None, which=None, src=None, out=None):
+        """hvq_distance_pictures: the exact distance transform of one plane of the resident pictures (sids[i], ordinals[i]) -- which
+        samples are foreground, the metric, the border rule and the values are include/hvqm4_amd.h's --, on torch's current stream,
+        without a host synchronisation and without moving a picture.  `rules`: one hvqm4_amd.distance.Rule (default distance.rule():
+        the 255s of Y, squared Euclidean, nothing outside the plane: an Otsu mask), a list of one per picture (equal ones share an
+        entry; more than 64 distinct ones: ValueError), or a list of distinct rules together with `which`, one index per picture.
+        -> a list of n CUDA tensors int32 [Ny, Nx] of the rule's plane, viewed from the uint32 memory: 0 on the background, the distance
+        on the foreground, and distance.NONE (no background at all) reads as -1.  `out`, if given: such a list, contiguous, 16-byte
+        aligned.  hvqm4_amd.distance gives the expected values (of_picture) and reads a map (max_inscribed, signed).  `src` as in
+        picture_checksums.  Ordering and slot safety are export()'s."""
+        import torch
+        from . import distance as ds
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if which is not None:
+            table, which = Context._explicit_table(rules, which, n, ds.Rule, ds.MAX_RULES, "rules")
+        else:
+            table, which = Context._table_which(ds.Rule() if rules is None else rules, n, ds.Rule, "rules", "distance.Rule", ds.MAX_RULES, "rules")
+        for r in table:
+            ds.check(r)
+        from .checksums import sources
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        shapes = [ds.plane_shape(self._geometry(sids[i]), table[which[i] if which else 0].plane) for i in range(n)]
+        if out is None:
+            out = [torch.empty(shapes[i], dtype=torch.int32, device="cuda") for i in range(n)]
+        else:
+            def one(i, t):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(shapes[i]) or not t.is_contiguous():
+                    raise ValueError(f"out[{i}] must be a contiguous int32 tensor of shape {tuple(shapes[i])}")
+                if t.data_ptr() & 15:
+                    raise ValueError(f"out[{i}]: pointer {t.data_ptr():#x} must be a multiple of 16")
+            out = Context._out_list(out, n, one)
+        if not n:
+            return out
+        a_s, a_o, stream = Context._launch_args(out[0].device, sids, ordinals)
+        from ._lib import HvqDistanceRule
+        a_r = (HvqDistanceRule * len(table))(*[r.struct() for r in table])
+        a_w = Context._which_array(which, n)
+        a_d = Context._ptr_array([t.data_ptr() for t in out])
+        check(lib().hvq_distance_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_d, stream))
+        return out
+
+    def distance_mask(self, sids, dist, mask, which=None, out=None):
+        """hvq_distance_mask: distance maps of the Y planes (distance_pictures' results under a rule with plane 0) back into uint8
+        pictures IN SLOT LAYOUT of the geometries of sids[i]: under a distance.mask_range(lo, hi) Y 255 where lo <= d <= hi, else 0
+        (invert swaps the two), under distance.mask_root() Y min(255, isqrt(d)); U and V 128.  `mask`: one hvqm4_amd.distance.Mask, a
+        list of one per picture, or a list of distinct ones together with `which`.  The maps are read when the work runs on torch's
+        current stream: distance -> mask needs no host synchronisation.  Return forms and `out` are rank_pictures'; whatever takes
+        src= takes a row of the result.  hvqm4_amd.distance.of_mask gives the expected bytes."""
+        import torch
+        from . import distance as ds
+        n = Context._pictures(self._geom, sids, [0] * len(sids), limit=True)
+        if which is not None:
+            table, which = Context._explicit_table(mask, which, n, ds.Mask, ds.MAX_MASKS, "masks")
+        else:
+            table, which = Context._table_which(mask, n, ds.Mask, "mask", "distance.Mask", ds.MAX_MASKS, "masks")
+        for e in table:
+            ds.check_mask(e)
+        if not isinstance(dist, (list, tuple)) or len(dist) != n:
+            raise ValueError(f"dist must be a list of {n} tensors")
+        for i in range(n):
+            w, h = self._geometry(sids[i])[:2]
+            t = dist[i]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (h, w) or not t.is_contiguous() or t.data_ptr() & 15:
+                raise ValueError(f"dist[{i}] must be a contiguous, 16-byte aligned int32 tensor of shape ({h}, {w})")
+            if t.device.type != "cuda":
+                raise ValueError(f"dist[{i}] is not on a GPU")
+        pb = [self.pic_bytes(s) for s in sids]
+        uniform = len({self._geometry(s) for s in set(sids)}) <= 1
+        out, device, where = Context._slot_outputs(out, pb, uniform, "geometries")
+        if not n:
+            return out
+        a_s, _a_o, stream = Context._launch_args(device, sids, ())
+        from ._lib import HvqDistanceMask
+        a_e = (HvqDistanceMask * len(table))(*[e.struct() for e in table])
+        a_w = Context._which_array(which, n)
+        a_l = Context._ptr_array([t.data_ptr() for t in dist])
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_distance_mask(self._h, n, a_s, a_l, C.cast(a_e, C.c_void_p), len(table), a_w, a_d, stream))
+        return out
+
+    def disc_morph(self, sids, ordinals, steps, src=None, out=None):
+        """resident pictures (sids[i], ordinals[i]) through a list of disc steps (hvqm4_amd.distance.erode_disc / dilate_disc /
+        opening_disc / closing_disc: (Rule, Mask) pairs of any radius), a distance_pictures and a distance_mask a step on torch's
+        current stream: the first from the resident pictures (or `src`, a mask of map_pictures, say), every later one from the result
+        before it through src=.  All steps share one list of maps; the results between them alternate between two scratch tensors of the
+        output's form; the last lands in `out` (rank_pictures' rules; default: a new one).  No host synchronisation.  -> rank_pictures'
+        return forms.  hvqm4_amd.distance.of_steps gives the expected bytes."""
+        from . import distance as ds
+        steps = ds.as_steps(steps)
+        n = len(sids)
+        maps = cur = spare = None
+        for k, (r, m) in enumerate(steps):
+            if cur is None:
+                maps = self.distance_pictures(sids, ordinals, r, src=src, out=maps)
+            else:
+                maps = self.distance_pictures(sids, [-1] * n, r, src=[cur[i] for i in range(n)], out=maps)
+            res = self.distance_mask(sids, maps, m, out=out if k == len(steps) - 1 else spare)
+            spare, cur = cur, res
+        return cur
+
     def warp_force_direct(self, on) -> int:
         """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen
         one again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) -> the setting before.  The

@@ -803,5 +803,47 @@ static_assert(HVQ_LB_TX * HVQ_LB_TY == HVQ_LB_LANES * 4u && HVQ_LB_TX % 4u == 0u
 _Static_assert(sizeof(HvqLabelJob) == 64 && sizeof(HvqSelectJob) == 80, "job tables are uploaded in 16-byte units");
 #endif
 
+/* one picture of the two distance launches (hvq_distance.hip, hvq_distance_pictures): the plane of the picture's rule and its distance
+ * map, which is also the only working memory.  Grid row = picture in both launches.  Column pass: a workgroup of HVQ_DT_CLANES lanes owns
+ * HVQ_DT_COLS consecutive columns, a lane four of them (one dword of the plane, sixteen bytes of the map a row).  Row pass: a workgroup of
+ * HVQ_DT_LANES lanes owns `rows` whole rows, as many as fit HVQ_DT_SPAN samples of uint16 in LDS (16 KiB).  64 bytes. */
+#define HVQ_DT_CLANES 64u
+#define HVQ_DT_COLS   (HVQ_DT_CLANES * 4u)           /* columns of a workgroup of the column pass */
+#define HVQ_DT_LANES  256u
+#define HVQ_DT_SPAN   8192u                          /* samples of a workgroup of the row pass: the widest row there is */
+#define HVQ_DT_INF    0xFFFFu                        /* a staged g of a column without background; the map holds 0xFFFFFFFF there */
+typedef struct HvqDistanceJob {
+    uint64_t src;                      /* device address of the plane, a multiple of 4 */
+    uint64_t dist;                     /* device address of uint32 [ny][nx], a multiple of 16 */
+    uint32_t nx, ny;                   /* the plane; nx is a multiple of 4 and at most HVQ_DT_SPAN */
+    uint32_t lo, hi;                   /* foreground: lo <= a <= hi */
+    uint32_t metric, border;           /* HVQ_DST_*; 0 or 1 */
+    uint32_t colgroups;                /* ceil(nx / HVQ_DT_COLS) */
+    uint32_t rows;                     /* min(ny, HVQ_DT_SPAN / nx) */
+    uint32_t rowgroups;                /* ceil(ny / rows) */
+    uint32_t pad[3];
+} HvqDistanceJob;
+
+/* one plane of one picture of the distance-mask launch (hvq_distance.hip, hvq_distance_mask): three jobs a picture, Y, U, V, tiles and
+ * lanes as in the map launch (HVQ_MP_*).  Y has body HVQ_DM_RANGE or HVQ_DM_ROOT and reads `dist`; U and V have HVQ_DM_FILL (128).
+ * 48 bytes. */
+#define HVQ_DM_RANGE 0u                /* the modes of include/hvqm4_amd.h (HVQ_DSM_*) */
+#define HVQ_DM_ROOT  1u
+#define HVQ_DM_FILL  2u
+typedef struct HvqDistMaskJob {
+    uint64_t dist;                     /* device address of uint32 [dwords * 4], a multiple of 16 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint32_t dwords, tiles, body;
+    uint32_t lo, hi, invert;
+    uint32_t pad[2];
+} HvqDistMaskJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqDistanceJob) == 64 && sizeof(HvqDistMaskJob) == 48, "job tables are uploaded in 16-byte units");
+static_assert(HVQ_DT_SPAN % (HVQ_DT_LANES * 4u) == 0u, "a lane of the row pass takes four samples a round");
+#else
+_Static_assert(sizeof(HvqDistanceJob) == 64 && sizeof(HvqDistMaskJob) == 48, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

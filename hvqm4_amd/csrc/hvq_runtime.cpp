@@ -46,6 +46,7 @@
 #include "hvq_rank.h"
 #include "hvq_map.h"
 #include "hvq_label.h"
+#include "hvq_distance.h"
 #include "hvq_warp.h"
 #include "hvq_compose.h"
 
@@ -106,6 +107,9 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_tables(const void *jobs_d
 extern "C" __attribute__((weak)) hipError_t hvq_launch_label(const void *jobs_dev, int npics, uint32_t max_tiles, uint32_t max_seams, uint32_t max_chunks,
                                                              hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_select(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_distance.hip.  Weak for the same reason: hvq_distance_pictures and hvq_distance_mask then refuse with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_distance(const void *jobs_dev, int npics, uint32_t max_colgroups, uint32_t max_rowgroups, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_distance_mask(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
@@ -3353,6 +3357,103 @@ HVQ_EXPORT int hvq_select_components(HvqContext *c, int n, const int *streams, c
     }
     HIPCHK(hipSetDevice(c->device));
     return slot_enqueue(c, hvq_launch_select, "select", "hvq_label.hip", jobs.data(), jobs.size() * sizeof(HvqSelectJob), n, max_tiles, hip_stream);
+}
+
+/* Exact distance transforms of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Distances").  The two launches
+ * of a call go behind ONE job table; the map is the only working memory. */
+HVQ_EXPORT int hvq_distance_check(const HvqDistanceRule *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    if (r->plane < 0 || r->plane > 2) return fail(HVQ_E_ARG, "distance rule: plane %d (0 Y, 1 U, 2 V)", r->plane);
+    if (r->lo < 0 || r->lo > r->hi || r->hi > 255) return fail(HVQ_E_ARG, "distance rule: window %d .. %d (0 <= lo <= hi <= 255)", r->lo, r->hi);
+    if (r->metric < HVQ_DST_EUCLID2 || r->metric > HVQ_DST_CHESS) return fail(HVQ_E_ARG, "distance rule: metric %d (0 EUCLID2, 1 CITY, 2 CHESS)", r->metric);
+    if (r->border < 0 || r->border > 1) return fail(HVQ_E_ARG, "distance rule: border %d (0 or 1)", r->border);
+    if (r->pad[0] || r->pad[1] || r->pad[2]) return fail(HVQ_E_ARG, "distance rule: pad must be 0");
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int64_t hvq_distance_bytes(int width, int height, int h_samp, int v_samp, int plane)
+{
+    return hvq_label_bytes(width, height, h_samp, v_samp, plane);     /* a uint32 a sample, like a label map */
+}
+
+HVQ_EXPORT int hvq_distance_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                     const HvqDistanceRule *rules, int nrules, const int *which, uint32_t *const *dist, void *hip_stream)
+{
+    static_assert(HVQ_DST_EUCLID2 == (int)HVQ_DT_EUCLID2 && HVQ_DST_CITY == (int)HVQ_DT_CITY && HVQ_DST_CHESS == (int)HVQ_DT_CHESS && HVQ_DST_NONE == HVQ_DT_NONE,
+                  "the header's values are the kernels'");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dist || !rules))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nrules < 1 || nrules > HVQ_DST_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", nrules, HVQ_DST_MAX_RULES);
+    for (int r = 0; r < nrules; ++r) { int rc = hvq_distance_check(rules + r); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqDistanceJob> jobs((size_t)n);
+    uint32_t max_cols = 0, max_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("distance map", i, dist[i]); if (rc) return rc; }
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nrules) return fail(HVQ_E_ARG, "picture %d: rule %d of %d", i, r, nrules);
+        const HvqDistanceRule &rule = rules[r];
+        HvqDistanceJob &j = jobs[(size_t)i];
+        plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            if (p == rule.plane)
+                j = hvq_dt_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)dist[i], nx, ny, (uint32_t)rule.lo, (uint32_t)rule.hi, (uint32_t)rule.metric,
+                               (uint32_t)rule.border);
+            return 0;
+        });
+        if (j.nx > HVQ_DT_SPAN) return fail(HVQ_E_ARG, "picture %d: a row of %u samples, the row pass holds %u", i, j.nx, HVQ_DT_SPAN);
+        max_cols = std::max(max_cols, j.colgroups);
+        max_rows = std::max(max_rows, j.rowgroups);
+    }
+    if (!hvq_launch_distance) return fail(HVQ_E_NOGPU, "this build of the library has no distance kernels (hvq_distance.hip is not linked)");
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqDistanceJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_distance(t, n, max_cols, max_rows, st); });
+}
+
+/* Distances back into mask pictures in slot layout.  No picture is looked up: the stream gives the geometry; the launch goes behind its
+ * job table through export_enqueue, so it is ordered behind an hvq_distance_pictures on the same stream. */
+HVQ_EXPORT int hvq_distance_mask_check(const HvqDistanceMask *m)
+{
+    if (!m) return fail(HVQ_E_ARG, "bad arguments");
+    if (m->mode > (uint32_t)HVQ_DSM_ROOT) return fail(HVQ_E_ARG, "distance mask: mode %u (0 RANGE, 1 ROOT)", m->mode);
+    if (m->lo > m->hi) return fail(HVQ_E_ARG, "distance mask: range %u .. %u", m->lo, m->hi);
+    if (m->invert > 1u) return fail(HVQ_E_ARG, "distance mask: invert %u (0 or 1)", m->invert);
+    if (m->pad[0] || m->pad[1] || m->pad[2] || m->pad[3]) return fail(HVQ_E_ARG, "distance mask: pad must be 0");
+    if (m->mode == (uint32_t)HVQ_DSM_ROOT && (m->lo || m->hi || m->invert)) return fail(HVQ_E_ARG, "distance mask: ROOT takes lo, hi and invert 0");
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_distance_mask(HvqContext *c, int n, const int *streams, const uint32_t *const *dist, const HvqDistanceMask *sel, int nsel,
+                                 const int *which, void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_DSM_RANGE == (int)HVQ_DM_RANGE && HVQ_DSM_ROOT == (int)HVQ_DM_ROOT, "the header's values are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !dist || !sel || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nsel < 1 || nsel > HVQ_DSM_MAX) return fail(HVQ_E_ARG, "%d masks: one call takes 1 .. %d", nsel, HVQ_DSM_MAX);
+    for (int k = 0; k < nsel; ++k) { int rc = hvq_distance_mask_check(sel + k); if (rc) return rc; }
+    std::vector<HvqDistMaskJob> jobs((size_t)n * 3u);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0 || (size_t)streams[i] >= c->streams.size() || !c->streams[(size_t)streams[i]].open) return fail(HVQ_E_ARG, "bad stream %d", streams[i]);
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("distance map", i, dist[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
+        const int k = which ? which[i] : 0;
+        if (k < 0 || k >= nsel) return fail(HVQ_E_ARG, "picture %d: mask %d of %d", i, k, nsel);
+        uint8_t *const b = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            HvqDistMaskJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_dm_job((uint64_t)(uintptr_t)dist[i], (uint64_t)(uintptr_t)(b + off), nx, ny, p ? HVQ_DM_FILL : sel[k].mode, sel[k].lo, sel[k].hi, sel[k].invert);
+            return j.tiles;
+        }));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    return slot_enqueue(c, hvq_launch_distance_mask, "distance mask", "hvq_distance.hip", jobs.data(), jobs.size() * sizeof(HvqDistMaskJob), n, max_tiles, hip_stream);
 }
 
 /* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job

@@ -1041,6 +1041,79 @@ typedef struct HvqSelect { uint32_t area_min, area_max, w_min, w_max, h_min, h_m
 int     hvq_select_components(HvqContext *ctx, int n, const int *streams, const uint32_t *const *labels, const uint64_t *const *comps,
                               int cap, const HvqSelect *sel, int nsel, const int *which, void *const *dst, void *hip_stream);
 
+/* EXACT DISTANCE TRANSFORMS of resident pictures, where they lie: for ONE plane of each of `n` pictures, of any streams, sizes and
+ * samplings, how far every foreground sample is from the background, on the caller's HIP stream and without a host synchronisation.
+ * It is the step behind a mask that labelling is not: erosion and dilation by a disc of any radius, the thickness of an object, seeds
+ * for splitting touching blobs, a signed field, buffer zones.  This text is the authority for the values.
+ *   Foreground. Picture i goes through rules[which[i]] (which == NULL: rules[0] for all).  A sample a of plane rule.plane (0 Y, 1 U, 2 V;
+ *              Nx x Ny samples at the plane's own resolution) is foreground when lo <= a <= hi, as in HvqLabelRule; everything else is
+ *              background.  The distance of the background to the foreground is the same call with the complementary window; a signed
+ *              field is two calls.
+ *   dist[i]    a DEVICE pointer, a non-null multiple of 16: uint32 [Ny][Nx], dense, hvq_distance_bytes bytes.  0 at a background
+ *              sample.  At a foreground sample (x, y) the minimum over all background samples (bx, by) of the plane of
+ *              (bx - x)^2 + (by - y)^2 under HVQ_DST_EUCLID2, |bx - x| + |by - y| under HVQ_DST_CITY, max(|bx - x|, |by - y|) under
+ *              HVQ_DST_CHESS.  With border = 1 the samples just outside the plane count as background too, which adds the candidate
+ *              e = min(x + 1, Nx - x, y + 1, Ny - y): e^2 under EUCLID2, e under the other two; with border = 0 nothing outside the
+ *              plane exists.  A foreground sample with no candidate at all (a plane without background, border = 0) holds
+ *              HVQ_DST_NONE.  Nothing is rounded; the largest plane is 8192 x 8192, so every other value is below 2^27.  Every
+ *              element is written once the call has run, nothing outside the map is written; while the work runs the map holds
+ *              working values.
+ *   Known answers.  An all-background plane: all 0.  A full 8 x 5 plane with border = 0: all HVQ_DST_NONE; with border = 1 under
+ *              EUCLID2 the rows 1 1 1 1 1 1 1 1 / 1 4 4 4 4 4 4 1 / 1 4 9 9 9 9 4 1 / 1 4 4 4 4 4 4 1 / 1 1 1 1 1 1 1 1.  An 8 x 6
+ *              plane whose only background sample is (0, 0) has 7^2 + 5^2 = 74 at (7, 5), 12 under CITY and 7 under CHESS.
+ *   hvq_distance_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL rule, a plane outside 0 .. 2, a window that is not
+ *              0 <= lo <= hi <= 255, a metric outside 0 .. 2, a border outside 0 .. 1, a pad that is not 0.
+ *   hvq_distance_bytes (host only): 4 Nx Ny of that plane of such a picture; HVQ_E_GEOMETRY, or HVQ_E_ARG for the plane.
+ *   The call.  Two launches behind one job table, and no memory besides the map: a lane walks four columns down and up and leaves the
+ *              vertical distances in the map; a workgroup stages whole rows of them (HVQ_DT_SPAN = 8192 samples, uint16) in LDS and
+ *              overwrites the rows in place with the minimum over the row, searching outwards from each sample until nothing further
+ *              out can win.  Integers only: the values do not depend on any order.
+ *   HVQ_E_ARG for the whole call: what hvq_distance_check refuses, in any entry, used or not; nrules outside 1 .. HVQ_DST_MAX_RULES; a
+ *              which[i] outside 0 .. nrules - 1; a null or misaligned dist[i]; n above 65535; a bad stream or ordinal; a src[i] with
+ *              an ordinal other than -1 or that is no multiple of 16; a NULL context, rules or dist.  n == 0 is HVQ_OK and does
+ *              nothing.  Every argument is checked before anything is enqueued: a refused call leaves every output untouched.
+ *              HVQ_E_NOGPU (after those checks) from a build without the distance kernels.
+ *   a_i and `src`, lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain and slot safety are
+ *   hvq_label_pictures'. */
+#define HVQ_DST_EUCLID2 0
+#define HVQ_DST_CITY    1
+#define HVQ_DST_CHESS   2
+#define HVQ_DST_NONE    0xFFFFFFFFu
+#define HVQ_DST_MAX_RULES 64
+typedef struct HvqDistanceRule { int32_t plane, lo, hi, metric, border, pad[3]; } HvqDistanceRule;
+int     hvq_distance_check(const HvqDistanceRule *r);
+int64_t hvq_distance_bytes(int width, int height, int h_samp, int v_samp, int plane);   /* 4 * Nx * Ny of that plane */
+int     hvq_distance_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                              const HvqDistanceRule *rules, int nrules, const int *which,
+                              uint32_t *const *dist, void *hip_stream);
+
+/* DISTANCES BACK INTO PICTURES: output i is a uint8 picture in slot layout (Y | U | V) of the geometry of streams[i] -- the stream gives
+ * the geometry only, no picture is looked up --, so the result composes with whatever takes `src`.  One launch of the map kernel's shape
+ * on the caller's stream, a member of the export chain.
+ *   Values.    With d the distance of a Y sample and S = sel[which[i]] (which == NULL: sel[0] for all).  HVQ_DSM_RANGE: Y is 255 where
+ *              lo <= d <= hi, else 0; invert = 1 swaps the two, after that rule.  HVQ_DST_NONE is an ordinary value here: hi =
+ *              0xFFFFFFFF includes it.  HVQ_DSM_ROOT: Y is min(255, isqrt(d)), isqrt the exact integer floor square root, so
+ *              HVQ_DST_NONE gives 255; lo, hi and invert must be 0.  It is the viewable field under EUCLID2.  U and V are filled
+ *              with 128.
+ *              Erosion by a disc of radius r is hvq_distance_pictures (EUCLID2) -> RANGE [r^2 + 1, HVQ_DST_NONE]; dilation by a disc
+ *              is the same on the complementary window, inverted.
+ *   Inputs.    dist[i] is a map of the Y plane (a rule with plane 0) of a picture of that geometry, read when the work runs: distance
+ *              -> mask on one stream needs no host synchronisation.
+ *   The call.  dst[i] is a non-null DEVICE pointer, a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written,
+ *              each once; nothing outside them.
+ *   HVQ_E_ARG for the whole call: nsel outside 1 .. HVQ_DSM_MAX; in any entry, used or not, lo above hi, a mode outside 0 .. 1, an
+ *              invert other than 0 or 1, a pad that is not 0, under ROOT a lo, hi or invert that is not 0; a which[i] outside
+ *              0 .. nsel - 1; a null or misaligned dist[i] or dst[i]; n above 65535; a bad stream; a NULL context, dist, sel or dst.
+ *              n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued.  HVQ_E_NOGPU (after those
+ *              checks) from a build without the kernel. */
+#define HVQ_DSM_RANGE 0
+#define HVQ_DSM_ROOT  1
+#define HVQ_DSM_MAX 64
+typedef struct HvqDistanceMask { uint32_t mode, lo, hi, invert, pad[4]; } HvqDistanceMask;
+int     hvq_distance_mask_check(const HvqDistanceMask *m);
+int     hvq_distance_mask(HvqContext *ctx, int n, const int *streams, const uint32_t *const *dist,
+                          const HvqDistanceMask *sel, int nsel, const int *which, void *const *dst, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
