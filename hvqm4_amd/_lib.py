@@ -112,6 +112,10 @@ class HvqDistanceMask(C.Structure):            # an entry of hvq_distance_mask: 
     _fields_ = [(n, C.c_uint32) for n in ("mode", "lo", "hi", "invert")] + [("pad", C.c_uint32 * 4)]
 
 
+class HvqWindowRule(C.Structure):              # include/hvqm4_amd.h: an entry of hvq_window_pictures: the plane of the tables, the mode (HVQ_WIN_*), the radii, k, c, invert
+    _fields_ = [(n, C.c_int32) for n in ("plane", "mode", "rx", "ry", "k", "c", "invert", "pad")]
+
+
 class HvqWarp(C.Structure):                     # include/hvqm4_amd.h: the map of a picture of hvq_warp_pictures, Q16, target -> source
     _fields_ = [(n, C.c_int32) for n in ("m00", "m01", "m10", "m11", "t0", "t1", "border")] + [("fill", C.c_uint8 * 3), ("pad", C.c_uint8)]
 
@@ -228,6 +232,12 @@ SYMBOLS = {
                                         C.c_void_p]),
     "hvq_distance_mask_check": (C.c_int, [C.c_void_p]),
     "hvq_distance_mask": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_integral_bytes": (C.c_int64, [C.c_int] * 6),
+    "hvq_integral_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvq_window_check": (C.c_int, [C.c_void_p]),
+    "hvq_window_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "hvq_rect_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_check": (C.c_int, [C.c_void_p]),
     "hvq_warp_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hvq_warp_body": (C.c_int, [C.c_void_p] + [C.c_int] * 6),

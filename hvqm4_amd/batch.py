@@ -1021,6 +1021,138 @@ class Context:
             spare, cur = cur, res
         return cur
 
+    @staticmethod
+    def _tables(given, name, n, shapes, dtype, optional=False):
+        """the caller's list of n tables (int32 [Ny, Nx] of S, viewed from the uint32 memory, or int64 of Q), contiguous and 16-byte
+        aligned, on a GPU; optional: an entry may be None -> their addresses (0 for None)"""
+        import torch
+        if not isinstance(given, (list, tuple)) or len(given) != n:
+            raise ValueError(f"{name} must be a list of {n} tensors")
+        for i, t in enumerate(given):
+            if t is None and optional:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shapes[i]) or not t.is_contiguous() or t.data_ptr() & 15:
+                raise ValueError(f"{name}[{i}] must be a contiguous, 16-byte aligned {str(dtype).replace('torch.', '')} tensor of shape {tuple(shapes[i])}")
+            if t.device.type != "cuda":
+                raise ValueError(f"{name}[{i}] is not on a GPU")
+        return [0 if t is None else t.data_ptr() for t in given]
+
+    def integral_pictures(self, sids, ordinals, planes=0, squares=True, src=None, out=None):
+        """hvq_integral_pictures: the inclusive summed-area tables of one plane of the resident pictures (sids[i], ordinals[i]) -- the
+        values are include/hvqm4_amd.h's --, on torch's current stream, without a host synchronisation and without moving a picture.
+        `planes`: 0 Y, 1 U, 2 V, one for all or a list of one per picture.  -> (sums, squares): lists of n CUDA tensors, sums[i] int32
+        [Ny, Nx] viewed from the uint32 memory (modulo 2^32: a rectangle of at most 2^24 samples comes out exact from the wrapped
+        corners), squares[i] int64 [Ny, Nx]; `squares` False: no tables of squares, the second list is None.  `out`, if given: such a
+        pair of lists (the second None without squares), contiguous, 16-byte aligned.  hvqm4_amd.integral gives the expected values
+        (of_plane), the padded view and the sum of a rectangle.  `src` as in picture_checksums.  Ordering and slot safety are
+        export()'s."""
+        import torch
+        from .labels import plane_shape
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        planes = [planes] * n if isinstance(planes, int) and not isinstance(planes, bool) else [int(p) for p in planes]
+        if len(planes) != n or any(not 0 <= p <= 2 for p in planes):
+            raise ValueError(f"planes: 0 Y, 1 U, 2 V, one for all or {n} of them")
+        from .checksums import sources
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        shapes = [plane_shape(self._geometry(sids[i]), planes[i]) for i in range(n)]
+        if out is None:
+            sums = [torch.empty(shapes[i], dtype=torch.int32, device="cuda") for i in range(n)]
+            sq = [torch.empty(shapes[i], dtype=torch.int64, device="cuda") for i in range(n)] if squares else None
+        else:
+            if not isinstance(out, (list, tuple)) or len(out) != 2:
+                raise ValueError("out must be a pair (sums, squares) of lists")
+            sums, sq = list(out[0]), (list(out[1]) if squares else None)
+            if squares is False and out[1] is not None:
+                raise ValueError("out: tables of squares without squares=True")
+        p_s = Context._tables(sums, "sums", n, shapes, torch.int32)
+        p_q = Context._tables(sq, "squares", n, shapes, torch.int64) if squares else None
+        if not n:
+            return sums, sq
+        a_s, a_o, stream = Context._launch_args(sums[0].device, sids, ordinals)
+        a_p = C.cast((C.c_int * n)(*planes), C.c_void_p)
+        check(lib().hvq_integral_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), a_p, Context._ptr_array(p_s), Context._ptr_array(p_q), stream))
+        return sums, sq
+
+    def window_pictures(self, sids, ordinals, sums, squares, rules, which=None, src=None, out=None):
+        """hvq_window_pictures: the tables of integral_pictures (of the rule's plane, which must have the size of Y) and the pictures
+        (sids[i], ordinals[i]) back into uint8 pictures IN SLOT LAYOUT of the geometries of sids[i]: Y the local mean, the local
+        deviation or the threshold of the rule over its window cut to the plane, U and V 128.  `rules`: one hvqm4_amd.integral.Rule
+        (integral.mean / deviation / adaptive), a list of one per picture (equal ones share an entry; more than 64 distinct ones:
+        ValueError), or a list of distinct ones together with `which`.  `squares`: None, or a list whose entries may be None, where no
+        rule needs them.  The tables are read when the work runs on torch's current stream: integral -> window needs no host
+        synchronisation.  Return forms and `out` are rank_pictures'; whatever takes src= takes a row of the result.
+        hvqm4_amd.integral.of_picture gives the expected bytes.  `src` as in picture_checksums."""
+        import torch
+        from . import integral as ig
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if which is not None:
+            table, which = Context._explicit_table(rules, which, n, ig.Rule, ig.MAX_RULES, "rules")
+        else:
+            table, which = Context._table_which(rules, n, ig.Rule, "rules", "integral.Rule", ig.MAX_RULES, "rules")
+        for r in table:
+            ig.check(r)
+        shapes = []
+        for i in range(n):
+            w, h = self._geometry(sids[i])[:2]
+            shapes.append((h, w))
+        p_s = Context._tables(sums, "sums", n, shapes, torch.int32)
+        p_q = None if squares is None else Context._tables(squares, "squares", n, shapes, torch.int64, optional=True)
+        ptrs, out, device, where = Context._slot_frame(self, sids, ordinals, src, out)
+        if not n:
+            return out
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
+        from ._lib import HvqWindowRule
+        a_r = (HvqWindowRule * len(table))(*[r.struct() for r in table])
+        a_w = Context._which_array(which, n)
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_window_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), Context._ptr_array(p_s), Context._ptr_array(p_q), C.cast(a_r, C.c_void_p),
+                                        len(table), a_w, a_d, stream))
+        return out
+
+    def rect_sums(self, rects, sums, squares=None, dims=None, out=None):
+        """hvq_rect_sums: `rects`, a CUDA tensor int32 [nrects, 5] = (i, x0, y0, x1, y1) with inclusive corners (integral.rects_of_boxes
+        makes them of label_pictures' records on the device), against the tables of integral_pictures -> a CUDA tensor int64 [nrects,
+        3] = (count, S, Q), Q 0 where picture i has no table of squares; (0, 0, 0) for a rectangle that leaves its plane, is empty,
+        holds more than 2^24 samples or names no picture.  `dims`: a CUDA tensor int32 [n, 2] = (Nx, Ny); default: of the tables' shapes,
+        uploaded by this call (a caller that repeats the call keeps the tensor).  On torch's current stream, no host synchronisation.  hvqm4_amd.integral.of_rects gives the expected values."""
+        import torch
+        n = len(sums)
+        if not 1 <= n <= 65535:
+            raise ValueError(f"{n} pictures: one call takes 1 .. 65535")
+        if not isinstance(rects, torch.Tensor) or rects.dtype != torch.int32 or rects.dim() != 2 or rects.shape[1] != 5 or not rects.is_contiguous() or rects.device.type != "cuda":
+            raise ValueError("rects must be a contiguous int32 CUDA tensor of shape (nrects, 5)")
+        nrects = int(rects.shape[0])
+        shapes = [tuple(t.shape) if isinstance(t, torch.Tensor) else () for t in sums]
+        p_s = Context._tables(sums, "sums", n, shapes, torch.int32)
+        p_q = None if squares is None else Context._tables(squares, "squares", n, shapes, torch.int64, optional=True)
+        if dims is None:
+            dims = torch.tensor([[s[1], s[0]] for s in shapes], dtype=torch.int32).to(rects.device, non_blocking=False)
+        elif not isinstance(dims, torch.Tensor) or dims.dtype != torch.int32 or tuple(dims.shape) != (n, 2) or not dims.is_contiguous() or dims.device.type != "cuda":
+            raise ValueError(f"dims must be a contiguous int32 CUDA tensor of shape ({n}, 2)")
+        out = Context._out_tensor(out, (nrects, 3), torch.int64, name="out", align=8)
+        if not nrects:
+            return out
+        _a_s, _a_o, stream = Context._launch_args(rects.device, (), ())
+        check(lib().hvq_rect_sums(self._h, n, nrects, C.c_void_p(rects.data_ptr()), Context._ptr_array(p_s), Context._ptr_array(p_q), C.c_void_p(dims.data_ptr()),
+                                  C.c_void_p(out.data_ptr()), stream))
+        return out
+
+    def adaptive_pictures(self, sids, ordinals, rules, which=None, src=None, out=None):
+        """resident pictures (sids[i], ordinals[i]) through integral_pictures and window_pictures on torch's current stream, the tables
+        in scratch tensors that torch's allocator takes back behind the stream's work: local thresholds (integral.adaptive), means
+        and deviations with no host synchronisation.  Tables of squares are made only where a rule needs them.  `rules`, `which`, `src`
+        and `out` are window_pictures'.  hvqm4_amd.integral.of_picture gives the expected bytes."""
+        from . import integral as ig
+        n = len(sids)
+        flat = [rules] if isinstance(rules, ig.Rule) else list(rules or ())
+        for r in flat:
+            ig.check(r)
+        per = [flat[which[i]] for i in range(n)] if which is not None else (flat * n if isinstance(rules, ig.Rule) else flat)
+        if len(per) != n:
+            raise ValueError(f"rules: one integral.Rule, or a list of {n}, or a list of distinct ones together with which")
+        sums, squares = self.integral_pictures(sids, ordinals, [r.plane for r in per], squares=any(ig.needs_squares(r) for r in per), src=src)
+        return self.window_pictures(sids, ordinals, sums, squares, rules, which=which, src=src, out=out)
+
     def warp_force_direct(self, on) -> int:
         """hvq_warp_force_direct: every later warp_pictures of this context takes the direct body of the kernel (False / 0: the chosen
         one again; 2: the tiled one wherever LDS holds the box, for the measurement that sets the rule) -> the setting before.  The

@@ -845,5 +845,70 @@ static_assert(HVQ_DT_SPAN % (HVQ_DT_LANES * 4u) == 0u, "a lane of the row pass t
 _Static_assert(sizeof(HvqDistanceJob) == 64 && sizeof(HvqDistMaskJob) == 48, "job tables are uploaded in 16-byte units");
 #endif
 
+/* one picture of the two integral launches (hvq_integral.hip, hvq_integral_pictures): a plane and its inclusive summed-area tables, which
+ * are also the only working memory.  Grid row = picture in both launches.  Row pass: a workgroup of HVQ_IG_RLANES lanes is HVQ_IG_WAVES
+ * waves, a wave scans ONE row in chunks of HVQ_IG_CHUNK samples, a lane a dword of the plane a chunk.  Column pass: a workgroup of
+ * HVQ_IG_CLANES lanes owns HVQ_IG_COLS consecutive columns, a lane four of them, and adds downwards.  48 bytes. */
+#define HVQ_IG_WAVE   64u                            /* lanes of a wave: the width of the prefix */
+#define HVQ_IG_WAVES  4u                             /* rows of a workgroup of the row pass */
+#define HVQ_IG_RLANES (HVQ_IG_WAVE * HVQ_IG_WAVES)
+#define HVQ_IG_CHUNK  (HVQ_IG_WAVE * 4u)             /* samples of a wave a step */
+#define HVQ_IG_CLANES 64u
+#define HVQ_IG_COLS   (HVQ_IG_CLANES * 4u)           /* columns of a workgroup of the column pass */
+typedef struct HvqIntegralJob {
+    uint64_t src;                      /* device address of the plane, a multiple of 4 */
+    uint64_t sums;                     /* device address of uint32 [ny][nx], a multiple of 16 */
+    uint64_t squares;                  /* device address of uint64 [ny][nx], a multiple of 16, or 0: no such table */
+    uint32_t nx, ny;                   /* the plane; nx is a multiple of 4 */
+    uint32_t rowgroups;                /* ceil(ny / HVQ_IG_WAVES) */
+    uint32_t colgroups;                /* ceil(nx / HVQ_IG_COLS) */
+    uint32_t chunks;                   /* ceil(nx / HVQ_IG_CHUNK) */
+    uint32_t pad;
+} HvqIntegralJob;
+
+/* one picture of the window launch (hvq_integral.hip, hvq_window_pictures): the tables of a plane of Y's size, that plane, and the
+ * picture written in slot layout.  Grid row = picture; a workgroup of HVQ_WN_LANES lanes takes a tile of HVQ_WN_TX x HVQ_WN_TY samples of
+ * Y, a lane four adjacent samples (one dword stored), or, past the Y tiles, HVQ_WN_LANES * HVQ_WN_PER consecutive dwords of U | V, which
+ * follow Y in a slot and are filled with 128.  80 bytes. */
+#define HVQ_WN_TX     64u
+#define HVQ_WN_TY     16u
+#define HVQ_WN_LANES  256u
+#define HVQ_WN_PER    8u                             /* chroma dwords of a lane */
+#define HVQ_WN_MEAN      0u                          /* the modes of include/hvqm4_amd.h (HVQ_WIN_*) */
+#define HVQ_WN_DEVIATION 1u
+#define HVQ_WN_THRESHOLD 2u
+#define HVQ_WN_MAX_AREA  (1u << 24)                  /* the samples of a window, of a rectangle: 255 * 2^24 < 2^32 */
+typedef struct HvqWindowJob {
+    uint64_t src;                      /* device address of the plane the tables are of (THRESHOLD reads it), a multiple of 4 */
+    uint64_t sums;                     /* uint32 [ny][nx], a multiple of 16 */
+    uint64_t squares;                  /* uint64 [ny][nx], a multiple of 16, or 0 where the rule needs none */
+    uint64_t dst;                      /* device address of the picture written, a multiple of 16: Y, then cdwords dwords of 128 */
+    uint32_t nx, ny;                   /* Y; nx is a multiple of 4 */
+    uint32_t tx;                       /* ceil(nx / HVQ_WN_TX) */
+    uint32_t ytiles;                   /* tx * ceil(ny / HVQ_WN_TY) */
+    uint32_t cdwords;                  /* dwords of U | V */
+    uint32_t tiles;                    /* ytiles + ceil(cdwords / (HVQ_WN_LANES * HVQ_WN_PER)) */
+    uint32_t mode, rx, ry;
+    int32_t k, c;
+    uint32_t invert;
+} HvqWindowJob;
+
+/* the rectangle launch (hvq_integral.hip, hvq_rect_sums): ONE head, then one HvqRectTables a picture.  A lane a rectangle. */
+#define HVQ_RC_LANES 256u
+typedef struct HvqRectHead {
+    uint64_t rects;                    /* device address of int32 [nrects][5]: i, x0, y0, x1, y1 */
+    uint64_t dims;                     /* device address of uint32 [npics][2]: nx, ny */
+    uint64_t out;                      /* device address of uint64 [nrects][3]: count, S, Q */
+    uint32_t nrects, npics;
+} HvqRectHead;
+typedef struct HvqRectTables { uint64_t sums, squares; } HvqRectTables;      /* of picture i; squares 0: Q comes out 0 */
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqIntegralJob) == 48 && sizeof(HvqWindowJob) == 80 && sizeof(HvqRectHead) == 32 && sizeof(HvqRectTables) == 16, "job tables are uploaded in 16-byte units");
+static_assert(HVQ_WN_TX * HVQ_WN_TY == HVQ_WN_LANES * 4u && HVQ_WN_TX % 4u == 0u, "a lane of the window launch takes four adjacent samples");
+#else
+_Static_assert(sizeof(HvqIntegralJob) == 48 && sizeof(HvqWindowJob) == 80 && sizeof(HvqRectHead) == 32 && sizeof(HvqRectTables) == 16, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

@@ -47,6 +47,7 @@
 #include "hvq_map.h"
 #include "hvq_label.h"
 #include "hvq_distance.h"
+#include "hvq_integral.h"
 #include "hvq_warp.h"
 #include "hvq_compose.h"
 
@@ -110,6 +111,10 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_select(const void *jobs_d
 /* hvq_distance.hip.  Weak for the same reason: hvq_distance_pictures and hvq_distance_mask then refuse with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_distance(const void *jobs_dev, int npics, uint32_t max_colgroups, uint32_t max_rowgroups, hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_distance_mask(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_integral.hip.  Weak for the same reason: hvq_integral_pictures, hvq_window_pictures and hvq_rect_sums then refuse with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_integral(const void *jobs_dev, int npics, uint32_t max_rowgroups, uint32_t max_colgroups, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_window(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t hvq_launch_rects(const void *head_dev, int npics, uint32_t nrects, hipStream_t stream);
 /* hvq_warp.hip.  Weak for the same reason: hvq_warp_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_warp(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_compose.hip.  Weak for the same reason: hvq_compose_pictures then refuses with HVQ_E_NOGPU */
@@ -3454,6 +3459,130 @@ HVQ_EXPORT int hvq_distance_mask(HvqContext *c, int n, const int *streams, const
     }
     HIPCHK(hipSetDevice(c->device));
     return slot_enqueue(c, hvq_launch_distance_mask, "distance mask", "hvq_distance.hip", jobs.data(), jobs.size() * sizeof(HvqDistMaskJob), n, max_tiles, hip_stream);
+}
+
+/* Summed-area tables of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Integrals").  The two launches of a
+ * call go behind ONE job table; the tables are the only working memory. */
+HVQ_EXPORT int64_t hvq_integral_bytes(int width, int height, int h_samp, int v_samp, int plane, int order)
+{
+    if (order != 1 && order != 2) return fail(HVQ_E_ARG, "order %d (1 sums, 2 squares)", order);
+    const int64_t b = hvq_label_bytes(width, height, h_samp, v_samp, plane);    /* a uint32 a sample */
+    return b < 0 ? b : b * order;
+}
+
+HVQ_EXPORT int hvq_integral_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, const int *which_plane,
+                                     uint32_t *const *sums, uint64_t *const *squares, void *hip_stream)
+{
+    if (!c || n < 0 || (n && (!streams || !ordinals || !sums))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqIntegralJob> jobs((size_t)n);
+    uint32_t max_rows = 0, max_cols = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("table of sums", i, sums[i]); if (rc) return rc; }
+        uint64_t *const q = squares ? squares[i] : nullptr;
+        if ((uintptr_t)q & 15u) return fail(HVQ_E_ARG, "table of squares %d: the pointer must be a multiple of 16", i);
+        const int plane = which_plane ? which_plane[i] : 0;
+        if (plane < 0 || plane > 2) return fail(HVQ_E_ARG, "picture %d: plane %d (0 Y, 1 U, 2 V)", i, plane);
+        HvqIntegralJob &j = jobs[(size_t)i];
+        plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            if (p == plane) j = hvq_ig_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)sums[i], (uint64_t)(uintptr_t)q, nx, ny);
+            return 0;
+        });
+        max_rows = std::max(max_rows, j.rowgroups);
+        max_cols = std::max(max_cols, j.colgroups);
+    }
+    if (!hvq_launch_integral) return fail(HVQ_E_NOGPU, "this build of the library has no integral kernels (hvq_integral.hip is not linked)");
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqIntegralJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_integral(t, n, max_rows, max_cols, st); });
+}
+
+/* Tables back into pictures in slot layout: local means, deviations, thresholds.  The launch goes behind its job table through
+ * export_enqueue, so it is ordered behind an hvq_integral_pictures on the same stream. */
+HVQ_EXPORT int hvq_window_check(const HvqWindowRule *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    if (r->plane < 0 || r->plane > 2) return fail(HVQ_E_ARG, "window rule: plane %d (0 Y, 1 U, 2 V)", r->plane);
+    if (r->mode < HVQ_WIN_MEAN || r->mode > HVQ_WIN_THRESHOLD) return fail(HVQ_E_ARG, "window rule: mode %d (0 MEAN, 1 DEVIATION, 2 THRESHOLD)", r->mode);
+    if (r->rx < 0 || r->rx > HVQ_WIN_MAX_RADIUS || r->ry < 0 || r->ry > HVQ_WIN_MAX_RADIUS)
+        return fail(HVQ_E_ARG, "window rule: radii %d, %d (0 .. %d)", r->rx, r->ry, HVQ_WIN_MAX_RADIUS);
+    if (r->k < -1024 || r->k > 1024) return fail(HVQ_E_ARG, "window rule: k %d (-1024 .. 1024)", r->k);
+    if (r->c < -255 || r->c > 255) return fail(HVQ_E_ARG, "window rule: c %d (-255 .. 255)", r->c);
+    if (r->invert < 0 || r->invert > 1) return fail(HVQ_E_ARG, "window rule: invert %d (0 or 1)", r->invert);
+    if (r->pad) return fail(HVQ_E_ARG, "window rule: pad must be 0");
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_window_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src, const uint32_t *const *sums,
+                                   const uint64_t *const *squares, const HvqWindowRule *rules, int nrules, const int *which, void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_WIN_MEAN == (int)HVQ_WN_MEAN && HVQ_WIN_DEVIATION == (int)HVQ_WN_DEVIATION && HVQ_WIN_THRESHOLD == (int)HVQ_WN_THRESHOLD,
+                  "the header's values are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !sums || !rules || !dst))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nrules < 1 || nrules > HVQ_WIN_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", nrules, HVQ_WIN_MAX_RULES);
+    for (int r = 0; r < nrules; ++r) { int rc = hvq_window_check(rules + r); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqWindowJob> jobs((size_t)n);
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("table of sums", i, sums[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
+        const uint64_t *const q = squares ? squares[i] : nullptr;
+        if ((uintptr_t)q & 15u) return fail(HVQ_E_ARG, "table of squares %d: the pointer must be a multiple of 16", i);
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nrules) return fail(HVQ_E_ARG, "picture %d: rule %d of %d", i, r, nrules);
+        const HvqWindowRule &rule = rules[r];
+        if (!q && hvq_wn_needs_squares((uint32_t)rule.mode, rule.k)) return fail(HVQ_E_ARG, "picture %d: rule %d needs the table of squares", i, r);
+        size_t plane_off = 0;
+        uint32_t pnx = 0, pny = 0, ynx = 0, yny = 0, cdwords = 0;
+        plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            if (!p) { ynx = nx; yny = ny; } else cdwords += (nx * ny) >> 2;
+            if (p == rule.plane) { plane_off = off; pnx = nx; pny = ny; }
+            return 0;
+        });
+        if (pnx != ynx || pny != yny) return fail(HVQ_E_ARG, "picture %d: plane %d is %u x %u, Y %u x %u: the result is written into Y", i, rule.plane, pnx, pny, ynx, yny);
+        const uint64_t wx = std::min<uint64_t>(2u * (uint64_t)rule.rx + 1u, ynx), wy = std::min<uint64_t>(2u * (uint64_t)rule.ry + 1u, yny);
+        if (wx * wy > HVQ_WN_MAX_AREA) return fail(HVQ_E_ARG, "picture %d: a window of %llu x %llu samples, a window holds 2^24", i, (unsigned long long)wx, (unsigned long long)wy);
+        HvqWindowJob &j = jobs[(size_t)i];
+        j = hvq_wn_job((uint64_t)(uintptr_t)(a + plane_off), (uint64_t)(uintptr_t)sums[i], (uint64_t)(uintptr_t)q, (uint64_t)(uintptr_t)dst[i], ynx, yny, cdwords,
+                       (uint32_t)rule.mode, (uint32_t)rule.rx, (uint32_t)rule.ry, rule.k, rule.c, (uint32_t)rule.invert);
+        max_tiles = std::max(max_tiles, j.tiles);
+    }
+    return slot_enqueue(c, hvq_launch_window, "window", "hvq_integral.hip", jobs.data(), jobs.size() * sizeof(HvqWindowJob), n, max_tiles, hip_stream);
+}
+
+/* Sums of rectangles that lie in device memory.  No picture is looked up; ONE head and a pair of tables a picture go up as the job table */
+HVQ_EXPORT int hvq_rect_sums(HvqContext *c, int n, int nrects, const int32_t *rects, const uint32_t *const *sums, const uint64_t *const *squares, const uint32_t *dims,
+                             uint64_t *out, void *hip_stream)
+{
+    if (!c || n < 0 || nrects < 0 || !sums) return fail(HVQ_E_ARG, "bad arguments");
+    if (n < 1) return fail(HVQ_E_ARG, "%d pictures: one call takes 1 .. 65535", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (nrects > HVQ_RECT_MAX) return fail(HVQ_E_ARG, "%d rectangles: one call takes %d at the most", nrects, HVQ_RECT_MAX);
+    if (!nrects) return HVQ_OK;
+    if (!rects || ((uintptr_t)rects & 3u) || !dims || ((uintptr_t)dims & 3u) || !out || ((uintptr_t)out & 7u))
+        return fail(HVQ_E_ARG, "rects and dims must be non-null multiples of 4, out a non-null multiple of 8");
+    std::vector<HvqRectTables> tab((size_t)n + 2u);                    /* the head takes the room of two */
+    static_assert(sizeof(HvqRectHead) == 2 * sizeof(HvqRectTables), "the head lies before the tables");
+    HvqRectHead head = { (uint64_t)(uintptr_t)rects, (uint64_t)(uintptr_t)dims, (uint64_t)(uintptr_t)out, (uint32_t)nrects, (uint32_t)n };
+    memcpy(tab.data(), &head, sizeof head);
+    for (int i = 0; i < n; ++i) {
+        { int rc = slot_pointer_check("table of sums", i, sums[i]); if (rc) return rc; }
+        const uint64_t *const q = squares ? squares[i] : nullptr;
+        if ((uintptr_t)q & 15u) return fail(HVQ_E_ARG, "table of squares %d: the pointer must be a multiple of 16", i);
+        tab[(size_t)i + 2u] = HvqRectTables{ (uint64_t)(uintptr_t)sums[i], (uint64_t)(uintptr_t)q };
+    }
+    HIPCHK(hipSetDevice(c->device));
+    return slot_enqueue(c, hvq_launch_rects, "rectangle", "hvq_integral.hip", tab.data(), tab.size() * sizeof(HvqRectTables), n, (uint32_t)nrects, hip_stream);
 }
 
 /* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job

@@ -1114,6 +1114,90 @@ int     hvq_distance_mask_check(const HvqDistanceMask *m);
 int     hvq_distance_mask(HvqContext *ctx, int n, const int *streams, const uint32_t *const *dist,
                           const HvqDistanceMask *sel, int nsel, const int *which, void *const *dst, void *hip_stream);
 
+/* SUMMED-AREA TABLES of resident pictures, where they lie: for ONE plane of each of `n` pictures, of any streams, sizes and samplings,
+ * the inclusive table of sums and, where asked, of squares, on the caller's HIP stream and without a host synchronisation.  A table makes
+ * the sum of a window of ANY size cost four reads: local means and deviations over windows far wider than the filter and rank calls
+ * reach, thresholds relative to them (a page, a vignette, a night scene with one lamp, where one threshold a plane fails), the mean
+ * brightness of every box that hvq_label_pictures found, Haar-like features.  This text is the authority for the values.
+ *   Tables.    Picture i contributes plane which_plane[i] (0 Y, 1 U, 2 V; Nx x Ny samples a at the plane's own resolution;
+ *              which_plane == NULL: Y of all).  sums[i] is a DEVICE pointer, a non-null multiple of 16: uint32 [Ny][Nx], dense,
+ *                  S(x, y) = sum of a(x', y') over x' <= x, y' <= y,   modulo 2^32.
+ *              A plane holds up to 2^26 samples, so S wraps, by design: the sum of a rectangle of at most 2^24 samples comes out exact
+ *              from the wrapped corners in uint32 arithmetic, because 255 * 2^24 < 2^32.  `squares` may be NULL; where squares[i] is
+ *              non-null it is a multiple of 16, uint64 [Ny][Nx], Q(x, y) = the same sum of a^2, which never wraps (2^26 * 255^2 < 2^64).
+ *              The tables are INCLUSIVE, not the (Ny + 1) x (Nx + 1) tables of other libraries: rows stay multiples of 16 bytes.  A
+ *              corner at x = -1 or y = -1 reads as 0.  Every element is written once the call has run, nothing outside the tables;
+ *              while the work runs they hold working values.
+ *   hvq_integral_bytes (host only): 4 Nx Ny (order 1) or 8 Nx Ny (order 2) of that plane of such a picture; HVQ_E_GEOMETRY, or HVQ_E_ARG
+ *              for the plane or the order.
+ *   The call.  Two launches behind one job table, and no memory besides the tables: a wave scans a row a dword of the plane a lane a
+ *              step (HVQ_IG_CHUNK = 256 samples a step: the prefix of the lanes' totals by shuffles, a carry from step to step); then a
+ *              lane walks four columns downwards in place.  Integers only: the values do not depend on any order.
+ *   HVQ_E_ARG for the whole call: a which_plane[i] outside 0 .. 2; a null or misaligned sums[i]; a misaligned squares[i]; n above
+ *              65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no multiple of 16; a NULL context or
+ *              sums.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a refused call leaves
+ *              every output untouched.  HVQ_E_NOGPU (after those checks) from a build without the integral kernels.
+ *   a_i and `src`, lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain and slot safety are
+ *   hvq_distance_pictures'. */
+int64_t hvq_integral_bytes(int width, int height, int h_samp, int v_samp, int plane, int order);   /* 4 or 8 * Nx * Ny of that plane */
+int     hvq_integral_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                              const int *which_plane, uint32_t *const *sums, uint64_t *const *squares, void *hip_stream);
+
+/* TABLES BACK INTO PICTURES: output i is a uint8 picture in slot layout (Y | U | V) of the geometry of streams[i]; Y holds the result, U
+ * and V are filled with 128, exactly as hvq_distance_mask does, so the result goes wherever `src` goes.  One launch on the caller's
+ * stream, a member of the export chain.
+ *   Inputs.    Picture i goes through rules[which[i]] (which == NULL: rules[0] for all).  sums[i] (and squares[i]) are the tables of
+ *              plane rule.plane of picture i as hvq_integral_pictures left them, read when the work runs: integral -> window on one
+ *              stream needs no host synchronisation.  That plane must have the size of Y: plane 0, or any plane of a 4:4:4 picture.
+ *              The picture itself (a_i, `src`, lookup as in hvq_integral_pictures) is read by HVQ_WIN_THRESHOLD only.
+ *   Window.    The window of sample (x, y) is [x - rx, x + rx] x [y - ry, y + ry], CUT TO THE PLANE: nothing is replicated.  Let n be
+ *              the number of samples left in the window, S their sum and Q their sum of squares, a the sample itself.
+ *   HVQ_WIN_MEAN       (2 S + n) / (2 n) rounded down: the mean rounded half up.  It is the only rounding.
+ *   HVQ_WIN_DEVIATION  the largest d with (d n)^2 <= n Q - S^2: the floor of the population standard deviation, always in 0 .. 127.
+ *   HVQ_WIN_THRESHOLD  255 where 256 n a > 256 S + k d n - 256 c n, else 0, with d as in HVQ_WIN_DEVIATION; invert = 1 swaps the two.
+ *              It reads as a > mean + (k / 256) d - c: k = 0 is the "mean - C" rule and needs no squares, k != 0 is Niblack's rule on
+ *              the integer deviation.  k in -1024 .. 1024, c in -255 .. 255: everything fits int64.  The other two modes ignore k, c
+ *              and invert.
+ *   Known answers.  A plane of constant v: MEAN v, DEVIATION 0, THRESHOLD with k = 0 gives 0 for c <= 0 and 255 for c > 0.  A 0 / 255
+ *              checkerboard wherever the cut window has an even number of samples: DEVIATION 127.  rx >= Nx and ry >= Ny: every sample
+ *              sees the whole plane.  An 8192 x 2064 plane of 255: S(Nx - 1, Ny - 1) = 4 311 613 440 mod 2^32 = 16 646 144, and the
+ *              rectangle x 100 .. 8191, y 10 .. 2057 (16 572 416 samples) still gives exactly 255 * 16 572 416.
+ *   hvq_window_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL rule, a plane outside 0 .. 2, a mode outside 0 .. 2, rx or ry outside
+ *              0 .. 8191, k outside -1024 .. 1024, c outside -255 .. 255, an invert other than 0 or 1, a pad that is not 0.
+ *   The call.  dst[i] is a non-null DEVICE pointer, a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written,
+ *              each once; nothing outside them.  A workgroup takes 64 x 16 samples of Y, a lane four adjacent ones.
+ *   HVQ_E_ARG for the whole call: what hvq_window_check refuses, in any entry, used or not; nrules outside 1 .. HVQ_WIN_MAX_RULES; a
+ *              which[i] outside 0 .. nrules - 1; min(2 rx + 1, Nx) * min(2 ry + 1, Ny) above 2^24 for any picture; a rule that needs Q
+ *              (DEVIATION, THRESHOLD with k != 0) where `squares` or squares[i] is NULL; a rule whose plane has not the size of Y; a
+ *              null or misaligned sums[i] or dst[i], a misaligned squares[i]; n above 65535; a bad stream or ordinal, a bad src[i]; a
+ *              NULL context, sums, rules or dst.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is
+ *              enqueued.  HVQ_E_NOGPU (after those checks) from a build without the kernel. */
+#define HVQ_WIN_MEAN      0
+#define HVQ_WIN_DEVIATION 1
+#define HVQ_WIN_THRESHOLD 2
+#define HVQ_WIN_MAX_RULES 64
+#define HVQ_WIN_MAX_RADIUS 8191
+typedef struct HvqWindowRule { int32_t plane, mode, rx, ry, k, c, invert, pad; } HvqWindowRule;
+int     hvq_window_check(const HvqWindowRule *r);
+int     hvq_window_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                            const uint32_t *const *sums, const uint64_t *const *squares, const HvqWindowRule *rules, int nrules,
+                            const int *which, void *const *dst, void *hip_stream);
+
+/* SUMS OF RECTANGLES from the tables of `n` pictures, the rectangles IN DEVICE MEMORY: the boxes of hvq_label_pictures' records become
+ * rectangles by an expression on the device, with no synchronisation.  One launch, a lane a rectangle and eight loads, a member of the
+ * export chain.
+ *   rects      a DEVICE pointer, a multiple of 4: int32 [nrects][5] = (i, x0, y0, x1, y1), corners inclusive, i the picture.
+ *   sums, squares   host arrays of n DEVICE pointers as in hvq_integral_pictures; squares or squares[i] NULL: Q comes out 0.
+ *   dims       a DEVICE pointer, a multiple of 4: uint32 [n][2] = (Nx, Ny) of the tables.
+ *   out        a DEVICE pointer, a multiple of 8: uint64 [nrects][3] = (count, S, Q).  A rectangle that leaves its plane, is empty
+ *              (x1 < x0 or y1 < y0), has more than 2^24 samples or names an i outside 0 .. n - 1 gives (0, 0, 0): the call cannot
+ *              check device data on the host.  Every element is written.
+ *   HVQ_E_ARG: n outside 1 .. 65535 or nrects outside 0 .. 2^24 (nrects == 0 is HVQ_OK and does nothing); a null or misaligned
+ *              rects, dims, out or sums[i], a misaligned squares[i]; a NULL context or sums.  HVQ_E_NOGPU after those checks. */
+#define HVQ_RECT_MAX (1 << 24)
+int     hvq_rect_sums(HvqContext *ctx, int n, int nrects, const int32_t *rects, const uint32_t *const *sums, const uint64_t *const *squares,
+                      const uint32_t *dims, uint64_t *out, void *hip_stream);
+
 /* Measurement helper: `reps` copies of `bytes` from pinned host memory to the device on the context's copy stream, HIP-event timed:
  * the PCIe rate the upload of a batch's bitstreams can reach on this box (GB/s, 1e9). */
 int  hvq_h2d_probe(HvqContext *ctx, size_t bytes, int reps, double *gb_per_s);
