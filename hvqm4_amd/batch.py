@@ -222,6 +222,13 @@ class Context:
         return list(out)
 
     @staticmethod
+    def _no_zeros(refs, why):
+        """the references of a call that takes no picture of zeros; why: the call's words for it"""
+        for i, r in enumerate(refs or ()):
+            if r[0] < 0 and r[2] is None:
+                raise ValueError(f"reference {i} is None: {why}")
+
+    @staticmethod
     def _slot_outputs(out, nb, uniform, differ):
         """the pictures in slot layout that a call writes, nb[i] bytes each: one uint8 tensor [n, bytes] when the geometries are one
         (`uniform`), a list of n otherwise; a new one, or the caller's after its checks -> (out, its device, uint64[n] the pictures'
@@ -417,9 +424,7 @@ class Context:
         if ref is None:
             raise ValueError("picture_ssim needs a reference for every picture (SSIM against zeros means nothing)")
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
-        for i, r in enumerate(refs):
-            if r[0] < 0 and r[2] is None:
-                raise ValueError(f"reference {i} is None: SSIM against zeros means nothing")
+        Context._no_zeros(refs, "SSIM against zeros means nothing")
         out = Context._out_tensor(out, (n, 3, 2), torch.int64)
         a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
         views, a_m = None, None
@@ -509,9 +514,7 @@ class Context:
         from .metrics import references
         n = Context._pictures(self._geom, sids, ordinals)
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
-        for i, r in enumerate(refs or ()):
-            if r[0] < 0 and r[2] is None:
-                raise ValueError(f"reference {i} is None: |a - 0| is a itself, ref=None gives its histogram")
+        Context._no_zeros(refs, "|a - 0| is a itself, ref=None gives its histogram")
         ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
         out = Context._out_tensor(out, (n, 3, BINS), torch.int32)
         a_s, a_o, stream = Context._launch_args(out.device, sids, ordinals)
@@ -538,9 +541,7 @@ class Context:
         if ref is None:
             raise ValueError("picture_motion needs a reference for every picture (motion against zeros means nothing)")
         refs = references(ref, n, lambda i: self.pic_bytes(sids[i]))
-        for i, r in enumerate(refs):
-            if r[0] < 0 and r[2] is None:
-                raise ValueError(f"reference {i} is None: motion against zeros means nothing")
+        Context._no_zeros(refs, "motion against zeros means nothing")
         if out is None:
             out = [torch.empty((r, c, 4), dtype=torch.int32, device="cuda") for r, c in dims]
         else:

@@ -2334,8 +2334,8 @@ static int picture_source(HvqContext *c, int i, const int *streams, const int *o
 
 /* Reference i of a call (`r`, NULL when the call has none) against a picture of stream `sid` -> *b: a resident picture of the same
  * geometry (r->stream >= 0, no pointer), the caller's memory (stream -1, a pointer that is a multiple of 16) or nullptr (stream -1, no
- * pointer: zeros).  A call that takes no zeros (`zeros_ok` false) refuses a nullptr itself, in its own words. */
-static int picture_reference(HvqContext *c, int i, int sid, const HvqMetricsRef *r, bool zeros_ok, const uint8_t **b)
+ * pointer: zeros).  A call that takes no zeros says why in `no_zeros` (NULL: zeros are a reference), and they are refused in those words. */
+static int picture_reference(HvqContext *c, int i, int sid, const HvqMetricsRef *r, const char *no_zeros, const uint8_t **b)
 {
     *b = nullptr;
     if (!r) return HVQ_OK;
@@ -2349,27 +2349,14 @@ static int picture_reference(HvqContext *c, int i, int sid, const HvqMetricsRef 
             return fail(HVQ_E_ARG, "reference %d: stream %d (%d x %d, chroma shifts %d, %d) has not the geometry of stream %d (%d x %d, %d, %d)", i,
                         r->stream, t.w, t.h, t.wshift, t.hshift, sid, s.w, s.h, s.wshift, s.hshift);
     } else if (r->stream != -1) {
-        return zeros_ok ? fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory or zeros)", i, r->stream)
-                        : fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory)", i, r->stream);
+        return fail(HVQ_E_ARG, "reference %d: stream %d (a stream, or -1 for the caller's memory%s)", i, r->stream, no_zeros ? "" : " or zeros");
     } else if (r->ptr) {
         if ((uintptr_t)r->ptr & 15u) return fail(HVQ_E_ARG, "reference %d: the pointer must be a multiple of 16", i);
         *b = (const uint8_t *)r->ptr;
+    } else if (no_zeros) {
+        return fail(HVQ_E_ARG, "reference %d: %s (stream -1 needs a pointer)", i, no_zeros);
     }
     return HVQ_OK;
-}
-
-/* Layout of the jobs whose workgroups take `chunk` consecutive 16-byte units of ONE plane (metrics, checksums, histograms): planes of
- * ny, nc, nc bytes one behind the other; wg_first[0] is 0 already (the job was zeroed), wg_first[3] comes out as the picture's workgroups */
-static void plane_layout(size_t ny, size_t nc, uint32_t chunk, uint32_t plane_off[3], uint32_t units[3], uint32_t wg_first[4])
-{
-    const size_t len[3] = { ny, nc, nc };
-    size_t off = 0;
-    for (int p = 0; p < 3; ++p) {
-        plane_off[p] = (uint32_t)off;
-        units[p] = (uint32_t)(len[p] / 16u);
-        wg_first[p + 1] = wg_first[p] + (units[p] + chunk - 1u) / chunk;
-        off += len[p];
-    }
 }
 
 /* The context's own scratch of one kind of call (ck_acc, jp_scr, ph_acc), reused by every such call: the chain orders the calls.  When
@@ -2496,10 +2483,10 @@ static int export_enqueue(HvqContext *c, const void *jobs, size_t bytes, void *h
 /* ---- The frame of the calls that write uint8 pictures in slot layout, Y | U | V ("The slot-layout frame"): scale,
  * filter, warp, compose, rank, map.  Everything here inlines into the entry point's loop: no allocation, no indirect call ---- */
 
-/* "%d pictures": the most one launch's grid takes */
-static int count_check(int n, const char *noun)
+/* "%d pictures": the most one launch's grid takes; `why` is what a record call adds to the text (GRID_ROW) */
+static int count_check(int n, const char *noun, const char *why = "")
 {
-    if (n > 65535) return fail(HVQ_E_ARG, "%d %s: one call takes 65535 at the most", n, noun);
+    if (n > 65535) return fail(HVQ_E_ARG, "%d %s: one call takes 65535 at the most%s", n, noun, why);
     return HVQ_OK;
 }
 
@@ -2554,14 +2541,68 @@ __attribute__((always_inline)) static inline int64_t plane_walk(const SlotShape 
     return plane_walk(s, s, [&](int p, size_t off, size_t, uint32_t nx, uint32_t ny, uint32_t, uint32_t) { return job(p, off, nx, ny); });
 }
 
-/* The tail: `count` pictures of at most `max_tiles` tiles go to `launch` (a weak symbol: null where the kernel's file is not linked)
- * behind the upload of the table */
-typedef hipError_t SlotLaunch(const void *tab_dev, int count, uint32_t max_tiles, hipStream_t stream);
-static int slot_enqueue(HvqContext *c, SlotLaunch *launch, const char *kernel, const char *file, const void *table, size_t bytes, int count,
-                        uint32_t max_tiles, void *hip_stream)
+/* a launch is a weak symbol: null where the kernel's file is not linked.  Refused before anything is allocated or enqueued */
+template <class Launch>
+static int kernel_check(Launch *launch, const char *kernel, const char *file, bool several = false)
 {
-    if (!launch) return fail(HVQ_E_NOGPU, "this build of the library has no %s kernel (%s is not linked)", kernel, file);
-    return export_enqueue(c, table, bytes, hip_stream, [=](const void *t, hipStream_t st) { return launch(t, count, max_tiles, st); });
+    if (!launch) return fail(HVQ_E_NOGPU, "this build of the library has no %s kernel%s (%s is not linked)", kernel, several ? "s" : "", file);
+    return HVQ_OK;
+}
+
+/* The tail: `count` pictures of at most `max_tiles` tiles (or workgroups) go to `launch` behind the upload of the table; a call whose
+ * launch adds into its records has `zero_bytes` at `zero` cleared on the stream in front of it */
+typedef hipError_t SlotLaunch(const void *tab_dev, int count, uint32_t max_tiles, hipStream_t stream);
+static int table_enqueue(HvqContext *c, SlotLaunch *launch, const char *kernel, const char *file, const void *table, size_t bytes, int count,
+                         uint32_t max_tiles, void *hip_stream, void *zero, size_t zero_bytes)
+{
+    { int rc = kernel_check(launch, kernel, file); if (rc) return rc; }
+    return export_enqueue(c, table, bytes, hip_stream, [=](const void *t, hipStream_t st) {
+        if (zero) { hipError_t e = hipMemsetAsync(zero, 0, zero_bytes, st); if (e != hipSuccess) return e; }
+        return launch(t, count, max_tiles, st);
+    });
+}
+
+/* ... of a table of jobs, or of bytes that a call has laid out itself */
+template <class Job>
+static int slot_enqueue(HvqContext *c, SlotLaunch *launch, const char *kernel, const char *file, const std::vector<Job> &table, int count,
+                        uint32_t max_tiles, void *hip_stream, void *zero = nullptr, size_t zero_bytes = 0)
+{
+    static_assert(sizeof(Job) == 1 || sizeof(Job) % 16 == 0, "job tables are uploaded in 16-byte units");
+    return table_enqueue(c, launch, kernel, file, table.data(), table.size() * sizeof(Job), count, max_tiles, hip_stream, zero, zero_bytes);
+}
+
+/* ---- The frame of the calls that read pictures and write records ("The record frame"): metrics, SSIM, checksums,
+ * histograms, motion, JPEG, hashes.  The head is count_check (with GRID_ROW, hashes without) and record_out_check, the loop begins with
+ * picture_source and picture_reference (above), the tail is slot_enqueue where one launch takes (table, count, most workgroups) ---- */
+
+static const char GRID_ROW[] = " (one grid row each)";
+
+/* the records of a call (`out`, `lengths`): the kernels store whole words of `align` bytes */
+static int record_out_check(const char *name, const void *ptr, unsigned align)
+{
+    if (!ptr || ((uintptr_t)ptr & (align - 1u))) return fail(HVQ_E_ARG, "%s must be a non-null multiple of %u", name, align);
+    return HVQ_OK;
+}
+
+/* Picture i (at `a`, of stream `sid`) for a job whose workgroups take `chunk` consecutive 16-byte units of ONE plane (metrics, checksums,
+ * histograms): the planes, of ny, nc, nc bytes one behind the other, must be made of such units, `max_units` of them at the most where
+ * the kernel counts them in fewer bits (0: no limit).  wg_first[0] is 0 already (the job was zeroed) -> the picture's workgroups, which
+ * is wg_first[3], or a negative code.  Always inline, as plane_walk is. */
+__attribute__((always_inline)) static inline int64_t unit_planes(const Stream &s, int i, int sid, const uint8_t *a, uint32_t chunk, uint32_t max_units,
+                                                                 uint32_t plane_off[3], uint32_t units[3], uint32_t wg_first[4])
+{
+    const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
+    if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, sid);
+    if (max_units && ny / 16u > max_units) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, sid, max_units);
+    const size_t len[3] = { ny, nc, nc };
+    size_t off = 0;
+    for (int p = 0; p < 3; ++p) {
+        plane_off[p] = (uint32_t)off;
+        units[p] = (uint32_t)(len[p] / 16u);
+        wg_first[p + 1] = wg_first[p] + (units[p] + chunk - 1u) / chunk;
+        off += len[p];
+    }
+    return wg_first[3];
 }
 
 /* the hvq_*_force_* switches of the tests: -> the state before; `states` 3 where 2 is a state of its own (warp) */
@@ -2612,34 +2653,26 @@ HVQ_EXPORT int hvq_export_pictures(HvqContext *c, int n, const int *streams, con
 HVQ_EXPORT int hvq_picture_metrics(HvqContext *c, int n, const int *streams, const int *ordinals, const HvqMetricsRef *ref,
                                    uint64_t *out, void *hip_stream)
 {
-    static_assert(sizeof(HvqMetricsJob) % 16 == 0, "job tables are uploaded in 16-byte units");
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
-    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    { int rc = record_out_check("out", out, 8); if (rc) return rc; }
     { int rc = chain_begin(c, n, streams, ordinals, nullptr, ref); if (rc) return rc; }
     std::vector<HvqMetricsJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr, *b = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
-        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, true, &b); if (rc) return rc; }
-        const Stream &s = c->streams[(size_t)streams[i]];
-        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
-        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
+        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, nullptr, &b); if (rc) return rc; }
         HvqMetricsJob &j = jobs[(size_t)i];
         memset(&j, 0, sizeof j);
+        const int64_t wgs = unit_planes(c->streams[(size_t)streams[i]], i, streams[i], a, HVQ_MT_CHUNK, 0, j.plane_off, j.units, j.wg_first);
+        if (wgs < 0) return (int)wgs;
         j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 12u);
-        plane_layout(ny, nc, HVQ_MT_CHUNK, j.plane_off, j.units, j.wg_first);
-        max_wgs = std::max(max_wgs, j.wg_first[3]);
+        max_wgs = std::max(max_wgs, (uint32_t)wgs);
     }
-    if (!hvq_launch_metrics) return fail(HVQ_E_NOGPU, "this build of the library has no metrics kernel (hvq_metrics.hip is not linked)");
-    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqMetricsJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) {
-                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 96u, st);       /* the launch adds into the records */
-                              return e != hipSuccess ? e : hvq_launch_metrics(tab, n, max_wgs, st);
-                          });
+    return slot_enqueue(c, hvq_launch_metrics, "metrics", "hvq_metrics.hip", jobs, n, max_wgs, hip_stream, out, (size_t)n * 96u);
 }
 
 /* Windows of SSIM per plane (include/hvqm4_amd.h): host only */
@@ -2664,9 +2697,9 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
                                 int64_t *out, float *const *maps, void *hip_stream)
 {
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
-    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    { int rc = record_out_check("out", out, 8); if (rc) return rc; }
     if (!ref) return fail(HVQ_E_ARG, "SSIM needs a reference for every picture (ref is NULL)");
     for (int i = 0; maps && i < n; ++i)
         if ((uintptr_t)maps[i] & 3u) return fail(HVQ_E_ARG, "map %d: the pointer must be a multiple of 4", i);
@@ -2676,8 +2709,7 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr, *b = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
-        { int rc = picture_reference(c, i, streams[i], ref + i, false, &b); if (rc) return rc; }
-        if (!b) return fail(HVQ_E_ARG, "reference %d: SSIM against a picture of zeros means nothing (stream -1 needs a pointer)", i);
+        { int rc = picture_reference(c, i, streams[i], ref + i, "SSIM against a picture of zeros means nothing", &b); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         const uint32_t cw = (uint32_t)(s.w >> s.wshift), ch = (uint32_t)(s.h >> s.hshift);
         const uint32_t w[3] = { (uint32_t)s.w, cw, cw }, h[3] = { (uint32_t)s.h, ch, ch };
@@ -2699,12 +2731,7 @@ HVQ_EXPORT int hvq_picture_ssim(HvqContext *c, int n, const int *streams, const 
         }
         max_wgs = std::max(max_wgs, j.wg_first[3]);
     }
-    if (!hvq_launch_ssim) return fail(HVQ_E_NOGPU, "this build of the library has no SSIM kernel (hvq_ssim.hip is not linked)");
-    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqSsimJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) {
-                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 48u, st);       /* the launch adds into the records */
-                              return e != hipSuccess ? e : hvq_launch_ssim(tab, n, max_wgs, st);
-                          });
+    return slot_enqueue(c, hvq_launch_ssim, "SSIM", "hvq_ssim.hip", jobs, n, max_wgs, hip_stream, out, (size_t)n * 48u);
 }
 
 /* Checksums of resident pictures (include/hvqm4_amd.h: the specification): a fifth member of the export chain: chain_begin over the
@@ -2715,9 +2742,9 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
                                      uint64_t *out, void *hip_stream)
 {
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
-    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    { int rc = record_out_check("out", out, 8); if (rc) return rc; }
     { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqChecksumJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
@@ -2726,33 +2753,26 @@ HVQ_EXPORT int hvq_picture_checksums(HvqContext *c, int n, const int *streams, c
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
-        const Stream &s = c->streams[(size_t)streams[i]];
-        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
-        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
-        if (ny / 16u > HVQ_CK_MAX_UNITS) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, streams[i], HVQ_CK_MAX_UNITS);
         HvqChecksumJob &j = jobs[(size_t)i];
         memset(&j, 0, sizeof j);
+        const int64_t wgs = unit_planes(c->streams[(size_t)streams[i]], i, streams[i], a, HVQ_CK_CHUNK, HVQ_CK_MAX_UNITS, j.plane_off, j.units, j.wg_first);
+        if (wgs < 0) return (int)wgs;
         j.a = (uint64_t)(uintptr_t)a;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 8u);
-        plane_layout(ny, nc, HVQ_CK_CHUNK, j.plane_off, j.units, j.wg_first);
         for (int p = 0; p < 3; ++p) {
-            const size_t len = p ? nc : ny;
+            const size_t len = (size_t)j.units[p] * 16u;
             const int slot = p != 0;
             if (known_len[slot] != len) { known_len[slot] = len; known_x[slot] = hvq_gf_xpow8(len); }
             j.xlen[p] = known_x[slot];
         }
-        max_wgs = std::max(max_wgs, j.wg_first[3]);
+        max_wgs = std::max(max_wgs, (uint32_t)wgs);
     }
-    if (!hvq_launch_checksums) return fail(HVQ_E_NOGPU, "this build of the library has no checksum kernel (hvq_checksum.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_checksums, "checksum", "hvq_checksum.hip"); if (rc) return rc; }
     const size_t acc_bytes = (size_t)n * 96u;
     { int rc = scratch_grow(c, &c->ck_acc, &c->ck_cap, acc_bytes, 4096); if (rc) return rc; }
     uint8_t *acc = c->ck_acc;
     for (int i = 0; i < n; ++i) jobs[(size_t)i].acc = (uint64_t)(uintptr_t)(acc + (size_t)i * 96u);
-    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqChecksumJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) {
-                              hipError_t e = hipMemsetAsync(acc, 0, acc_bytes, st);             /* the first launch xors and adds into them */
-                              return e != hipSuccess ? e : hvq_launch_checksums(tab, n, max_wgs, st);
-                          });
+    return slot_enqueue(c, hvq_launch_checksums, "checksum", "hvq_checksum.hip", jobs, n, max_wgs, hip_stream, acc, acc_bytes);
 }
 
 /* Histograms of resident pictures (include/hvqm4_amd.h: the specification): a sixth member of the export chain: chain_begin over the
@@ -2765,9 +2785,9 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
     if (mode != HVQ_HIST_VALUES && mode != HVQ_HIST_ABSDIFF) return fail(HVQ_E_ARG, "bad mode %d", mode);
     if (mode == HVQ_HIST_VALUES && ref) return fail(HVQ_E_ARG, "HVQ_HIST_VALUES takes no reference (ref must be NULL)");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
-    if (!out || ((uintptr_t)out & 3u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 4");
+    { int rc = record_out_check("out", out, 4); if (rc) return rc; }
     if (mode == HVQ_HIST_ABSDIFF && !ref) return fail(HVQ_E_ARG, "HVQ_HIST_ABSDIFF needs a reference for every picture (ref is NULL)");
     { int rc = chain_begin(c, n, streams, ordinals, src, ref); if (rc) return rc; }
     std::vector<HvqHistogramJob> jobs((size_t)n);
@@ -2775,25 +2795,17 @@ HVQ_EXPORT int hvq_picture_histograms(HvqContext *c, int n, const int *streams, 
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr, *b = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
-        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, false, &b); if (rc) return rc; }
-        if (ref && !b) return fail(HVQ_E_ARG, "reference %d: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)", i);
-        const Stream &s = c->streams[(size_t)streams[i]];
-        const size_t ny = (size_t)s.w * s.h, nc = (size_t)(s.w >> s.wshift) * (size_t)(s.h >> s.hshift);
-        if (((uintptr_t)a | ny | nc) & 15u) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d is not made of 16-byte units", i, streams[i]);
-        if (ny / 16u > HVQ_HG_MAX_UNITS) return fail(HVQ_E_ARG, "picture %d: a plane of stream %d has more than %u 16-byte units", i, streams[i], HVQ_HG_MAX_UNITS);
+        /* no reference (HVQ_HIST_VALUES) is none to refuse; a given one of zeros is */
+        { int rc = picture_reference(c, i, streams[i], ref ? ref + i : nullptr, "|a - 0| is a itself, HVQ_HIST_VALUES gives it", &b); if (rc) return rc; }
         HvqHistogramJob &j = jobs[(size_t)i];
         memset(&j, 0, sizeof j);
+        const int64_t wgs = unit_planes(c->streams[(size_t)streams[i]], i, streams[i], a, HVQ_HG_CHUNK, HVQ_HG_MAX_UNITS, j.plane_off, j.units, j.wg_first);
+        if (wgs < 0) return (int)wgs;
         j.a = (uint64_t)(uintptr_t)a; j.b = (uint64_t)(uintptr_t)b;
         j.out = (uint64_t)(uintptr_t)(out + (size_t)i * 3u * HVQ_HIST_BINS);
-        plane_layout(ny, nc, HVQ_HG_CHUNK, j.plane_off, j.units, j.wg_first);
-        max_wgs = std::max(max_wgs, j.wg_first[3]);
+        max_wgs = std::max(max_wgs, (uint32_t)wgs);
     }
-    if (!hvq_launch_histograms) return fail(HVQ_E_NOGPU, "this build of the library has no histogram kernel (hvq_histogram.hip is not linked)");
-    return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqHistogramJob), hip_stream,
-                          [=](const void *tab, hipStream_t st) {
-                              hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 3u * HVQ_HIST_BINS * sizeof(uint32_t), st);   /* the launch adds into the records */
-                              return e != hipSuccess ? e : hvq_launch_histograms(tab, n, max_wgs, st);
-                          });
+    return slot_enqueue(c, hvq_launch_histograms, "histogram", "hvq_histogram.hip", jobs, n, max_wgs, hip_stream, out, (size_t)n * 3u * HVQ_HIST_BINS * sizeof(uint32_t));
 }
 
 /* Blocks of a motion field (include/hvqm4_amd.h): host only */
@@ -2816,20 +2828,18 @@ HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, cons
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
     if (block != 8 && block != 16) return fail(HVQ_E_ARG, "block %d (8 or 16)", block);
     if (radius < 0 || radius > HVQ_MOTION_MAX_RADIUS) return fail(HVQ_E_ARG, "radius %d outside [0, %d]", radius, HVQ_MOTION_MAX_RADIUS);
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (!out) return fail(HVQ_E_ARG, "out is NULL");
     if (!ref) return fail(HVQ_E_ARG, "motion needs a reference for every picture (ref is NULL)");
-    for (int i = 0; i < n; ++i)
-        if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "field %d: the pointer must be a non-null multiple of 16", i);
+    for (int i = 0; i < n; ++i) { int rc = slot_pointer_check("field", i, out[i]); if (rc) return rc; }
     { int rc = chain_begin(c, n, streams, ordinals, nullptr, ref); if (rc) return rc; }
     std::vector<HvqMotionJob> jobs((size_t)n);
     uint32_t max_tiles = 0;
     for (int i = 0; i < n; ++i) {
         const uint8_t *a = nullptr, *b = nullptr;
         { int rc = picture_source(c, i, streams, ordinals, nullptr, &a); if (rc) return rc; }
-        { int rc = picture_reference(c, i, streams[i], ref + i, false, &b); if (rc) return rc; }
-        if (!b) return fail(HVQ_E_ARG, "reference %d: motion against a picture of zeros means nothing (stream -1 needs a pointer)", i);
+        { int rc = picture_reference(c, i, streams[i], ref + i, "motion against a picture of zeros means nothing", &b); if (rc) return rc; }
         const Stream &s = c->streams[(size_t)streams[i]];
         if (s.w % block || s.h % block) return fail(HVQ_E_ARG, "picture %d: blocks of %d do not tile stream %d (%d x %d)", i, block, streams[i], s.w, s.h);
         if ((uintptr_t)a & 15u || s.w >= (int)HVQ_MV_MAX_SIDE || s.h >= (int)HVQ_MV_MAX_SIDE)
@@ -2844,7 +2854,7 @@ HVQ_EXPORT int hvq_picture_motion(HvqContext *c, int n, const int *streams, cons
         j.tiles = j.tiles_x * ((j.h + HVQ_MV_TILE - 1u) / HVQ_MV_TILE);
         max_tiles = std::max(max_tiles, j.tiles);
     }
-    if (!hvq_launch_motion) return fail(HVQ_E_NOGPU, "this build of the library has no motion kernel (hvq_motion.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_motion, "motion", "hvq_motion.hip"); if (rc) return rc; }
     return export_enqueue(c, jobs.data(), (size_t)n * sizeof(HvqMotionJob), hip_stream,
                           [=](const void *tab, hipStream_t st) { return hvq_launch_motion(tab, n, max_tiles, block, radius, st); });
 }
@@ -2887,12 +2897,12 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
     static_assert(HVQ_JPEG_HEADER == HVQ_JPEG_HEADER_BYTES, "the kernel's header length is the header's");
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
     if (quality < 1 || quality > 100) return fail(HVQ_E_ARG, "quality %d outside [1, 100]", quality);
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most (one grid row each)", n);
+    { int rc = count_check(n, "pictures", GRID_ROW); if (rc) return rc; }
     if (!n) return HVQ_OK;
     if (!out || !cap) return fail(HVQ_E_ARG, "out or cap is NULL");
-    if (!lengths || ((uintptr_t)lengths & 7u)) return fail(HVQ_E_ARG, "lengths must be a non-null multiple of 8");
+    { int rc = record_out_check("lengths", lengths, 8); if (rc) return rc; }
     for (int i = 0; i < n; ++i) {
-        if (!out[i] || ((uintptr_t)out[i] & 15u)) return fail(HVQ_E_ARG, "file %d: the pointer must be a non-null multiple of 16", i);
+        { int rc = slot_pointer_check("file", i, out[i]); if (rc) return rc; }
         if (cap[i] < HVQ_JPEG_HEADER_BYTES + 2u) return fail(HVQ_E_ARG, "file %d: %llu bytes hold not even the header and EOI (%u)", i, (unsigned long long)cap[i], HVQ_JPEG_HEADER_BYTES + 2u);
     }
     { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
@@ -2932,7 +2942,7 @@ HVQ_EXPORT int hvq_encode_jpeg(HvqContext *c, int n, const int *streams, const i
     for (int t = 0; t < 2; ++t)
         for (int k = 0; k < 64; ++k) qt.q[t][k] = hvq_jpeg_qpack(hvq_jpeg_q(HVQ_JPEG_QBASE[t][k], quality));
     memcpy(table.data() + quant_off, &qt, sizeof qt);
-    if (!hvq_launch_jpeg) return fail(HVQ_E_NOGPU, "this build of the library has no JPEG kernels (hvq_jpeg.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_jpeg, "JPEG", "hvq_jpeg.hip", true); if (rc) return rc; }
     { int rc = scratch_grow(c, &c->jp_scr, &c->jp_cap, scr_dwords, 1024); if (rc) return rc; }
     uint32_t *scr = c->jp_scr;
     return export_enqueue(c, table.data(), table.size(), hip_stream,
@@ -2950,9 +2960,9 @@ HVQ_EXPORT int hvq_picture_hashes(HvqContext *c, int n, const int *streams, cons
                                   uint64_t *out, void *hip_stream)
 {
     if (!c || n < 0 || (n && (!streams || !ordinals))) return fail(HVQ_E_ARG, "bad arguments");
-    if (n > 65535) return fail(HVQ_E_ARG, "%d pictures: one call takes 65535 at the most", n);
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
     if (!n) return HVQ_OK;
-    if (!out || ((uintptr_t)out & 7u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 8");
+    { int rc = record_out_check("out", out, 8); if (rc) return rc; }
     { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
     std::vector<HvqHashJob> jobs((size_t)n);
     uint32_t max_wgs = 0;
@@ -2977,7 +2987,7 @@ HVQ_EXPORT int hvq_picture_hashes(HvqContext *c, int n, const int *streams, cons
         j.wgs = HVQ_PH_ROWS / j.cells_pw * ((j.units + HVQ_PH_LANES - 1u) / HVQ_PH_LANES);
         max_wgs = std::max(max_wgs, j.wgs);
     }
-    if (!hvq_launch_hashes) return fail(HVQ_E_NOGPU, "this build of the library has no hash kernels (hvq_phash.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_hashes, "hash", "hvq_phash.hip", true); if (rc) return rc; }
     const size_t cell_bytes = (size_t)HVQ_PH_CELLS * 8u;
     const size_t acc_bytes = (size_t)std::min(n, (int)HVQ_PH_BATCH) * cell_bytes;
     { int rc = scratch_grow(c, &c->ph_acc, &c->ph_cap, acc_bytes, 4096, align_up((size_t)HVQ_PH_BATCH * cell_bytes, 4096)); if (rc) return rc; }
@@ -3010,7 +3020,7 @@ HVQ_EXPORT int hvq_hash_nearest(HvqContext *c, const uint64_t *q, int nq, int q_
     if (!q || ((uintptr_t)q & 7u)) return fail(HVQ_E_ARG, "q must be a non-null multiple of 8");
     if (ndb && (!db || ((uintptr_t)db & 7u))) return fail(HVQ_E_ARG, "db must be a non-null multiple of 8");
     if (!out || ((uintptr_t)out & 15u)) return fail(HVQ_E_ARG, "out must be a non-null multiple of 16");
-    if (!hvq_launch_hash_nearest) return fail(HVQ_E_NOGPU, "this build of the library has no hash kernels (hvq_phash.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_hash_nearest, "hash", "hvq_phash.hip", true); if (rc) return rc; }
     HIPCHK(hipSetDevice(c->device));
     /* an offset that admits every candidate for every query is "all" */
     const int64_t off = self_offset < 0 || self_offset >= (int64_t)ndb ? -1 : self_offset;
@@ -3090,7 +3100,7 @@ HVQ_EXPORT int hvq_scale_pictures(HvqContext *c, int n, const int *streams, cons
         if (tiles < 0) return (int)tiles;
         max_tiles = std::max(max_tiles, (uint32_t)tiles);
     }
-    return slot_enqueue(c, hvq_launch_scale, "scale", "hvq_scale.hip", jobs.data(), jobs.size() * sizeof(HvqScaleJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_scale, "scale", "hvq_scale.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Filtered copies of resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):
@@ -3180,7 +3190,7 @@ HVQ_EXPORT int hvq_filter_pictures(HvqContext *c, int n, const int *streams, con
             return j.tiles;
         }));
     }
-    return slot_enqueue(c, hvq_launch_filter, "filter", "hvq_filter.hip", up.data(), up.size(), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_filter, "filter", "hvq_filter.hip", up, n, max_tiles, hip_stream);
 }
 
 /* Rank filters on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame") */
@@ -3231,7 +3241,7 @@ HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const
             return j.tiles;
         }));
     }
-    return slot_enqueue(c, hvq_launch_rank, "rank", "hvq_rank.hip", jobs.data(), jobs.size() * sizeof(HvqRankJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_rank, "rank", "hvq_rank.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Lookup tables on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):
@@ -3265,7 +3275,7 @@ HVQ_EXPORT int hvq_map_pictures(HvqContext *c, int n, const int *streams, const 
             return j.tiles;
         }));
     }
-    return slot_enqueue(c, hvq_launch_map, "map", "hvq_map.hip", jobs.data(), jobs.size() * sizeof(HvqMapJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_map, "map", "hvq_map.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Connected components of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Labels").  The launches of a call
@@ -3321,7 +3331,7 @@ HVQ_EXPORT int hvq_label_pictures(HvqContext *c, int n, const int *streams, cons
         max_seams = std::max(max_seams, j.seams);
         max_chunks = std::max(max_chunks, j.chunks);
     }
-    if (!hvq_launch_label) return fail(HVQ_E_NOGPU, "this build of the library has no label kernels (hvq_label.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_label, "label", "hvq_label.hip", true); if (rc) return rc; }
     return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqLabelJob), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_label(t, n, max_tiles, max_seams, max_chunks, st); });
 }
@@ -3361,7 +3371,7 @@ HVQ_EXPORT int hvq_select_components(HvqContext *c, int n, const int *streams, c
         }));
     }
     HIPCHK(hipSetDevice(c->device));
-    return slot_enqueue(c, hvq_launch_select, "select", "hvq_label.hip", jobs.data(), jobs.size() * sizeof(HvqSelectJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_select, "select", "hvq_label.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Exact distance transforms of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Distances").  The two launches
@@ -3414,7 +3424,7 @@ HVQ_EXPORT int hvq_distance_pictures(HvqContext *c, int n, const int *streams, c
         max_cols = std::max(max_cols, j.colgroups);
         max_rows = std::max(max_rows, j.rowgroups);
     }
-    if (!hvq_launch_distance) return fail(HVQ_E_NOGPU, "this build of the library has no distance kernels (hvq_distance.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_distance, "distance", "hvq_distance.hip", true); if (rc) return rc; }
     return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqDistanceJob), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_distance(t, n, max_cols, max_rows, st); });
 }
@@ -3458,7 +3468,7 @@ HVQ_EXPORT int hvq_distance_mask(HvqContext *c, int n, const int *streams, const
         }));
     }
     HIPCHK(hipSetDevice(c->device));
-    return slot_enqueue(c, hvq_launch_distance_mask, "distance mask", "hvq_distance.hip", jobs.data(), jobs.size() * sizeof(HvqDistMaskJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_distance_mask, "distance mask", "hvq_distance.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Summed-area tables of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Integrals").  The two launches of a
@@ -3496,7 +3506,7 @@ HVQ_EXPORT int hvq_integral_pictures(HvqContext *c, int n, const int *streams, c
         max_rows = std::max(max_rows, j.rowgroups);
         max_cols = std::max(max_cols, j.colgroups);
     }
-    if (!hvq_launch_integral) return fail(HVQ_E_NOGPU, "this build of the library has no integral kernels (hvq_integral.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_integral, "integral", "hvq_integral.hip", true); if (rc) return rc; }
     return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqIntegralJob), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_integral(t, n, max_rows, max_cols, st); });
 }
@@ -3557,7 +3567,7 @@ HVQ_EXPORT int hvq_window_pictures(HvqContext *c, int n, const int *streams, con
                        (uint32_t)rule.mode, (uint32_t)rule.rx, (uint32_t)rule.ry, rule.k, rule.c, (uint32_t)rule.invert);
         max_tiles = std::max(max_tiles, j.tiles);
     }
-    return slot_enqueue(c, hvq_launch_window, "window", "hvq_integral.hip", jobs.data(), jobs.size() * sizeof(HvqWindowJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_window, "window", "hvq_integral.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Sums of rectangles that lie in device memory.  No picture is looked up; ONE head and a pair of tables a picture go up as the job table */
@@ -3582,7 +3592,7 @@ HVQ_EXPORT int hvq_rect_sums(HvqContext *c, int n, int nrects, const int32_t *re
         tab[(size_t)i + 2u] = HvqRectTables{ (uint64_t)(uintptr_t)sums[i], (uint64_t)(uintptr_t)q };
     }
     HIPCHK(hipSetDevice(c->device));
-    return slot_enqueue(c, hvq_launch_rects, "rectangle", "hvq_integral.hip", tab.data(), tab.size() * sizeof(HvqRectTables), n, (uint32_t)nrects, hip_stream);
+    return slot_enqueue(c, hvq_launch_rects, "rectangle", "hvq_integral.hip", tab, n, (uint32_t)nrects, hip_stream);
 }
 
 /* Tables from histogram records (include/hvqm4_amd.h: the specification).  No picture is looked up; the launch goes behind its job
@@ -3629,7 +3639,7 @@ HVQ_EXPORT int hvq_histogram_tables(HvqContext *c, int n, const uint32_t *hist, 
         const HvqTablePlane *pl[2] = { &rules[r].luma, &rules[r].chroma };
         for (int k = 0; k < 2; ++k) { j.rule[k].kind = (uint32_t)pl[k]->kind; j.rule[k].a = (uint32_t)pl[k]->a; j.rule[k].b = (uint32_t)pl[k]->b; j.rule[k].pad = 0; }
     }
-    if (!hvq_launch_tables) return fail(HVQ_E_NOGPU, "this build of the library has no table kernel (hvq_map.hip is not linked)");
+    { int rc = kernel_check(hvq_launch_tables, "table", "hvq_map.hip"); if (rc) return rc; }
     HIPCHK(hipSetDevice(c->device));
     return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqTableJob), hip_stream,
                           [=](const void *t, hipStream_t st) { return hvq_launch_tables(t, n, st); });
@@ -3690,7 +3700,7 @@ HVQ_EXPORT int hvq_warp_pictures(HvqContext *c, int n, const int *streams, const
             return j.tiles;
         }));
     }
-    return slot_enqueue(c, hvq_launch_warp, "warp", "hvq_warp.hip", jobs.data(), jobs.size() * sizeof(HvqWarpJob), n, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_warp, "warp", "hvq_warp.hip", jobs, n, max_tiles, hip_stream);
 }
 
 /* Pictures composed of layers of resident pictures, in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The
@@ -3776,7 +3786,7 @@ HVQ_EXPORT int hvq_compose_pictures(HvqContext *c, int nlayers, const int *strea
             return j.tiles;
         }));
     }
-    return slot_enqueue(c, hvq_launch_compose, "compose", "hvq_compose.hip", up.data(), up.size(), ntargets, max_tiles, hip_stream);
+    return slot_enqueue(c, hvq_launch_compose, "compose", "hvq_compose.hip", up, ntargets, max_tiles, hip_stream);
 }
 
 /* zlib's crc32_combine and adler32_combine (include/hvqm4_amd.h): host only */

@@ -10,11 +10,12 @@
  *   C <label> <clip> <ordinal> <form> <8 numbers>     one record read back: crc32 Y, U, V, picture, adler32 Y, U, V, picture
  *       form: pic (the resident picture), inv (the caller's memory: the picture with every byte inverted, 255 - x)
  *   R <label> <return code>                           a return code the test wants to see
+ *   E <label> <text>                                  the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>     an output buffer after refused calls
  * Caller-side resources (a stream, output records, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_checksums_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 
 /* one picture of a call and what the test is told about it */
 struct Item { int sid, k; const void *src; std::string clip, form; int kk; };
@@ -24,15 +25,7 @@ static Item resident(int sid, const Clip &c, int k) { return Item{ sid, k, nullp
 /* the caller's memory: picture k of stream sid read back, every byte inverted, in device memory at `offset` bytes into an allocation */
 static Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, size_t offset, std::vector<void *> *keep)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ sid, -1, (uint8_t *)d + offset, c.name, "inv", k };
+    return Item{ sid, -1, uploaded(inverted(ctx, sid, k), offset, keep), c.name, "inv", k };
 }
 
 struct Call { uint64_t *out; std::vector<Item> items; std::string label; };
@@ -44,10 +37,7 @@ static Call call_checksums(HvqContext *ctx, const std::vector<Item> &items, bool
     std::vector<int> sids, ords;
     std::vector<const void *> src;
     for (const Item &p : items) { sids.push_back(p.sid); ords.push_back(p.k); src.push_back(p.src); }
-    void *out = nullptr;
-    HIP(hipMalloc(&out, (size_t)n * 64u));
-    std::vector<uint8_t> ff((size_t)n * 64u, 0xFF);
-    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    void *out = record_room((size_t)n * 64u);
     CHECK(hvq_picture_checksums(ctx, n, sids.data(), ords.data(), null_src ? nullptr : src.data(), (uint64_t *)out, caller));
     return Call{ (uint64_t *)out, items, label };
 }
@@ -55,27 +45,21 @@ static Call call_checksums(HvqContext *ctx, const std::vector<Item> &items, bool
 /* after the caller's stream has been waited for */
 static void write_call(Call *c)
 {
-    std::vector<uint64_t> host(c->items.size() * 8u);
-    HIP(hipMemcpy(host.data(), c->out, host.size() * 8u, hipMemcpyDeviceToHost));
+    const std::vector<uint64_t> host = take_records(&c->out, c->items.size() * 8u);
     for (size_t i = 0; i < c->items.size(); ++i) {
         const Item &p = c->items[i];
         fprintf(g_res, "C %s %s %d %s", c->label.c_str(), p.clip.c_str(), p.kk, p.form.c_str());
         for (int v = 0; v < 8; ++v) fprintf(g_res, " %llu", (unsigned long long)host[i * 8u + (size_t)v]);
         fprintf(g_res, "\n");
     }
-    HIP(hipFree(c->out));
-    c->out = nullptr;
 }
 
 static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8" };
 
 /* six clips of three samplings in one context: per clip one call over its pictures (src = NULL), then one call over all clips with the
  * pictures interleaved, a call of one picture, and n == 0 */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     for (const char *nm : SIX) {
@@ -95,17 +79,12 @@ static void scenario_goldens()
     HIP(hipStreamSynchronize(caller));
     for (Call &c : calls) write_call(&c);
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* pictures in the caller's memory, at the start of an allocation and 16 bytes into one, mixed with resident ones; on the caller's stream
  * and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     std::vector<void *> keep;
@@ -123,17 +102,12 @@ static void scenario_memory()
     write_call(&c);
     write_call(&d);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the records are those of the pictures as they were */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -157,21 +131,17 @@ static void scenario_reuse()
     d.items = late;
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(resident(se, e, k));
     Call f = call_checksums(ctx, other, false, caller, "reuse/destroy");
-    hvq_context_destroy(ctx);
+    hvq_context_destroy(ctx); ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* two calls back to back on one stream, nothing waited for in between: they share the context's accumulators.  A small call, then a
  * larger one (the accumulators grow with the first still queued), then the small one again */
-static void scenario_backtoback()
+static void scenario_backtoback(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("wide296x160"), &b = clip("gop64x48_15");
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     std::vector<Item> small, large;
@@ -189,16 +159,11 @@ static void scenario_backtoback()
     write_call(&d);
     write_call(&e);
     write_call(&f);
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into one sentinel-filled buffer that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a;
     const int sa = decode(ctx, a);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -210,15 +175,12 @@ static void scenario_refused()
     CHECK(hvq_stream_submit(ctx, sa, a.pics[0].type, a.pics[0].p, a.pics[0].len));      /* queued, not flushed: ordinal n of sa */
     const int queued = (int)a.pics.size();
 
-    const size_t bytes = 2u * 64u;
-    void *out = nullptr, *mem = nullptr;
-    HIP(hipMalloc(&out, bytes + 8u));
+    Sentinels sent;
+    void *out = sent.room(2u * 64u + 8u), *mem = nullptr;
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    std::vector<uint8_t> sent(bytes + 8u, 0xA5);
-    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
     uint64_t *o = (uint64_t *)out;
     auto refuse = [&](const char *label, HvqContext *cx, int n, std::vector<int> sids, std::vector<int> ords, std::vector<const void *> src, uint64_t *dst) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_checksums(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), dst, caller));
+        write_code("refused", label, hvq_picture_checksums(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), dst, caller));
     };
     refuse("null_context", nullptr, 2, { sa, sa }, { 0, 1 }, {}, o);
     refuse("bad_stream", ctx, 2, { sa, 99 }, { 0, 0 }, {}, o);
@@ -232,38 +194,19 @@ static void scenario_refused()
     refuse("too_many", ctx, 65536, { sa }, { 0 }, {}, o);
     refuse("evicted", ctx, 2, { sd, sd }, { last, 0 }, {}, o);
     refuse("queued", ctx, 2, { sa, sa }, { 0, queued }, {}, o);
-    fprintf(g_res, "R refused/n0 %d\n", hvq_picture_checksums(ctx, 0, nullptr, nullptr, nullptr, nullptr, caller));
+    write_code("refused", "n0", hvq_picture_checksums(ctx, 0, nullptr, nullptr, nullptr, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
-    std::vector<uint8_t> back(sent.size());
-    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
-    size_t same = 0;
-    for (uint8_t x : back) same += x == 0xA5;
-    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    sent.write("refused");
     /* the well-formed call right after them works */
     CHECK(hvq_flush(ctx));
     Call c = call_checksums(ctx, { resident(sa, a, 1), resident(sd, d, last) }, false, caller, "refused/then_ok");
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
-    HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_checksums_driver <scenario> <outdir> <golden dir>\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_checksums_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "backtoback") scenario_backtoback();
-    else if (sc == "refused") scenario_refused();
-    else { fprintf(stderr, "fake_checksums_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "memory", scenario_memory }, { "reuse", scenario_reuse },
+                                     { "backtoback", scenario_backtoback }, { "refused", scenario_refused } });
 }

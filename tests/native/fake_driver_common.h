@@ -1,13 +1,15 @@
 /*
  * tests/native/fake_driver_common.h -- TEST INFRASTRUCTURE: what the stand-alone fake-device drivers (fake_driver.cpp and the
  * fake_*_driver.cpp of the export-chain calls) have in common: the clips of the golden directory with their pictures, a stream that
- * holds a decoded clip, the caller's stream, CRC-32, and the two macros that end the program when a call of the library or of the fake
- * HIP fails.  Only what is the same in every driver is here; a driver says who it is before it includes the header:
+ * holds a decoded clip, the caller's stream, CRC-32, the two macros that end the program when a call of the library or of the fake
+ * HIP fails, a picture read back (as it is, or inverted) and uploaded as the caller's memory, the frame of a scenario (run_scenario)
+ * and the frame of the program (driver_main).  Only what is the same in every driver is here; fake_slot_driver.h and
+ * fake_record_driver.h add what the drivers of one family of calls share.  A driver says who it is before it includes a header:
  *
  *   #define DRIVER_NAME "fake_metrics_driver"
- *   #include "fake_driver_common.h"
+ *   #include "fake_record_driver.h"
  *
- * and sets g_golden, g_out and g_res from its arguments in main.
+ * and either hands its scenarios to driver_main or sets g_golden, g_out and g_res from its arguments in a main of its own.
  */
 #ifndef FAKE_DRIVER_COMMON_H
 #define FAKE_DRIVER_COMMON_H
@@ -21,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -36,6 +39,7 @@ struct Clip {
 };
 
 static std::string g_golden, g_out;
+static std::vector<std::string> g_extra;             /* what follows the golden directory on the command line (driver_main) */
 static FILE *g_res;
 static std::map<std::string, Clip> g_clips;
 
@@ -96,6 +100,66 @@ static inline uint32_t crc32_of(const uint8_t *p, size_t n)
         for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
     }
     return ~c;
+}
+
+/* picture k of stream sid read back */
+static inline std::vector<uint8_t> read_back(HvqContext *ctx, int sid, int k)
+{
+    std::vector<uint8_t> host(hvq_stream_pic_bytes(ctx, sid));
+    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
+    return host;
+}
+
+/* ... with every byte inverted */
+static inline std::vector<uint8_t> inverted(HvqContext *ctx, int sid, int k)
+{
+    std::vector<uint8_t> host = read_back(ctx, sid, k);
+    for (uint8_t &x : host) x = (uint8_t)(255 - x);
+    return host;
+}
+
+/* the caller's memory: `host` in device memory, `offset` bytes into an allocation of its own, which `keep` gets -> where the bytes lie */
+static inline void *uploaded(const std::vector<uint8_t> &host, size_t offset, std::vector<void *> *keep)
+{
+    void *d = nullptr;
+    HIP(hipMalloc(&d, host.size() + offset));
+    keep->push_back(d);
+    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), host.size(), hipMemcpyHostToDevice));
+    return (uint8_t *)d + offset;
+}
+
+/* The frame of a scenario: a context and the caller's stream around `body`, destroyed in that order.  A body that destroys the context
+ * itself, with work still queued, sets `ctx` to null. */
+static inline void run_scenario(void (*body)(HvqContext *&ctx, hipStream_t caller))
+{
+    HvqContext *ctx = nullptr;
+    CHECK(hvq_context_create(0, &ctx));
+    hipStream_t caller = caller_stream();
+    body(ctx, caller);
+    if (ctx) hvq_context_destroy(ctx);
+    HIP(hipStreamDestroy(caller));
+}
+
+/* The frame of the program: <scenario> <outdir> <golden dir> and whatever `more` names (it lands in g_extra); the scenario's body runs
+ * inside run_scenario, a `plain` one (host only) as it is; then everything the fake device still holds is drained. */
+struct Scenario { const char *name; void (*body)(HvqContext *&ctx, hipStream_t caller); void (*plain)() = nullptr; };
+
+static inline int driver_main(int argc, char **argv, std::initializer_list<Scenario> scenarios, const char *more = "")
+{
+    if (argc < 4) { fprintf(stderr, "usage: " DRIVER_NAME " <scenario> <outdir> <golden dir>%s\n", more); return 2; }
+    g_out = argv[2]; g_golden = argv[3];
+    g_extra.assign(argv + 4, argv + argc);
+    const Scenario *sc = nullptr;
+    for (const Scenario &s : scenarios)
+        if (!strcmp(s.name, argv[1])) sc = &s;
+    if (!sc) { fprintf(stderr, DRIVER_NAME ": unknown scenario %s\n", argv[1]); return 2; }
+    g_res = fopen((g_out + "/results.txt").c_str(), "w");
+    if (!g_res) { fprintf(stderr, DRIVER_NAME ": cannot write into %s\n", g_out.c_str()); return 2; }
+    if (sc->body) run_scenario(sc->body);
+    else sc->plain();
+    fake_drain_all();
+    fclose(g_res);
+    return 0;
 }
 
 #endif

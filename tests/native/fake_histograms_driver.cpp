@@ -11,11 +11,12 @@
  *       a form: pic (the resident picture), inv (the caller's memory: the picture with every byte inverted, 255 - x)
  *       b form: none (HVQ_HIST_VALUES), pic (a resident reference), inv (a reference in the caller's memory, inverted)
  *   R <label> <return code>                           a return code the test wants to see
+ *   E <label> <text>                                  the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>     an output buffer after refused calls
  * Caller-side resources (a stream, output records, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_histograms_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 
 static const size_t REC = 3u * HVQ_HIST_BINS;           /* dwords of a record */
 
@@ -29,15 +30,7 @@ static Side none() { return Side{ -1, 0, nullptr, "none", 0 }; }
 /* the caller's memory: picture k of stream sid read back, every byte inverted, in device memory at `offset` bytes into an allocation */
 static Side in_memory(HvqContext *ctx, int sid, int k, size_t offset, std::vector<void *> *keep)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Side{ sid, -1, (uint8_t *)d + offset, "inv", k };
+    return Side{ sid, -1, uploaded(inverted(ctx, sid, k), offset, keep), "inv", k };
 }
 
 struct Call { uint32_t *out; std::vector<Item> items; std::string label; };
@@ -55,10 +48,7 @@ static Call call_histograms(HvqContext *ctx, const std::vector<Item> &items, boo
         sids.push_back(p.a.sid); ords.push_back(p.a.k); src.push_back(p.a.mem);
         ref.push_back(p.b.mem ? HvqMetricsRef{ -1, 0, p.b.mem } : HvqMetricsRef{ p.b.sid, p.b.k, nullptr });
     }
-    void *out = nullptr;
-    HIP(hipMalloc(&out, (size_t)n * REC * 4u));
-    std::vector<uint8_t> ff((size_t)n * REC * 4u, 0xFF);
-    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    void *out = record_room((size_t)n * REC * 4u);
     CHECK(hvq_picture_histograms(ctx, n, sids.data(), ords.data(), null_src ? nullptr : src.data(), values ? HVQ_HIST_VALUES : HVQ_HIST_ABSDIFF,
                                  values ? nullptr : ref.data(), (uint32_t *)out, caller));
     return Call{ (uint32_t *)out, items, label };
@@ -67,27 +57,21 @@ static Call call_histograms(HvqContext *ctx, const std::vector<Item> &items, boo
 /* after the caller's stream has been waited for */
 static void write_call(Call *c)
 {
-    std::vector<uint32_t> host(c->items.size() * REC);
-    HIP(hipMemcpy(host.data(), c->out, host.size() * 4u, hipMemcpyDeviceToHost));
+    const std::vector<uint32_t> host = take_records(&c->out, c->items.size() * REC);
     for (size_t i = 0; i < c->items.size(); ++i) {
         const Item &p = c->items[i];
         fprintf(g_res, "H %s %s %s %d %s %d", c->label.c_str(), p.clip.c_str(), p.a.form, p.a.kk, p.b.form, p.b.kk);
         for (size_t v = 0; v < REC; ++v) fprintf(g_res, " %u", host[i * REC + v]);
         fprintf(g_res, "\n");
     }
-    HIP(hipFree(c->out));
-    c->out = nullptr;
 }
 
 static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8" };
 
 /* six clips of three samplings in one context: per clip its pictures' values (src = NULL), every picture against its predecessor and
  * against itself; then one call over all clips with the pictures interleaved, a call of one picture, and n == 0 */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     for (const char *nm : SIX) {
@@ -114,17 +98,12 @@ static void scenario_goldens()
     HIP(hipStreamSynchronize(caller));
     for (Call &c : calls) write_call(&c);
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* the caller's memory as a and as b, at the start of an allocation and 16 bytes into one, mixed with resident pictures and with a
  * reference of another stream of the same geometry; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sb = decode(ctx, b), sa2 = decode(ctx, a);
     const int na = (int)a.pics.size();
@@ -148,17 +127,12 @@ static void scenario_memory()
     write_call(&d);
     write_call(&e);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* calls queued on the caller's stream, then flushes that hand the slots of their pictures to later ones, nothing waited for in between:
  * the records are those of the pictures as they were */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -187,21 +161,17 @@ static void scenario_reuse()
     d.items = late;
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(Item{ e.name, resident(se, k), none() });
     Call f = call_histograms(ctx, other, false, caller, "reuse/destroy");
-    hvq_context_destroy(ctx);
+    hvq_context_destroy(ctx); ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&c2);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into one sentinel-filled buffer that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a, &g = clip("yuv422_64x48");
     const int sa = decode(ctx, a), sg = decode(ctx, g);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -213,18 +183,15 @@ static void scenario_refused()
     CHECK(hvq_stream_submit(ctx, sa, a.pics[0].type, a.pics[0].p, a.pics[0].len));      /* queued, not flushed: ordinal n of sa */
     const int queued = (int)a.pics.size();
 
-    const size_t bytes = 2u * REC * 4u;
-    void *out = nullptr, *mem = nullptr;
-    HIP(hipMalloc(&out, bytes + 8u));
+    Sentinels sent;
+    void *out = sent.room(2u * REC * 4u + 8u), *mem = nullptr;
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    std::vector<uint8_t> sent(bytes + 8u, 0xA5);
-    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
     uint32_t *o = (uint32_t *)out;
     const int V = HVQ_HIST_VALUES, D = HVQ_HIST_ABSDIFF;
     typedef std::vector<HvqMetricsRef> Refs;
     auto refuse = [&](const char *label, HvqContext *cx, int n, std::vector<int> sids, std::vector<int> ords, std::vector<const void *> src, int mode,
                       Refs ref, uint32_t *dst) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_histograms(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), mode,
+        write_code("refused", label, hvq_picture_histograms(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), mode,
                                                                            ref.empty() ? nullptr : ref.data(), dst, caller));
     };
     const Refs ok = { { sa, 1, nullptr }, { sa, 0, nullptr } };
@@ -255,13 +222,9 @@ static void scenario_refused()
     refuse("evicted_ref", ctx, 2, { sd, sd }, { last, last }, {}, D, { { sd, last, nullptr }, { sd, 0, nullptr } }, o);
     refuse("queued", ctx, 2, { sa, sa }, { 0, queued }, {}, V, {}, o);
     refuse("queued_ref", ctx, 2, { sa, sa }, { 0, 1 }, {}, D, { { sa, 1, nullptr }, { sa, queued, nullptr } }, o);
-    fprintf(g_res, "R refused/n0 %d\n", hvq_picture_histograms(ctx, 0, nullptr, nullptr, nullptr, V, nullptr, nullptr, caller));
+    write_code("refused", "n0", hvq_picture_histograms(ctx, 0, nullptr, nullptr, nullptr, V, nullptr, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
-    std::vector<uint8_t> back(sent.size());
-    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
-    size_t same = 0;
-    for (uint8_t x : back) same += x == 0xA5;
-    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    sent.write("refused");
     /* the well-formed calls right after them work */
     CHECK(hvq_flush(ctx));
     Call c = call_histograms(ctx, { Item{ a.name, resident(sa, 1), none() }, Item{ d.name, resident(sd, last), none() } }, false, caller, "refused/then_ok");
@@ -269,25 +232,11 @@ static void scenario_refused()
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&e);
-    HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_histograms_driver <scenario> <outdir> <golden dir>\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_histograms_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
-    else { fprintf(stderr, "fake_histograms_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "memory", scenario_memory }, { "reuse", scenario_reuse },
+                                     { "refused", scenario_refused } });
 }

@@ -11,12 +11,13 @@
  *       one file read back.  form: pic (a resident picture), mem (the caller's memory: a copy of that picture of the clip); the tail is
  *       what lies between the file's end and cap (everything within cap when the file did not fit)
  *   R <label> <return code>                           a return code the test wants to see
+ *   E <label> <text>                                  the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>     the destinations and lengths after refused calls
  *   G <label> <guard bytes that still hold the sentinel> <guard bytes>     the 64 bytes on either side of every destination of the label's calls
  * Caller-side resources (a stream, destinations, lengths, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_jpeg_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 #include "../../hvqm4_amd/csrc/hvq_jpeg.h"
 
 static const size_t GUARD = 64;
@@ -29,14 +30,7 @@ static Item resident(const Clip &c, int sid, int k, long long cap = -1) { return
 
 static Item in_memory(HvqContext *ctx, const Clip &c, int sid, int k, size_t offset, std::vector<void *> *keep, long long cap = -1)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Item{ &c, sid, -1, k, (uint8_t *)d + offset, cap };
+    return Item{ &c, sid, -1, k, uploaded(read_back(ctx, sid, k), offset, keep), cap };
 }
 
 struct Call { std::vector<void *> alloc; std::vector<uint64_t> cap; void *lengths; std::vector<Item> items; std::string label; int quality; };
@@ -105,11 +99,8 @@ static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrai
 
 /* six clips of three samplings in one context: per clip every picture at quality 90; one call over all clips interleaved at quality 50;
  * qualities 1 and 100 on the first two pictures of every clip; n == 0 */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     for (const char *nm : SIX) {
@@ -135,17 +126,12 @@ static void scenario_goldens()
     for (Call &c : calls) write_call(&c);
     write_guards("goldens");
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* the caller's memory as the picture, at the start of an allocation and 16 bytes into one, mixed with resident pictures, two streams of
  * different sizes and samplings in one call; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     const int na = (int)a.pics.size();
@@ -167,27 +153,23 @@ static void scenario_memory()
     write_call(&e);
     write_guards("memory");
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
-/* capacities: argv[4..] give, for pictures 0 .. 3 of gop64x48_15 at quality 90, the exact lengths (the test's reference knows them): picture
+/* capacities: the arguments behind the golden directory give, for pictures 0 .. 3 of gop64x48_15 at quality 90, the exact lengths (the test's reference knows them): picture
  * 1 gets one byte less than it needs, its neighbours exactly what they need; then the smallest capacity the call takes, 631; then the
  * call again with what the first reported */
-static std::vector<long long> g_args;
-static void scenario_overflow()
+static void scenario_overflow(HvqContext *&ctx, hipStream_t caller)
 {
-    if (g_args.size() != 4) { fprintf(stderr, "fake_jpeg_driver: overflow takes the four exact lengths\n"); exit(2); }
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
+    if (g_extra.size() != 4) { fprintf(stderr, "fake_jpeg_driver: overflow takes the four exact lengths\n"); exit(2); }
+    std::vector<long long> lengths;
+    for (const std::string &a : g_extra) lengths.push_back(atoll(a.c_str()));
     const Clip &a = clip("gop64x48_15");
     const int sa = decode(ctx, a);
     std::vector<Item> items, tiny, again;
     for (int k = 0; k < 4; ++k) {
-        items.push_back(resident(a, sa, k, g_args[(size_t)k] - (k == 1)));
+        items.push_back(resident(a, sa, k, lengths[(size_t)k] - (k == 1)));
         tiny.push_back(resident(a, sa, k, 631));
-        again.push_back(resident(a, sa, k, g_args[(size_t)k]));
+        again.push_back(resident(a, sa, k, lengths[(size_t)k]));
     }
     Call c = call_jpeg(ctx, items, 90, caller, "overflow/short");
     Call d = call_jpeg(ctx, tiny, 90, caller, "overflow/tiny");
@@ -197,16 +179,11 @@ static void scenario_overflow()
     write_call(&d);
     write_call(&e);
     write_guards("overflow");
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into two sentinel-filled destinations and lengths that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a;
     const int sa = decode(ctx, a);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -219,20 +196,17 @@ static void scenario_refused()
     const int queued = (int)a.pics.size();
 
     const uint64_t room = hvq_jpeg_bound(a.info.width, a.info.height, a.info.h_samp, a.info.v_samp);
-    void *out = nullptr, *mem = nullptr;
     const size_t stride = ((size_t)room + 15u) & ~(size_t)15u;
-    const size_t all = 2u * stride + 32u;                                              /* two destinations, then the lengths */
-    HIP(hipMalloc(&out, all));
+    Sentinels sent;
+    void *out = sent.room(2u * stride + 32u), *mem = nullptr;                          /* two destinations, then the lengths */
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    std::vector<uint8_t> sent(all, 0xA5);
-    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
     uint8_t *o0 = (uint8_t *)out, *o1 = o0 + stride;
     uint64_t *len = (uint64_t *)(o0 + 2u * stride);
     typedef std::vector<void *> Outs;
     typedef std::vector<const void *> Srcs;
     typedef std::vector<uint64_t> Caps;
     auto refuse = [&](const char *label, HvqContext *cx, int n, std::vector<int> sids, std::vector<int> ords, Srcs src, int quality, Outs dst, Caps cap, uint64_t *lengths, int null_what = 0) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_encode_jpeg(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), quality,
+        write_code("refused", label, hvq_encode_jpeg(cx, n, sids.data(), ords.data(), src.empty() ? nullptr : src.data(), quality,
                                                                     null_what == 1 ? nullptr : dst.data(), null_what == 2 ? nullptr : cap.data(), lengths, caller));
     };
     const Outs oo = { o0, o1 };
@@ -259,24 +233,20 @@ static void scenario_refused()
     refuse("too_many", ctx, 65536, { sa }, { 0 }, {}, 90, oo, cc, len);
     refuse("evicted", ctx, 2, { sd, sd }, { last, 0 }, {}, 90, oo, cc, len);
     refuse("queued", ctx, 2, { sa, sa }, { 0, queued }, {}, 90, oo, cc, len);
-    fprintf(g_res, "R refused/n0 %d\n", hvq_encode_jpeg(ctx, 0, nullptr, nullptr, nullptr, 90, nullptr, nullptr, nullptr, caller));
-    fprintf(g_res, "R refused/n0_bad_quality %d\n", hvq_encode_jpeg(ctx, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, caller));
+    write_code("refused", "n0", hvq_encode_jpeg(ctx, 0, nullptr, nullptr, nullptr, 90, nullptr, nullptr, nullptr, caller));
+    write_code("refused", "n0_bad_quality", hvq_encode_jpeg(ctx, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
-    std::vector<uint8_t> back(sent.size());
-    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
-    size_t same = 0;
-    for (uint8_t x : back) same += x == 0xA5;
-    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    sent.write("refused");
     /* hvq_jpeg_header and hvq_jpeg_bound */
     uint8_t hdr[700];
     size_t hl = 0;
-    fprintf(g_res, "R header/ok %d\n", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, sizeof hdr, &hl));
+    write_code("header", "ok", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, sizeof hdr, &hl));
     fprintf(g_res, "R header/len %d\n", (int)hl);
-    fprintf(g_res, "R header/no_len %d\n", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, 629, nullptr));
-    fprintf(g_res, "R header/short %d\n", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, 628, &hl));
-    fprintf(g_res, "R header/null %d\n", hvq_jpeg_header(64, 48, 2, 2, 90, nullptr, 700, &hl));
-    fprintf(g_res, "R header/quality %d\n", hvq_jpeg_header(64, 48, 2, 2, 0, hdr, sizeof hdr, &hl));
-    fprintf(g_res, "R header/geometry %d\n", hvq_jpeg_header(60, 48, 2, 2, 90, hdr, sizeof hdr, &hl));
+    write_code("header", "no_len", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, 629, nullptr));
+    write_code("header", "short", hvq_jpeg_header(64, 48, 2, 2, 90, hdr, 628, &hl));
+    write_code("header", "null", hvq_jpeg_header(64, 48, 2, 2, 90, nullptr, 700, &hl));
+    write_code("header", "quality", hvq_jpeg_header(64, 48, 2, 2, 0, hdr, sizeof hdr, &hl));
+    write_code("header", "geometry", hvq_jpeg_header(60, 48, 2, 2, 90, hdr, sizeof hdr, &hl));
     fprintf(g_res, "R bound/64x48 %d\n", (int)hvq_jpeg_bound(64, 48, 2, 2));
     fprintf(g_res, "R bound/geometry %d\n", (int)hvq_jpeg_bound(64, 48, 1, 2));
     /* the well-formed call right after them works */
@@ -285,10 +255,7 @@ static void scenario_refused()
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_guards("refused");
-    HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* the division helper the kernels and the fake body share (hvq_jpeg.h) against `/`, exhaustively: every numerator up to HVQ_JPEG_DIV_MAX
@@ -318,19 +285,6 @@ static void scenario_helpers()
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_jpeg_driver <scenario> <outdir> <golden dir> [lengths]\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    for (int i = 4; i < argc; ++i) g_args.push_back(atoll(argv[i]));
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_jpeg_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "overflow") scenario_overflow();
-    else if (sc == "refused") scenario_refused();
-    else if (sc == "helpers") scenario_helpers();
-    else { fprintf(stderr, "fake_jpeg_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "memory", scenario_memory }, { "overflow", scenario_overflow },
+                                     { "refused", scenario_refused }, { "helpers", nullptr, scenario_helpers } }, " [lengths]");
 }

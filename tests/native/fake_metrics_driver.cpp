@@ -10,11 +10,12 @@
  *   M <label> <clip a> <ordinal a> <form> <clip b> <ordinal b> <12 numbers>    one record read back: [Y, U, V][sum_a, sum_b, sad, sse]
  *       form: pic (a resident reference), zeros ("-" 0 for b), inv (the caller's memory: picture b with every byte inverted, 255 - x)
  *   R <label> <return code>                                                    a return code the test wants to see
+ *   E <label> <text>                                                           the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>                     an output buffer after refused calls
  * Caller-side resources (a stream, output records, reference memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_metrics_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 
 /* one pair of a call and what the test is told about it */
 struct Pair { int sid, k; HvqMetricsRef ref; std::string clip_a, form, clip_b; int kb; };
@@ -25,15 +26,7 @@ static Pair against_zeros(int sid, const Clip &a, int k) { return Pair{ sid, k, 
 /* the caller's memory: picture kb of stream sid_b read back, every byte inverted, in device memory at `offset` bytes into an allocation */
 static Pair against_memory(HvqContext *ctx, int sid, const Clip &a, int k, int sid_b, const Clip &b, int kb, size_t offset, std::vector<void *> *keep)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid_b);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid_b, kb, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Pair{ sid, k, HvqMetricsRef{ -1, 0, (uint8_t *)d + offset }, a.name, "inv", b.name, kb };
+    return Pair{ sid, k, HvqMetricsRef{ -1, 0, uploaded(inverted(ctx, sid_b, kb), offset, keep) }, a.name, "inv", b.name, kb };
 }
 
 struct Call { uint64_t *out; std::vector<Pair> pairs; std::string label; };
@@ -45,10 +38,7 @@ static Call call_metrics(HvqContext *ctx, const std::vector<Pair> &pairs, bool n
     std::vector<int> sids, ords;
     std::vector<HvqMetricsRef> refs;
     for (const Pair &p : pairs) { sids.push_back(p.sid); ords.push_back(p.k); refs.push_back(p.ref); }
-    void *out = nullptr;
-    HIP(hipMalloc(&out, (size_t)n * 96u));
-    std::vector<uint8_t> ff((size_t)n * 96u, 0xFF);
-    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    void *out = record_room((size_t)n * 96u);
     CHECK(hvq_picture_metrics(ctx, n, sids.data(), ords.data(), null_ref ? nullptr : refs.data(), (uint64_t *)out, caller));
     return Call{ (uint64_t *)out, pairs, label };
 }
@@ -56,27 +46,21 @@ static Call call_metrics(HvqContext *ctx, const std::vector<Pair> &pairs, bool n
 /* after the caller's stream has been waited for */
 static void write_call(Call *c)
 {
-    std::vector<uint64_t> host(c->pairs.size() * 12u);
-    HIP(hipMemcpy(host.data(), c->out, host.size() * 8u, hipMemcpyDeviceToHost));
+    const std::vector<uint64_t> host = take_records(&c->out, c->pairs.size() * 12u);
     for (size_t i = 0; i < c->pairs.size(); ++i) {
         const Pair &p = c->pairs[i];
         fprintf(g_res, "M %s %s %d %s %s %d", c->label.c_str(), p.clip_a.c_str(), p.k, p.form.c_str(), p.clip_b.c_str(), p.kb);
         for (int v = 0; v < 12; ++v) fprintf(g_res, " %llu", (unsigned long long)host[i * 12u + (size_t)v]);
         fprintf(g_res, "\n");
     }
-    HIP(hipFree(c->out));
-    c->out = nullptr;
 }
 
 static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8" };
 
 /* six clips of three samplings in one context: per clip a call of (k, k - 1), (k, k) and zeros for every picture, one call with ref = NULL,
  * then one call over all clips with the forms interleaved, and a call of one pair */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     for (const char *nm : SIX) {
@@ -106,16 +90,11 @@ static void scenario_goldens()
     HIP(hipStreamSynchronize(caller));
     for (Call &c : calls) write_call(&c);
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* references in the caller's memory, at the start of an allocation and 16 bytes into one; the same clip in two streams: across them */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sa2 = decode(ctx, a), sb = decode(ctx, b);
     std::vector<void *> keep;
@@ -133,17 +112,12 @@ static void scenario_memory()
     write_call(&c);
     write_call(&d);
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the records are those of the pictures as they were */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -170,20 +144,16 @@ static void scenario_reuse()
     d.pairs = late;
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(against_zeros(se, e, k));
     Call f = call_metrics(ctx, other, false, caller, "reuse/destroy");
-    hvq_context_destroy(ctx);
+    hvq_context_destroy(ctx); ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into one sentinel-filled buffer that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &b = clip("yuv422_64x48"), &d = a;
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -195,15 +165,12 @@ static void scenario_refused()
     CHECK(hvq_stream_submit(ctx, sa, a.pics[0].type, a.pics[0].p, a.pics[0].len));      /* queued, not flushed: ordinal n of sa */
     const int queued = (int)a.pics.size();
 
-    const size_t bytes = 2u * 96u;
-    void *out = nullptr, *mem = nullptr;
-    HIP(hipMalloc(&out, bytes + 8u));
+    Sentinels sent;
+    void *out = sent.room(2u * 96u + 8u), *mem = nullptr;
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    std::vector<uint8_t> sent(bytes + 8u, 0xA5);
-    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
     uint64_t *o = (uint64_t *)out;
     auto refuse = [&](const char *label, int n, std::vector<int> sids, std::vector<int> ords, std::vector<HvqMetricsRef> refs, uint64_t *dst) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_metrics(ctx, n, sids.data(), ords.data(), refs.empty() ? nullptr : refs.data(), dst, caller));
+        write_code("refused", label, hvq_picture_metrics(ctx, n, sids.data(), ords.data(), refs.empty() ? nullptr : refs.data(), dst, caller));
     };
     const HvqMetricsRef Z{ -1, 0, nullptr };
     refuse("geometry", 2, { sa, sa }, { 0, 1 }, { Z, HvqMetricsRef{ sb, 1, nullptr } }, o);
@@ -221,35 +188,17 @@ static void scenario_refused()
     refuse("evicted_ref", 2, { sd, sd }, { last, last }, { Z, HvqMetricsRef{ sd, 0, nullptr } }, o);
     refuse("queued", 2, { sa, sa }, { 0, queued }, {}, o);
     HIP(hipStreamSynchronize(caller));
-    std::vector<uint8_t> back(sent.size());
-    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
-    size_t same = 0;
-    for (uint8_t x : back) same += x == 0xA5;
-    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    sent.write("refused");
     /* the well-formed call right after them works */
     CHECK(hvq_flush(ctx));
     Call c = call_metrics(ctx, { against_picture(sa, a, 1, sa, a, 0), against_zeros(sd, d, last) }, false, caller, "refused/then_ok");
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
-    HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_metrics_driver <scenario> <outdir> <golden dir>\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_metrics_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
-    else { fprintf(stderr, "fake_metrics_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "memory", scenario_memory }, { "reuse", scenario_reuse },
+                                     { "refused", scenario_refused } });
 }

@@ -10,12 +10,13 @@
  *   F <label> <clip> <a ordinal> <b form> <b ordinal> <block> <radius> <rows> <cols> <rows * cols * 4 numbers>     one field read back
  *       b form: pic (a resident reference), mem (the caller's memory: a copy of that picture of the clip)
  *   R <label> <return code>                           a return code the test wants to see
+ *   E <label> <text>                                  the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>     the fields after refused calls
  *   G <label> <guard bytes that still hold the sentinel> <guard bytes>     the 64 bytes on either side of every field of the label's calls
  * Caller-side resources (a stream, fields, picture memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_motion_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 
 static const size_t GUARD = 64;
 
@@ -28,14 +29,7 @@ static Ref resident(int sid, int k) { return Ref{ sid, k, nullptr, "pic", k }; }
 /* the caller's memory: picture k of stream sid read back into device memory at `offset` bytes into an allocation */
 static Ref in_memory(HvqContext *ctx, int sid, int k, size_t offset, std::vector<void *> *keep)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Ref{ -1, 0, (uint8_t *)d + offset, "mem", k };
+    return Ref{ -1, 0, uploaded(read_back(ctx, sid, k), offset, keep), "mem", k };
 }
 
 struct Call { std::vector<void *> alloc; std::vector<size_t> bytes; std::vector<Item> items; std::string label; int block, radius; };
@@ -96,11 +90,8 @@ static const char *SIX[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrai
 
 /* six clips of three samplings in one context: per clip every picture against its predecessor at B = 8 with R = 15 and R = 3, and at
  * B = 16 with R = 15 where blocks of 16 tile the clip; one call over all clips interleaved; a call of one picture against itself; n == 0 */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     for (const char *nm : SIX) {
@@ -126,17 +117,12 @@ static void scenario_goldens()
     for (Call &c : calls) write_call(&c);
     write_guards("goldens");
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* the caller's memory as b, at the start of an allocation and 16 bytes into one, mixed with resident references and with a reference of
  * another stream of the same geometry, two streams of different sizes in one call; on the caller's stream and on the null stream */
-static void scenario_memory()
+static void scenario_memory(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("yuv422_64x48"), &b = clip("ragged24x40");
     const int sa = decode(ctx, a), sb = decode(ctx, b), sa2 = decode(ctx, a);
     const int na = (int)a.pics.size();
@@ -158,18 +144,13 @@ static void scenario_memory()
     write_call(&e);
     write_guards("memory");
     for (void *p : keep) HIP(hipFree(p));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* calls queued on the caller's stream, then flushes that hand the slots of their pictures to later ones, nothing waited for in between:
  * the later writer of a slot waits, the fields are those of the pictures as they were.  Then a picture of the batch in flight, as a and
  * as b: the call ends that batch itself */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -200,7 +181,7 @@ static void scenario_reuse()
     /* a call of another stream's pictures behind them in the chain; destroyed with that one still queued */
     for (int k = 1; k < (int)e.pics.size(); ++k) other.push_back(Item{ &e, se, k, k, resident(se, k - 1) });
     Call f = call_motion(ctx, other, 16, 15, caller, "reuse/destroy");
-    hvq_context_destroy(ctx);
+    hvq_context_destroy(ctx); ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&c2);
@@ -208,15 +189,11 @@ static void scenario_reuse()
     write_call(&d2);
     write_call(&f);
     write_guards("reuse");
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into two sentinel-filled fields that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &d = a, &g = clip("yuv422_64x48"), &q = clip("ragged24x40");
     const int sa = decode(ctx, a), sg = decode(ctx, g), sq = decode(ctx, q);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -229,16 +206,14 @@ static void scenario_refused()
     const int queued = (int)a.pics.size();
 
     const size_t fb = field_bytes(a, 8);                                                /* the largest field a call below could write */
-    void *out = nullptr, *mem = nullptr;
-    HIP(hipMalloc(&out, 2u * fb + 16u));
+    Sentinels sent;
+    void *out = sent.room(2u * fb + 16u), *mem = nullptr;
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    std::vector<uint8_t> sent(2u * fb + 16u, 0xA5);
-    HIP(hipMemcpy(out, sent.data(), sent.size(), hipMemcpyHostToDevice));
     int32_t *o0 = (int32_t *)out, *o1 = (int32_t *)((uint8_t *)out + fb);
     typedef std::vector<HvqMetricsRef> Refs;
     typedef std::vector<int32_t *> Outs;
     auto refuse = [&](const char *label, HvqContext *cx, int n, std::vector<int> sids, std::vector<int> ords, Refs ref, int block, int radius, Outs dst, bool null_out = false) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_motion(cx, n, sids.data(), ords.data(), ref.empty() ? nullptr : ref.data(), block, radius,
+        write_code("refused", label, hvq_picture_motion(cx, n, sids.data(), ords.data(), ref.empty() ? nullptr : ref.data(), block, radius,
                                                                        null_out ? nullptr : dst.data(), caller));
     };
     const Refs ok = { { sa, 1, nullptr }, { sa, 0, nullptr } };
@@ -273,47 +248,29 @@ static void scenario_refused()
     refuse("evicted_ref", ctx, 2, { sd, sd }, { last, last }, { { sd, last, nullptr }, { sd, 0, nullptr } }, 8, 15, oo);
     refuse("queued", ctx, 2, { sa, sa }, { 0, queued }, ok, 8, 15, oo);
     refuse("queued_ref", ctx, 2, { sa, sa }, { 0, 1 }, { { sa, 1, nullptr }, { sa, queued, nullptr } }, 8, 15, oo);
-    fprintf(g_res, "R refused/n0 %d\n", hvq_picture_motion(ctx, 0, nullptr, nullptr, nullptr, 8, 15, nullptr, caller));
-    fprintf(g_res, "R refused/n0_bad_block %d\n", hvq_picture_motion(ctx, 0, nullptr, nullptr, nullptr, 7, 15, nullptr, caller));
+    write_code("refused", "n0", hvq_picture_motion(ctx, 0, nullptr, nullptr, nullptr, 8, 15, nullptr, caller));
+    write_code("refused", "n0_bad_block", hvq_picture_motion(ctx, 0, nullptr, nullptr, nullptr, 7, 15, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
-    std::vector<uint8_t> back(sent.size());
-    HIP(hipMemcpy(back.data(), out, back.size(), hipMemcpyDeviceToHost));
-    size_t same = 0;
-    for (uint8_t x : back) same += x == 0xA5;
-    fprintf(g_res, "S refused %zu %zu\n", same, back.size());
+    sent.write("refused");
     /* hvq_motion_blocks */
     int32_t dims[2] = { -7, -7 };
-    fprintf(g_res, "R blocks/64x48_8 %d\n", hvq_motion_blocks(64, 48, 2, 2, 8, dims));
+    write_code("blocks", "64x48_8", hvq_motion_blocks(64, 48, 2, 2, 8, dims));
     fprintf(g_res, "R blocks/64x48_8_rows %d\nR blocks/64x48_8_cols %d\n", dims[0], dims[1]);
-    fprintf(g_res, "R blocks/64x48_16 %d\n", hvq_motion_blocks(64, 48, 2, 2, 16, nullptr));
-    fprintf(g_res, "R blocks/24x40_16 %d\n", hvq_motion_blocks(24, 40, 2, 2, 16, dims));
-    fprintf(g_res, "R blocks/64x48_12 %d\n", hvq_motion_blocks(64, 48, 2, 2, 12, dims));
-    fprintf(g_res, "R blocks/geometry %d\n", hvq_motion_blocks(60, 48, 2, 2, 8, dims));
+    write_code("blocks", "64x48_16", hvq_motion_blocks(64, 48, 2, 2, 16, nullptr));
+    write_code("blocks", "24x40_16", hvq_motion_blocks(24, 40, 2, 2, 16, dims));
+    write_code("blocks", "64x48_12", hvq_motion_blocks(64, 48, 2, 2, 12, dims));
+    write_code("blocks", "geometry", hvq_motion_blocks(60, 48, 2, 2, 8, dims));
     /* the well-formed calls right after them work */
     CHECK(hvq_flush(ctx));
     Call c = call_motion(ctx, { Item{ &a, sa, 1, 1, resident(sd, last) }, Item{ &d, sd, last, last, resident(sa, 0) } }, 8, 15, caller, "refused/then_ok");
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_guards("refused");
-    HIP(hipFree(out));
     HIP(hipFree(mem));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_motion_driver <scenario> <outdir> <golden dir>\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_motion_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "memory") scenario_memory();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
-    else { fprintf(stderr, "fake_motion_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "memory", scenario_memory }, { "reuse", scenario_reuse },
+                                     { "refused", scenario_refused } });
 }

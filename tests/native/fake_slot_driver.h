@@ -1,9 +1,9 @@
 /*
  * tests/native/fake_slot_driver.h -- TEST INFRASTRUCTURE: what the drivers of the calls that write uint8 pictures in slot layout
  * (fake_{scale,filter,warp,compose,rank,map}_driver.cpp) have in common on top of fake_driver_common.h: a geometry and its bytes, the
- * fill rules the tests know, the caller's memory a picture is uploaded into, the guarded room an output is written into and its
- * read-back, the picture and the item of a call, and the frame of a scenario.  A driver defines DRIVER_NAME and includes this header;
- * its own are its input files, its call_* (the library call and its forms), the format of its P line and its scenarios.
+ * fill rules the tests know, the guarded room an output is written into and its read-back, and the picture and the item of a call.
+ * A driver defines DRIVER_NAME and includes this header; its own are its input files, its call_* (the library call and its forms), the
+ * format of its P line and its scenarios.
  */
 #ifndef FAKE_SLOT_DRIVER_H
 #define FAKE_SLOT_DRIVER_H
@@ -35,25 +35,6 @@ static inline std::vector<uint8_t> filled(Geom g, const std::string &form, int k
         }
     } else { fprintf(stderr, DRIVER_NAME ": form %s\n", form.c_str()); exit(2); }
     return host;
-}
-
-/* picture k of stream sid read back, every byte inverted */
-static inline std::vector<uint8_t> inverted(HvqContext *ctx, int sid, int k)
-{
-    std::vector<uint8_t> host(hvq_stream_pic_bytes(ctx, sid));
-    CHECK(hvq_read_picture(ctx, sid, k, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    return host;
-}
-
-/* the caller's memory: `host` in device memory, `offset` bytes into an allocation of its own, which `keep` gets -> where the bytes lie */
-static inline void *uploaded(const std::vector<uint8_t> &host, size_t offset, std::vector<void *> *keep)
-{
-    void *d = nullptr;
-    HIP(hipMalloc(&d, host.size() + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), host.size(), hipMemcpyHostToDevice));
-    return (uint8_t *)d + offset;
 }
 
 /* The room of an output of nb bytes: an allocation of its own filled with the sentinel, `front` guard bytes (GUARD, or 0) before the
@@ -104,17 +85,5 @@ static inline Item in_memory(HvqContext *ctx, int sid, const Clip &c, int k, siz
     return Item{ inverted_picture(ctx, sid, c, k, offset, keep), entry };
 }
 static inline Item made(int sid, Geom g, const char *form, int k, std::vector<void *> *keep, int entry) { return Item{ made_picture(sid, g, form, k, keep), entry }; }
-
-/* The frame of a scenario: a context and the caller's stream around `body`, destroyed in that order.  A body that destroys the context
- * itself, with work still queued, sets `ctx` to null. */
-static inline void run_scenario(void (*body)(HvqContext *&ctx, hipStream_t caller))
-{
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
-    body(ctx, caller);
-    if (ctx) hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
-}
 
 #endif

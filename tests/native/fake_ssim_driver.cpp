@@ -12,11 +12,12 @@
  *   Q <label> <clip a> <ordinal a> <form> <clip b> <ordinal b> <guard words intact> <guard words> <n> <n hex words>
  *       the pair's map read back, the bits of its floats, and the sentinel words behind it
  *   R <label> <return code>                                                    a return code the test wants to see
+ *   E <label> <text>                                                           the library's words for the R line before it, to the end of the line (`refused` only)
  *   S <label> <bytes that still hold the sentinel> <bytes>                     an output buffer after refused calls
  * Caller-side resources (a stream, output records, maps, reference memory) come from the fake's HIP calls, as a caller's would from HIP.
  */
 #define DRIVER_NAME "fake_ssim_driver"
-#include "fake_driver_common.h"
+#include "fake_record_driver.h"
 
 static const uint32_t GUARD = 0xA5A5A5A5u;
 static const size_t GUARD_WORDS = 16;
@@ -39,15 +40,7 @@ static Pair against_picture(int sid, const Clip &a, int k, int sid_b, const Clip
 /* the caller's memory: picture kb of stream sid_b read back, every byte inverted, in device memory at `offset` bytes into an allocation */
 static Pair against_memory(HvqContext *ctx, int sid, const Clip &a, int k, int sid_b, const Clip &b, int kb, size_t offset, bool map, std::vector<void *> *keep)
 {
-    const uint32_t pb = hvq_stream_pic_bytes(ctx, sid_b);
-    std::vector<uint8_t> host(pb);
-    CHECK(hvq_read_picture(ctx, sid_b, kb, host.data(), host.size()));
-    for (uint8_t &x : host) x = (uint8_t)(255 - x);
-    void *d = nullptr;
-    HIP(hipMalloc(&d, pb + offset));
-    keep->push_back(d);
-    HIP(hipMemcpy((uint8_t *)d + offset, host.data(), pb, hipMemcpyHostToDevice));
-    return Pair{ sid, k, HvqMetricsRef{ -1, 0, (uint8_t *)d + offset }, a.name, "inv", b.name, kb, windows_of(a), map };
+    return Pair{ sid, k, HvqMetricsRef{ -1, 0, uploaded(inverted(ctx, sid_b, kb), offset, keep) }, a.name, "inv", b.name, kb, windows_of(a), map };
 }
 
 struct Call { int64_t *out; std::vector<float *> maps; std::vector<Pair> pairs; std::string label; };
@@ -73,10 +66,7 @@ static Call call_ssim(HvqContext *ctx, const std::vector<Pair> &pairs, hipStream
         }
         maps.push_back(m);
     }
-    void *out = nullptr;
-    HIP(hipMalloc(&out, (size_t)n * 48u));
-    std::vector<uint8_t> ff((size_t)n * 48u, 0xFF);
-    HIP(hipMemcpy(out, ff.data(), ff.size(), hipMemcpyHostToDevice));
+    void *out = record_room((size_t)n * 48u);
     CHECK(hvq_picture_ssim(ctx, n, sids.data(), ords.data(), refs.data(), (int64_t *)out, any ? maps.data() : nullptr, caller));
     return Call{ (int64_t *)out, maps, pairs, label };
 }
@@ -84,8 +74,7 @@ static Call call_ssim(HvqContext *ctx, const std::vector<Pair> &pairs, hipStream
 /* after the caller's stream has been waited for */
 static void write_call(Call *c)
 {
-    std::vector<int64_t> host(c->pairs.size() * 6u);
-    HIP(hipMemcpy(host.data(), c->out, host.size() * 8u, hipMemcpyDeviceToHost));
+    const std::vector<int64_t> host = take_records(&c->out, c->pairs.size() * 6u);
     for (size_t i = 0; i < c->pairs.size(); ++i) {
         const Pair &p = c->pairs[i];
         fprintf(g_res, "W %s %s %d %s %s %d", c->label.c_str(), p.clip_a.c_str(), p.k, p.form.c_str(), p.clip_b.c_str(), p.kb);
@@ -101,8 +90,6 @@ static void write_call(Call *c)
         fprintf(g_res, "\n");
         HIP(hipFree(c->maps[i]));
     }
-    HIP(hipFree(c->out));
-    c->out = nullptr;
 }
 
 static const char *SEVEN[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40", "wide296x160", "ip8", "i16" };
@@ -110,11 +97,8 @@ static const char *SEVEN[] = { "gop64x48_15", "yuv422_296x160", "yuv444_13_portr
 /* seven clips of three samplings in one context: per clip one call of (k, k - 1), (k, k) and (k, inverted k) for every picture with a map
  * for every pair, the same call without maps, then one call over all clips with the forms interleaved and a map for every other pair,
  * and a call of one pair */
-static void scenario_goldens()
+static void scenario_goldens(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     std::vector<std::pair<int, const Clip *>> sc;
     std::vector<Call> calls;
     std::vector<void *> keep;
@@ -149,17 +133,12 @@ static void scenario_goldens()
     for (Call &c : calls) write_call(&c);
     for (void *p : keep) HIP(hipFree(p));
     for (auto &s : sc) CHECK(hvq_stream_close(ctx, s.first));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* a call queued on the caller's stream, then flushes that hand the slots of its pictures to later ones, nothing waited for in between:
  * the records are those of the pictures as they were; then a call destroyed with the context while still queued */
-static void scenario_reuse()
+static void scenario_reuse(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &e = clip("yuv444_64x48");
     const int n = (int)a.pics.size();
     const int sa = decode(ctx, a), se = decode(ctx, e);
@@ -184,20 +163,16 @@ static void scenario_reuse()
     d.pairs = late;
     for (int k = 0; k < (int)e.pics.size(); ++k) other.push_back(against_picture(se, e, k, se, e, k ? k - 1 : 0, true));
     Call f = call_ssim(ctx, other, caller, "reuse/destroy");
-    hvq_context_destroy(ctx);
+    hvq_context_destroy(ctx); ctx = nullptr;
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
     write_call(&d);
     write_call(&f);
-    HIP(hipStreamDestroy(caller));
 }
 
 /* every refusal of the specification, into sentinel-filled buffers that must come back untouched */
-static void scenario_refused()
+static void scenario_refused(HvqContext *&ctx, hipStream_t caller)
 {
-    HvqContext *ctx = nullptr;
-    CHECK(hvq_context_create(0, &ctx));
-    hipStream_t caller = caller_stream();
     const Clip &a = clip("gop64x48_15"), &b = clip("yuv422_64x48"), &d = a;
     const int sa = decode(ctx, a), sb = decode(ctx, b);
     /* a ring of 3 slots: the clip's first pictures are gone when its last ones are decoded */
@@ -210,19 +185,13 @@ static void scenario_refused()
     const int queued = (int)a.pics.size();
 
     const size_t bytes = 8u + 2u * 48u + 8u, mbytes = ((size_t)windows_of(a) + 2u) * 4u;         /* sentinels on both sides of out; a map with room */
-    void *outbuf = nullptr, *mem = nullptr, *map0 = nullptr, *map1 = nullptr;
-    HIP(hipMalloc(&outbuf, bytes));
+    Sentinels sent;
+    void *outbuf = sent.room(bytes), *map0 = sent.room(mbytes), *map1 = sent.room(mbytes), *mem = nullptr;
     HIP(hipMalloc(&mem, hvq_stream_pic_bytes(ctx, sa) + 32u));
-    HIP(hipMalloc(&map0, mbytes));
-    HIP(hipMalloc(&map1, mbytes));
-    std::vector<uint8_t> sent(bytes, 0xA5), msent(mbytes, 0xA5);
-    HIP(hipMemcpy(outbuf, sent.data(), sent.size(), hipMemcpyHostToDevice));
-    HIP(hipMemcpy(map0, msent.data(), msent.size(), hipMemcpyHostToDevice));
-    HIP(hipMemcpy(map1, msent.data(), msent.size(), hipMemcpyHostToDevice));
     int64_t *o = (int64_t *)((uint8_t *)outbuf + 8);
     float *good_maps[2] = { (float *)map0, (float *)map1 };
     auto refuse = [&](const char *label, int n, std::vector<int> sids, std::vector<int> ords, std::vector<HvqMetricsRef> refs, int64_t *dst, float *const *maps) {
-        fprintf(g_res, "R refused/%s %d\n", label, hvq_picture_ssim(ctx, n, sids.data(), ords.data(), refs.empty() ? nullptr : refs.data(), dst, maps, caller));
+        write_code("refused", label, hvq_picture_ssim(ctx, n, sids.data(), ords.data(), refs.empty() ? nullptr : refs.data(), dst, maps, caller));
     };
     const HvqMetricsRef S0{ sa, 0, nullptr }, S1{ sa, 1, nullptr };
     refuse("geometry", 2, { sa, sa }, { 0, 1 }, { S1, HvqMetricsRef{ sb, 1, nullptr } }, o, good_maps);
@@ -243,41 +212,18 @@ static void scenario_refused()
     refuse("evicted", 2, { sd, sd }, { last, 0 }, { HvqMetricsRef{ sd, last, nullptr }, HvqMetricsRef{ sd, last, nullptr } }, o, good_maps);
     refuse("evicted_ref", 2, { sd, sd }, { last, last }, { HvqMetricsRef{ sd, last, nullptr }, HvqMetricsRef{ sd, 0, nullptr } }, o, good_maps);
     refuse("queued", 2, { sa, sa }, { 0, queued }, { S1, S0 }, o, good_maps);
-    fprintf(g_res, "R refused/null_context %d\n", hvq_picture_ssim(nullptr, 1, &sa, &last, &S0, o, nullptr, caller));
+    write_code("refused", "null_context", hvq_picture_ssim(nullptr, 1, &sa, &last, &S0, o, nullptr, caller));
     HIP(hipStreamSynchronize(caller));
-    size_t same = 0, total = 0;
-    for (void *buf : { outbuf, map0, map1 }) {
-        std::vector<uint8_t> back(buf == outbuf ? bytes : mbytes);
-        HIP(hipMemcpy(back.data(), buf, back.size(), hipMemcpyDeviceToHost));
-        for (uint8_t x : back) same += x == 0xA5;
-        total += back.size();
-    }
-    fprintf(g_res, "S refused %zu %zu\n", same, total);
+    sent.write("refused");
     /* the well-formed call right after them works */
     CHECK(hvq_flush(ctx));
     Call c = call_ssim(ctx, { against_picture(sa, a, 1, sa, a, 0, true), against_picture(sd, d, last, sd, d, last, false) }, caller, "refused/then_ok");
     HIP(hipStreamSynchronize(caller));
     write_call(&c);
-    HIP(hipFree(outbuf));
     HIP(hipFree(mem));
-    HIP(hipFree(map0));
-    HIP(hipFree(map1));
-    hvq_context_destroy(ctx);
-    HIP(hipStreamDestroy(caller));
 }
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: fake_ssim_driver <scenario> <outdir> <golden dir>\n"); return 2; }
-    const std::string sc = argv[1];
-    g_out = argv[2]; g_golden = argv[3];
-    g_res = fopen((g_out + "/results.txt").c_str(), "w");
-    if (!g_res) { fprintf(stderr, "fake_ssim_driver: cannot write into %s\n", g_out.c_str()); return 2; }
-    if (sc == "goldens") scenario_goldens();
-    else if (sc == "reuse") scenario_reuse();
-    else if (sc == "refused") scenario_refused();
-    else { fprintf(stderr, "fake_ssim_driver: unknown scenario %s\n", sc.c_str()); return 2; }
-    fake_drain_all();
-    fclose(g_res);
-    return 0;
+    return driver_main(argc, argv, { { "goldens", scenario_goldens }, { "reuse", scenario_reuse }, { "refused", scenario_refused } });
 }

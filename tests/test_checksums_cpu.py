@@ -14,7 +14,6 @@
 import hashlib
 import json
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -221,15 +220,9 @@ def drivers():
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path)
     K, R, S = {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "C":
             label, name, k, form = f[1], f[2], int(f[3]), f[4]
@@ -241,10 +234,10 @@ def _run(exe, scenario, schedule, tmp_path):
             R[f[1]] = int(f[2])
         elif f[0] == "S":
             S[f[1]] = (int(f[2]), int(f[3]))
-    return K, R, S
+    return K, R, S, fd.refusal_texts(lines)
 
 
-def _check_goldens(K, R, S):
+def _check_goldens(K, R, S, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert len({_geometry(nm)[2:] for nm in SIX}) == 3                    # 4:2:0, 4:2:2 and 4:4:4
     assert K["goldens/clip"] == [(nm, k, "pic") for nm in SIX for k in range(n[nm])]
@@ -254,13 +247,13 @@ def _check_goldens(K, R, S):
     assert R == {"goldens/n0": 0}
 
 
-def _check_memory(K, R, S):
+def _check_memory(K, R, S, E):
     na = fd.n_pics("yuv422_64x48")
     want = [x for k in range(na) for x in (("yuv422_64x48", k, "inv"), ("yuv422_64x48", k, "pic"))] + [("ragged24x40", 1, "inv"), ("ragged24x40", 1, "pic")]
     assert K["memory"] == want and K["memory/nullstream"] == want
 
 
-def _check_reuse(K, R, S):
+def _check_reuse(K, R, S, E):
     from hvqm4_amd._lib import HVQ_E_STATE
     n, ne = fd.n_pics("gop64x48_15"), fd.n_pics("yuv444_64x48")
     assert K["reuse"] == [("gop64x48_15", k, "pic") for k in range(n)]
@@ -269,7 +262,7 @@ def _check_reuse(K, R, S):
     assert K["reuse/destroy"] == [("yuv444_64x48", k, "pic") for k in range(ne)]
 
 
-def _check_backtoback(K, R, S):
+def _check_backtoback(K, R, S, E):
     small = [("wide296x160", k, "pic") for k in range(2)]
     large = ([("gop64x48_15", k, "pic") for k in range(fd.n_pics("gop64x48_15"))] + [("wide296x160", k, "pic") for k in range(fd.n_pics("wide296x160"))]) * 6
     assert K["backtoback/small"] == small == K["backtoback/again"]
@@ -277,7 +270,29 @@ def _check_backtoback(K, R, S):
     assert len(large) * 96 > 4096 >= len(small) * 96 * 2, "the accumulators (96 bytes a picture, a page at first) had to grow with the small call queued"
 
 
-def _check_refused(K, R, S):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/null_context": "bad arguments",
+    "refused/bad_stream": "bad stream 99",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/misaligned_src": "picture 1: the pointer must be a multiple of 16",
+    "refused/src_with_ordinal": "picture 1: a pointer together with ordinal 1 (the caller's memory takes ordinal -1)",
+    "refused/src_with_bad_stream": "bad stream 99",
+    "refused/minus_one_without_src": "stream 0: bad picture ordinal -1",
+    "refused/null_out": "out must be a non-null multiple of 8",
+    "refused/misaligned_out": "out must be a non-null multiple of 8",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most (one grid row each)",
+    "refused/evicted": "stream 1 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0": "stream 0 picture 7 is queued but not flushed",
+}
+
+
+def _check_refused(K, R, S, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_STATE
     want = {"null_context": HVQ_E_ARG, "bad_stream": HVQ_E_ARG, "bad_ordinal": HVQ_E_ARG, "misaligned_src": HVQ_E_ARG, "src_with_ordinal": HVQ_E_ARG,
             "src_with_bad_stream": HVQ_E_ARG, "minus_one_without_src": HVQ_E_ARG, "null_out": HVQ_E_ARG, "misaligned_out": HVQ_E_ARG,
@@ -295,8 +310,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "reuse": _check_re
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    K, R, S = _run(drivers[build], scenario, schedule, tmp_path)
-    CHECKS[scenario](K, R, S)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path))
 
 
 def test_the_existing_fake_builds_link_without_the_checksum_body():

@@ -6,7 +6,6 @@ import ctypes as C
 import hashlib
 import json
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -534,21 +533,15 @@ _scripts = {}
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
     script = None
     if scenario in SCRIPTS:
         if scenario not in _scripts:
             _scripts[scenario] = SCRIPTS[scenario]()
         script = _scripts[scenario]
-        (out / "script.txt").write_text("\n".join(script.lines) + "\n")
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "script" if script else scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, "script" if script else scenario, schedule, tmp_path,
+                                inputs={"script.txt": "\n".join(script.lines) + "\n"} if script else None)
     P, R, S, B = {}, {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "P":
             assert int(f[8]) == 1, f"{f[1]}: the bytes around target {f[2]} were written"

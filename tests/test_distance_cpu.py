@@ -7,7 +7,6 @@ builds its own; nothing is preloaded and no Python is involved in the sanitised 
 import json
 import math
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -242,21 +241,13 @@ def _inputs(scenario):
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
     items = _inputs(scenario)
     lines = [f"M {m.mode} {m.lo} {m.hi} {m.invert}" for m in cases.MASKS]
     lines += [f"P {g[0]} {g[1]} {g[2]} {g[3]} {r.plane} {r.lo} {r.hi} {r.metric} {r.border} {s}" for _l, g, _p, r, s in items]
-    (out / "calls.txt").write_text("\n".join(lines) + "\n")
-    (out / "pictures.bin").write_bytes(b"".join(p.tobytes() for _l, _g, p, _r, _s in items))
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    out, lines = fd.run_checked(exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", schedule, tmp_path,
+                                inputs={"calls.txt": "\n".join(lines) + "\n", "pictures.bin": b"".join(p.tobytes() for _l, _g, p, _r, _s in items)})
     G, P, Rc, S = [], [], {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "G":
             G.append((f[1], int(f[2]), int(f[3])))

@@ -134,6 +134,28 @@ def run_driver(exe, scenario, env_extra, schedule, tmp_path):
     return r, out
 
 
+def run_checked(exe, scenario, schedule, tmp_path, extra=(), inputs=None, timeout=600):
+    """One scenario of a stand-alone driver under `schedule`: `inputs` (name -> text or bytes) are written into the out directory first,
+    `extra` follows the golden directory on the command line.  Passing: no sanitizer report, no fake_span abort, exit status 0.
+    -> (the out directory, the lines of results.txt)"""
+    out = tmp_path / "out"
+    out.mkdir()
+    for name, data in (inputs or {}).items():
+        (out / name).write_bytes(data) if isinstance(data, bytes) else (out / name).write_text(data)
+    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, scenario, str(out), GOLDEN] + [str(x) for x in extra], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=timeout)
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
+    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    return out, open(out / "results.txt").read().splitlines()
+
+
+def refusal_texts(lines):
+    """the E lines of a `refused` scenario: label -> the library's words, which run to the end of the line"""
+    return {f[1]: (f[2] if len(f) > 2 else "") for f in (line.split(" ", 2) for line in lines) if f[0] == "E"}
+
+
 def n_pics(name):
     return len(CLIPS[name]["frame_types"])
 

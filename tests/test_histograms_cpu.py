@@ -13,7 +13,6 @@
 """
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -305,15 +304,9 @@ def drivers():
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path)
     K, R, S = {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "H":
             label, name, aform, ak, bform, bk = f[1], f[2], f[3], int(f[4]), f[5], int(f[6])
@@ -325,10 +318,10 @@ def _run(exe, scenario, schedule, tmp_path):
             R[f[1]] = int(f[2])
         elif f[0] == "S":
             S[f[1]] = (int(f[2]), int(f[3]))
-    return K, R, S
+    return K, R, S, fd.refusal_texts(lines)
 
 
-def _check_goldens(K, R, S):
+def _check_goldens(K, R, S, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert len({_geometry(nm)[2:] for nm in SIX}) == 3                    # 4:2:0, 4:2:2 and 4:4:4
     assert K["goldens/values"] == [(nm, "pic", k, "none", 0) for nm in SIX for k in range(n[nm])]
@@ -342,7 +335,7 @@ def _check_goldens(K, R, S):
     assert R == {"goldens/n0": 0, "goldens/n0_absdiff": 0}
 
 
-def _check_memory(K, R, S):
+def _check_memory(K, R, S, E):
     na = fd.n_pics("yuv422_64x48")
     nm = "yuv422_64x48"
     assert K["memory/values"] == [x for k in range(na) for x in ((nm, "inv", k, "none", 0), (nm, "pic", k, "none", 0))] + [("ragged24x40", "inv", 1, "none", 0)]
@@ -351,7 +344,7 @@ def _check_memory(K, R, S):
     assert K["memory/diffs"] == want and K["memory/nullstream"] == want
 
 
-def _check_reuse(K, R, S):
+def _check_reuse(K, R, S, E):
     from hvqm4_amd._lib import HVQ_E_STATE
     n, ne = fd.n_pics("gop64x48_15"), fd.n_pics("yuv444_64x48")
     diffs = [("gop64x48_15", "pic", k, "pic", (k + 1) % n) for k in range(n)]
@@ -363,7 +356,44 @@ def _check_reuse(K, R, S):
     assert K["reuse/destroy"] == [("yuv444_64x48", "pic", k, "none", 0) for k in range(ne)]
 
 
-def _check_refused(K, R, S):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/null_context": "bad arguments",
+    "refused/null_context_absdiff": "bad arguments",
+    "refused/bad_mode": "bad mode 2",
+    "refused/negative_mode": "bad mode -1",
+    "refused/values_with_ref": "HVQ_HIST_VALUES takes no reference (ref must be NULL)",
+    "refused/absdiff_without_ref": "HVQ_HIST_ABSDIFF needs a reference for every picture (ref is NULL)",
+    "refused/absdiff_against_zeros": "reference 1: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)",
+    "refused/absdiff_against_zeros_ordinal": "reference 1: |a - 0| is a itself, HVQ_HIST_VALUES gives it (stream -1 needs a pointer)",
+    "refused/bad_stream": "bad stream 99",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/misaligned_src": "picture 1: the pointer must be a multiple of 16",
+    "refused/src_with_ordinal": "picture 1: a pointer together with ordinal 1 (the caller's memory takes ordinal -1)",
+    "refused/src_with_bad_stream": "bad stream 99",
+    "refused/minus_one_without_src": "stream 0: bad picture ordinal -1",
+    "refused/ref_bad_stream": "bad stream 99",
+    "refused/ref_below_minus_one": "reference 1: stream -2 (a stream, or -1 for the caller's memory)",
+    "refused/ref_bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/ref_pointer_with_stream": "reference 1: a pointer together with stream 0 (a resident reference takes no pointer)",
+    "refused/ref_misaligned": "reference 1: the pointer must be a multiple of 16",
+    "refused/ref_other_geometry": "reference 1: stream 1 (64 x 48, chroma shifts 1, 0) has not the geometry of stream 0 (64 x 48, 1, 1)",
+    "refused/null_out": "out must be a non-null multiple of 4",
+    "refused/misaligned_out": "out must be a non-null multiple of 4",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most (one grid row each)",
+    "refused/evicted": "stream 2 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/evicted_ref": "stream 2 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+    "refused/queued_ref": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0": "stream 0 picture 7 is queued but not flushed",
+}
+
+
+def _check_refused(K, R, S, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_STATE
     arg = ["null_context", "null_context_absdiff", "bad_mode", "negative_mode", "values_with_ref", "absdiff_without_ref", "absdiff_against_zeros",
            "absdiff_against_zeros_ordinal", "bad_stream", "bad_ordinal", "misaligned_src", "src_with_ordinal", "src_with_bad_stream",
@@ -386,8 +416,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "reuse": _check_re
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    K, R, S = _run(drivers[build], scenario, schedule, tmp_path)
-    CHECKS[scenario](K, R, S)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path))
 
 
 def test_the_existing_fake_builds_link_without_the_histogram_body():

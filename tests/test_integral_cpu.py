@@ -7,7 +7,6 @@ run plain and with ASan + UBSan as tests/test_distance_cpu.py builds its own; no
 sanitised run."""
 import json
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -235,24 +234,16 @@ def _inputs(scenario):
 
 
 def _run(exe, scenario, schedule, tmp_path, timeout=600):
-    out = tmp_path / "out"
-    out.mkdir()
     items, rects = _inputs(scenario)
     lines = []
     for _l, g, _p, plane, sq, r in items:
         r_ = r or I.Rule(plane)
         lines.append(f"P {g[0]} {g[1]} {g[2]} {g[3]} {plane} {sq} {int(r is not None)} {r_.mode} {r_.rx} {r_.ry} {r_.k} {r_.c} {r_.invert}")
     lines += ["R " + " ".join(str(v) for v in row) for row in rects.tolist()]
-    (out / "calls.txt").write_text("\n".join(lines) + "\n")
-    (out / "pictures.bin").write_bytes(b"".join(it[2].tobytes() for it in items))
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=timeout)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    out, lines = fd.run_checked(exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", schedule, tmp_path, timeout=timeout,
+                                inputs={"calls.txt": "\n".join(lines) + "\n", "pictures.bin": b"".join(it[2].tobytes() for it in items)})
     G, P, Rc, S = [], [], {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "G":
             G.append((f[1], int(f[2]), int(f[3])))

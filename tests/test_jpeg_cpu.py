@@ -22,7 +22,6 @@ import io
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -331,15 +330,9 @@ def drivers():
 
 
 def _run(exe, scenario, schedule, tmp_path, extra=()):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN] + [str(x) for x in extra], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path, extra)
     K, R, S, G, Q = {}, {}, {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "J":
             label, name, k, form, q, cap, length, hexed, same, tail = f[1], f[2], int(f[3]), f[4], int(f[5]), int(f[6]), int(f[7]), f[8], int(f[9]), int(f[10])
@@ -364,10 +357,10 @@ def _run(exe, scenario, schedule, tmp_path, extra=()):
     assert len(G) == 1
     same, total = next(iter(G.values()))
     assert same == total > 0, "a call wrote outside its destination or its lengths"
-    return K, R, S, Q
+    return K, R, S, Q, fd.refusal_texts(lines)
 
 
-def _check_goldens(K, R, S, Q):
+def _check_goldens(K, R, S, Q, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert K["goldens/q90"] == [(nm, k, "pic", True) for nm in SIX for k in range(n[nm])] and len(K["goldens/q90"]) > 20
     assert K["goldens/mixed"] == [(nm, (r * 2 + 1) % n[nm], "pic", True) for r in range(2) for nm in SIX], "files come back in call order"
@@ -376,7 +369,7 @@ def _check_goldens(K, R, S, Q):
     assert R == {"goldens/n0": 0}
 
 
-def _check_memory(K, R, S, Q):
+def _check_memory(K, R, S, Q, E):
     nm, na = "yuv422_64x48", fd.n_pics("yuv422_64x48")
     want = [x for k in range(na) for x in ((nm, (k + 1) % na, "mem", True), (nm, k, "pic", True))]
     want += [("ragged24x40", 1, "mem", True), ("ragged24x40", 2, "pic", True)]
@@ -387,14 +380,53 @@ def _overflow_lengths():
     return [len(_expected("gop64x48_15", k, 90)) for k in range(4)]
 
 
-def _check_overflow(K, R, S, Q):
+def _check_overflow(K, R, S, Q, E):
     nm = "gop64x48_15"
     assert K["overflow/short"] == [(nm, 0, "pic", True), (nm, 1, "pic", False), (nm, 2, "pic", True), (nm, 3, "pic", True)]
     assert K["overflow/tiny"] == [(nm, k, "pic", False) for k in range(4)] and min(_overflow_lengths()) > 631
     assert K["overflow/again"] == [(nm, k, "pic", True) for k in range(4)]
 
 
-def _check_refused(K, R, S, Q):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/null_context": "bad arguments",
+    "refused/quality_0": "quality 0 outside [1, 100]",
+    "refused/quality_101": "quality 101 outside [1, 100]",
+    "refused/quality_negative": "quality -5 outside [1, 100]",
+    "refused/null_out": "out or cap is NULL",
+    "refused/null_cap": "out or cap is NULL",
+    "refused/null_lengths": "lengths must be a non-null multiple of 8",
+    "refused/misaligned_lengths": "lengths must be a non-null multiple of 8",
+    "refused/null_destination": "file 1: the pointer must be a non-null multiple of 16",
+    "refused/misaligned_destination": "file 1: the pointer must be a non-null multiple of 16",
+    "refused/cap_630": "file 1: 630 bytes hold not even the header and EOI (631)",
+    "refused/cap_0": "file 1: 0 bytes hold not even the header and EOI (631)",
+    "refused/bad_stream": "bad stream 99",
+    "refused/negative_stream": "bad stream -1",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/negative_ordinal": "stream 0: bad picture ordinal -1",
+    "refused/src_with_ordinal": "picture 1: a pointer together with ordinal 1 (the caller's memory takes ordinal -1)",
+    "refused/src_misaligned": "picture 1: the pointer must be a multiple of 16",
+    "refused/src_bad_stream": "bad stream 99",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most (one grid row each)",
+    "refused/evicted": "stream 1 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0_bad_quality": "quality 0 outside [1, 100]",
+    "header/ok": "quality 0 outside [1, 100]",
+    "header/no_len": "quality 0 outside [1, 100]",
+    "header/short": "the header takes 629 bytes",
+    "header/null": "the header takes 629 bytes",
+    "header/quality": "quality 0 outside [1, 100]",
+    "header/geometry": "unsupported geometry 60x48 sampling 2x2",
+}
+
+
+def _check_refused(K, R, S, Q, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd import jpeg
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_GEOMETRY, HVQ_E_STATE
     arg = ["null_context", "quality_0", "quality_101", "quality_negative", "null_out", "null_cap", "null_lengths", "misaligned_lengths", "null_destination",
@@ -411,7 +443,7 @@ def _check_refused(K, R, S, Q):
     assert K["refused/then_ok"] == [("gop64x48_15", 1, "pic", True), ("gop64x48_15", last, "pic", True)]
 
 
-def _check_helpers(K, R, S, Q):
+def _check_helpers(K, R, S, Q, E):
     """the division helper against `/` for every numerator up to 1278 (|F| <= 1151 and Q >> 1 <= 127 lie below) and every Q in 1 .. 255"""
     assert R["helpers/div_max"] >= 1151 + 127 and R["helpers/tried"] == 255 * (R["helpers/div_max"] + 1)
     assert R["helpers/div_mismatches"] == 0 and R["helpers/quantise_mismatches"] == 0
@@ -426,8 +458,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "overflow": _check
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    K, R, S, Q = _run(drivers[build], scenario, schedule, tmp_path, _overflow_lengths() if scenario == "overflow" else ())
-    CHECKS[scenario](K, R, S, Q)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path, _overflow_lengths() if scenario == "overflow" else ()))
 
 
 @pytest.mark.parametrize("build", list(fd.BUILDS))

@@ -5,7 +5,6 @@ with the functions of hvq_label.h) are compared with it by ==.  The fake-device 
 with ASan + UBSan as tests/test_map_cpu.py builds its own; nothing is preloaded and no Python is involved in the sanitised run."""
 import json
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -228,21 +227,13 @@ def _inputs(scenario):
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
     cap, items = _inputs(scenario)
     lines = [f"cap {cap}"] + [f"S {s.area_min} {s.area_max} {s.w_min} {s.w_max} {s.h_min} {s.h_max} {s.invert}" for s in cases.SELECTS]
     lines += [f"P {g[0]} {g[1]} {g[2]} {g[3]} {r.plane} {r.lo} {r.hi} {r.connectivity} {s}" for _l, g, _p, r, s in items]
-    (out / "calls.txt").write_text("\n".join(lines) + "\n")
-    (out / "pictures.bin").write_bytes(b"".join(p.tobytes() for _l, _g, p, _r, _s in items))
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    out, lines = fd.run_checked(exe, scenario if scenario in ("resident", "refused", "nogpu") else "cases", schedule, tmp_path,
+                                inputs={"calls.txt": "\n".join(lines) + "\n", "pictures.bin": b"".join(p.tobytes() for _l, _g, p, _r, _s in items)})
     G, P, Rc, S = [], [], {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "G":
             G.append((f[1], int(f[2]), int(f[3])))

@@ -6,7 +6,6 @@ and no Python is involved in the sanitised run."""
 import hashlib
 import json
 import os
-import subprocess
 import sys
 import zlib
 
@@ -396,17 +395,9 @@ def _expected(source, form, k, geom, table, planes, produced):
 
 
 def _run(exe, scenario, schedule, tmp_path, records):
-    out = tmp_path / "out"
-    out.mkdir()
-    (out / "rules.txt").write_text("".join(f"{n} {r.luma.kind} {r.luma.a} {r.luma.b} {r.luma.pad} {r.chroma.kind} {r.chroma.a} {r.chroma.b} {r.chroma.pad}\n"
-                                           for n, r in cases.RULES.items()))
-    (out / "tables.bin").write_bytes(M.pack(_TABLES).tobytes())
-    (out / "records.bin").write_bytes(records[0].astype("<u4").tobytes())
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    rules = "".join(f"{n} {r.luma.kind} {r.luma.a} {r.luma.b} {r.luma.pad} {r.chroma.kind} {r.chroma.a} {r.chroma.b} {r.chroma.pad}\n" for n, r in cases.RULES.items())
+    out, lines = fd.run_checked(exe, scenario, schedule, tmp_path,
+                                inputs={"rules.txt": rules, "tables.bin": M.pack(_TABLES).tobytes(), "records.bin": records[0].astype("<u4").tobytes()})
     produced = None
     if scenario == "tables":                                                   # == the expected tables first: the pictures then go through them
         produced = np.frombuffer((out / "tables_out.bin").read_bytes(), dtype=np.uint8).reshape(-1, 3, 256)
@@ -415,7 +406,7 @@ def _run(exe, scenario, schedule, tmp_path, records):
         bad = np.flatnonzero((produced != want).any(axis=(1, 2)))
         assert not bad.size, f"record {bad[0] // len(cases.RULES)} through rule {list(cases.RULES)[bad[0] % len(cases.RULES)]}: {bad.size} tables differ"
     P, Rc, S = {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "P":
             label, source, form, k, geom, table, planes = f[1], f[2], f[3], int(f[4]), tuple(int(v) for v in f[5:9]), f[9], int(f[10])

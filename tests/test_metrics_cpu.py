@@ -10,7 +10,6 @@
 """
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -190,15 +189,9 @@ def _expected(clip_a, ka, form, clip_b, kb):
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path)
     M, R, S = {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "M":
             label, clip_a, ka, form, clip_b, kb = f[1], f[2], int(f[3]), f[4], f[5], int(f[6])
@@ -210,10 +203,10 @@ def _run(exe, scenario, schedule, tmp_path):
             R[f[1]] = int(f[2])
         elif f[0] == "S":
             S[f[1]] = (int(f[2]), int(f[3]))
-    return M, R, S
+    return M, R, S, fd.refusal_texts(lines)
 
 
-def _check_goldens(M, R, S):
+def _check_goldens(M, R, S, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert len({_geometry(nm)[2:] for nm in SIX}) == 3                    # 4:2:0, 4:2:2 and 4:4:4
     assert sorted(M["goldens/clip"]) == sorted(
@@ -226,7 +219,7 @@ def _check_goldens(M, R, S):
     assert M["goldens/one"] == [("yuv422_296x160", 1, "pic", "yuv422_296x160", 0)]
 
 
-def _check_memory(M, R, S):
+def _check_memory(M, R, S, E):
     na = fd.n_pics("yuv422_64x48")
     for label in ("memory", "memory/nullstream"):
         assert sorted(M[label]) == sorted(
@@ -235,7 +228,7 @@ def _check_memory(M, R, S):
             [("ragged24x40", 1, "inv", "ragged24x40", 0), ("ragged24x40", 1, "zeros", "-", 0)])
 
 
-def _check_reuse(M, R, S):
+def _check_reuse(M, R, S, E):
     from hvqm4_amd._lib import HVQ_E_STATE
     n, ne = fd.n_pics("gop64x48_15"), fd.n_pics("yuv444_64x48")
     assert sorted(M["reuse"]) == sorted([("gop64x48_15", k, "pic", "gop64x48_15", (k + 1) % n) for k in range(n)] +
@@ -245,7 +238,30 @@ def _check_reuse(M, R, S):
     assert M["reuse/destroy"] == [("yuv444_64x48", k, "zeros", "-", 0) for k in range(ne)]
 
 
-def _check_refused(M, R, S):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/geometry": "reference 1: stream 1 (64 x 48, chroma shifts 1, 0) has not the geometry of stream 0 (64 x 48, 1, 1)",
+    "refused/ptr_with_stream": "reference 1: a pointer together with stream 0 (a resident reference takes no pointer)",
+    "refused/misaligned_ptr": "reference 1: the pointer must be a multiple of 16",
+    "refused/bad_stream": "bad stream 99",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/bad_ref_stream": "bad stream 99",
+    "refused/bad_ref_ordinal": "stream 0: bad picture ordinal -1",
+    "refused/ref_stream_below_minus_one": "reference 1: stream -2 (a stream, or -1 for the caller's memory or zeros)",
+    "refused/null_out": "out must be a non-null multiple of 8",
+    "refused/misaligned_out": "out must be a non-null multiple of 8",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most (one grid row each)",
+    "refused/evicted": "stream 2 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/evicted_ref": "stream 2 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+}
+
+
+def _check_refused(M, R, S, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_STATE
     want = {"geometry": HVQ_E_ARG, "ptr_with_stream": HVQ_E_ARG, "misaligned_ptr": HVQ_E_ARG, "bad_stream": HVQ_E_ARG, "bad_ordinal": HVQ_E_ARG,
             "bad_ref_stream": HVQ_E_ARG, "bad_ref_ordinal": HVQ_E_ARG, "ref_stream_below_minus_one": HVQ_E_ARG, "null_out": HVQ_E_ARG,
@@ -263,8 +279,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "reuse": _check_re
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    M, R, S = _run(drivers[build], scenario, schedule, tmp_path)
-    CHECKS[scenario](M, R, S)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path))
 
 
 def test_the_existing_fake_build_links_without_the_metrics_body():

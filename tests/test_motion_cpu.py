@@ -13,7 +13,6 @@
 """
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -292,15 +291,9 @@ def drivers():
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path)
     K, R, S, G = {}, {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "F":
             label, name, ak, bform, bk, B, Rad, rows, cols = f[1], f[2], int(f[3]), f[4], int(f[5]), int(f[6]), int(f[7]), int(f[8]), int(f[9])
@@ -318,10 +311,10 @@ def _run(exe, scenario, schedule, tmp_path):
     assert len(G) == 1
     same, total = next(iter(G.values()))
     assert same == total > 0, "a call wrote outside its field"
-    return K, R, S
+    return K, R, S, fd.refusal_texts(lines)
 
 
-def _check_goldens(K, R, S):
+def _check_goldens(K, R, S, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert len({_geometry(nm)[2:] for nm in SIX}) == 3                    # 4:2:0, 4:2:2 and 4:4:4
     prev = [(nm, k, "pic", k - 1) for nm in SIX for k in range(1, n[nm])]
@@ -334,7 +327,7 @@ def _check_goldens(K, R, S):
     assert R == {"goldens/n0": 0}
 
 
-def _check_memory(K, R, S):
+def _check_memory(K, R, S, E):
     nm, na = "yuv422_64x48", fd.n_pics("yuv422_64x48")
     want = [x for k in range(na) for x in ((nm, k, "mem", (k + 1) % na), (nm, k, "pic", (k + 2) % na))]
     want += [("ragged24x40", 0, "mem", 1), ("ragged24x40", 2, "pic", 1)]
@@ -343,7 +336,7 @@ def _check_memory(K, R, S):
     assert not f[..., :2].any() and (f[..., 2] == f[..., 3]).all(), "R = 0: cost is cost_zero"
 
 
-def _check_reuse(K, R, S):
+def _check_reuse(K, R, S, E):
     from hvqm4_amd._lib import HVQ_E_STATE
     n, ne = fd.n_pics("gop64x48_15"), fd.n_pics("yuv444_64x48")
     first = [("gop64x48_15", k, "pic", (k + 1) % n) for k in range(n)]
@@ -355,7 +348,53 @@ def _check_reuse(K, R, S):
     assert K["reuse/destroy"] == [("yuv444_64x48", k, "pic", k - 1) for k in range(1, ne)]
 
 
-def _check_refused(K, R, S):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/null_context": "bad arguments",
+    "refused/block_4": "block 4 (8 or 16)",
+    "refused/block_0": "block 0 (8 or 16)",
+    "refused/block_32": "block 32 (8 or 16)",
+    "refused/block_12": "block 12 (8 or 16)",
+    "refused/radius_16": "radius 16 outside [0, 15]",
+    "refused/radius_negative": "radius -1 outside [0, 15]",
+    "refused/block_16_does_not_tile": "picture 1: blocks of 16 do not tile stream 2 (24 x 40)",
+    "refused/without_ref": "motion needs a reference for every picture (ref is NULL)",
+    "refused/against_zeros": "reference 1: motion against a picture of zeros means nothing (stream -1 needs a pointer)",
+    "refused/against_zeros_ordinal": "reference 1: motion against a picture of zeros means nothing (stream -1 needs a pointer)",
+    "refused/bad_stream": "bad stream 99",
+    "refused/negative_stream": "bad stream -1",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/negative_ordinal": "stream 0: bad picture ordinal -1",
+    "refused/ref_bad_stream": "bad stream 99",
+    "refused/ref_below_minus_one": "reference 1: stream -2 (a stream, or -1 for the caller's memory)",
+    "refused/ref_bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/ref_pointer_with_stream": "reference 1: a pointer together with stream 0 (a resident reference takes no pointer)",
+    "refused/ref_misaligned": "reference 1: the pointer must be a multiple of 16",
+    "refused/ref_other_sampling": "reference 1: stream 1 (64 x 48, chroma shifts 1, 0) has not the geometry of stream 0 (64 x 48, 1, 1)",
+    "refused/ref_other_size": "reference 1: stream 2 (24 x 40, chroma shifts 1, 1) has not the geometry of stream 0 (64 x 48, 1, 1)",
+    "refused/null_out": "out is NULL",
+    "refused/null_field": "field 1: the pointer must be a non-null multiple of 16",
+    "refused/misaligned_field": "field 1: the pointer must be a non-null multiple of 16",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most (one grid row each)",
+    "refused/evicted": "stream 3 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/evicted_ref": "stream 3 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+    "refused/queued_ref": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0_bad_block": "block 7 (8 or 16)",
+    "blocks/64x48_8": "block 7 (8 or 16)",
+    "blocks/64x48_16": "block 7 (8 or 16)",
+    "blocks/24x40_16": "blocks of 16 do not tile a 24 x 40 picture",
+    "blocks/64x48_12": "block 12 (8 or 16)",
+    "blocks/geometry": "unsupported geometry 60x48 sampling 2x2",
+}
+
+
+def _check_refused(K, R, S, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_GEOMETRY, HVQ_E_STATE
     arg = ["null_context", "block_4", "block_0", "block_32", "block_12", "radius_16", "radius_negative", "block_16_does_not_tile", "without_ref",
            "against_zeros", "against_zeros_ordinal", "bad_stream", "negative_stream", "bad_ordinal", "negative_ordinal", "ref_bad_stream",
@@ -380,8 +419,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "reuse": _check_re
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    K, R, S = _run(drivers[build], scenario, schedule, tmp_path)
-    CHECKS[scenario](K, R, S)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path))
 
 
 def test_the_existing_fake_builds_link_without_the_motion_body():

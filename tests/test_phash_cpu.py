@@ -17,7 +17,6 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -300,15 +299,9 @@ def _expected(name, k, form="pic"):
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path)
     K, R, S, N = {}, {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "H":
             label, name, k, form = f[1], f[2], int(f[3]), f[4]
@@ -326,10 +319,10 @@ def _run(exe, scenario, schedule, tmp_path):
             N[f[1]]["A"] = (int(f[2]), int(f[3]))
         elif f[0] == "N":
             N.setdefault(f[1], {"Q": [], "D": [], "N": []})["N"].append([int(v) for v in f[3:]])
-    return K, R, S, N
+    return K, R, S, N, fd.refusal_texts(lines)
 
 
-def _check_goldens(K, R, S, N):
+def _check_goldens(K, R, S, N, E):
     n = {nm: fd.n_pics(nm) for nm in SIX}
     assert K["goldens/clip"] == [(nm, k, "pic") for nm in SIX for k in range(n[nm])]
     assert K["goldens/clip"] and all(fixture_record(nm, k) == _expected(nm, k) for nm, k, _f in K["goldens/clip"])
@@ -339,13 +332,13 @@ def _check_goldens(K, R, S, N):
     assert {_geometry(nm)[0] % 16 for nm in SIX} == {0, 8}, "rows of 16-byte and of 8-byte units"
 
 
-def _check_memory(K, R, S, N):
+def _check_memory(K, R, S, N, E):
     na = fd.n_pics("yuv422_64x48")
     want = [x for k in range(na) for x in (("yuv422_64x48", k, "inv"), ("yuv422_64x48", k, "pic"))] + [("ragged24x40", 1, "inv"), ("ragged24x40", 1, "pic")]
     assert K["memory"] == want and K["memory/nullstream"] == want
 
 
-def _check_reuse(K, R, S, N):
+def _check_reuse(K, R, S, N, E):
     from hvqm4_amd._lib import HVQ_E_STATE
     n, ne = fd.n_pics("gop64x48_15"), fd.n_pics("yuv444_64x48")
     assert K["reuse"] == [("gop64x48_15", k, "pic") for k in range(n)]
@@ -354,7 +347,7 @@ def _check_reuse(K, R, S, N):
     assert K["reuse/destroy"] == [("yuv444_64x48", k, "pic") for k in range(ne)]
 
 
-def _check_backtoback(K, R, S, N):
+def _check_backtoback(K, R, S, N, E):
     small = [("wide296x160", k, "pic") for k in range(2)]
     large = ([("gop64x48_15", k, "pic") for k in range(fd.n_pics("gop64x48_15"))] + [("wide296x160", k, "pic") for k in range(fd.n_pics("wide296x160"))]) * 6
     assert K["backtoback/small"] == small == K["backtoback/again"]
@@ -362,7 +355,43 @@ def _check_backtoback(K, R, S, N):
     assert len(large) > 2 * 2 * len(small), "the cells (twice the first call's at first) had to grow with the small call queued"
 
 
-def _check_refused(K, R, S, N):
+# what hvq_last_error_string() said after each call of `refused`, recorded from the runtime before the record frame: the
+# order of the checks and their words are part of the interface.  A call that succeeds leaves the words of the refusal before it.
+REFUSAL_TEXTS = {
+    "refused/null_context": "bad arguments",
+    "refused/bad_stream": "bad stream 99",
+    "refused/bad_ordinal": "stream 0: bad picture ordinal 1000",
+    "refused/misaligned_src": "picture 1: the pointer must be a multiple of 16",
+    "refused/src_with_ordinal": "picture 1: a pointer together with ordinal 1 (the caller's memory takes ordinal -1)",
+    "refused/src_with_bad_stream": "bad stream 99",
+    "refused/minus_one_without_src": "stream 0: bad picture ordinal -1",
+    "refused/null_out": "out must be a non-null multiple of 8",
+    "refused/misaligned_out": "out must be a non-null multiple of 8",
+    "refused/too_many": "65536 pictures: one call takes 65535 at the most",
+    "refused/evicted": "stream 1 picture 0 is no longer resident (slot reused, or the picture was dropped)",
+    "refused/queued": "stream 0 picture 7 is queued but not flushed",
+    "refused/n0": "stream 0 picture 7 is queued but not flushed",
+    "refused/near_null_context": "bad arguments",
+    "refused/near_null_q": "q must be a non-null multiple of 8",
+    "refused/near_misaligned_q": "q must be a non-null multiple of 8",
+    "refused/near_null_db": "db must be a non-null multiple of 8",
+    "refused/near_misaligned_db": "db must be a non-null multiple of 8",
+    "refused/near_null_out": "out must be a non-null multiple of 16",
+    "refused/near_misaligned_out": "out must be a non-null multiple of 16",
+    "refused/near_q_stride0": "strides 0 and 1: a stride counts 64-bit words and is at least 1",
+    "refused/near_db_stride_negative": "strides 1 and -1: a stride counts 64-bit words and is at least 1",
+    "refused/near_threshold65": "threshold 65 outside [0, 64]",
+    "refused/near_threshold_negative": "threshold -1 outside [0, 64]",
+    "refused/near_nq_negative": "-1 queries against 4 hashes: each count lies in [0, 16777216]",
+    "refused/near_nq_too_many": "16777217 queries against 4 hashes: each count lies in [0, 16777216]",
+    "refused/near_ndb_too_many": "4 queries against 16777217 hashes: each count lies in [0, 16777216]",
+}
+
+
+def _check_refused(K, R, S, N, E):
+    for label, text in REFUSAL_TEXTS.items():
+        assert E.get(label) == text, (label, E.get(label))
+    assert set(E) == set(REFUSAL_TEXTS)
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_STATE
     want = {"null_context": HVQ_E_ARG, "bad_stream": HVQ_E_ARG, "bad_ordinal": HVQ_E_ARG, "misaligned_src": HVQ_E_ARG, "src_with_ordinal": HVQ_E_ARG,
             "src_with_bad_stream": HVQ_E_ARG, "minus_one_without_src": HVQ_E_ARG, "null_out": HVQ_E_ARG, "misaligned_out": HVQ_E_ARG,
@@ -376,7 +405,7 @@ def _check_refused(K, R, S, N):
     assert K["refused/then_ok"] == [("gop64x48_15", 1, "pic"), ("gop64x48_15", fd.n_pics("gop64x48_15") - 1, "pic")]
 
 
-def _check_nearest(K, R, S, N):
+def _check_nearest(K, R, S, N, E):
     labels = ["all", "strides_thr0", "thr64", "inplace", "block", "offset_beyond", "ndb0", "one", "big", "big_block", "big_inplace"]
     assert R == {"nearest/nq0": 0}
     for lb in labels:
@@ -407,8 +436,7 @@ CHECKS = {"goldens": _check_goldens, "memory": _check_memory, "reuse": _check_re
 @pytest.mark.parametrize("build", list(fd.BUILDS))
 @pytest.mark.parametrize("scenario", list(CHECKS))
 def test_fake_device_scenario(drivers, scenario, build, schedule, tmp_path):
-    K, R, S, N = _run(drivers[build], scenario, schedule, tmp_path)
-    CHECKS[scenario](K, R, S, N)
+    CHECKS[scenario](*_run(drivers[build], scenario, schedule, tmp_path))
 
 
 def test_the_existing_fake_builds_link_without_the_hash_bodies():

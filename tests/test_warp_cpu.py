@@ -6,7 +6,6 @@ in the sanitised run."""
 import hashlib
 import json
 import os
-import subprocess
 import zlib
 from fractions import Fraction
 
@@ -442,16 +441,9 @@ def _expected(source, form, k, geom, wname):
 
 
 def _run(exe, scenario, schedule, tmp_path):
-    out = tmp_path / "out"
-    out.mkdir()
-    (out / "warps.txt").write_text(_warps_txt())
-    env = dict(os.environ, FAKEHIP_SCHEDULE=schedule, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scenario, str(out), fd.GOLDEN], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "fake_span" not in r.stderr and "fakehip:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    _, lines = fd.run_checked(exe, scenario, schedule, tmp_path, inputs={"warps.txt": _warps_txt()})
     P, R, S = {}, {}, {}
-    for line in open(out / "results.txt").read().splitlines():
+    for line in lines:
         f = line.split()
         if f[0] == "P":
             label, source, form, k, geom, wname, tg = f[1], f[2], f[3], int(f[4]), tuple(int(v) for v in f[5:9]), f[9], tuple(int(v) for v in f[10:14])
