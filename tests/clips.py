@@ -72,11 +72,38 @@ MEDIUM = [
     # map flat (h4m:1169), so it reads border values and the next row's first entries -- deterministic, reproduced exactly
     ("nest_border1_320x240", SynthConfig(width=320, height=240, gop="IPB", seed=24, nest_overhang=1)),
     ("nest_border2_296x160", SynthConfig(width=296, height=160, gop="IPB", seed=25, nest_overhang=2)),
-    # up to 14 bases per MC-residual block, nearly every block coded: tiles with more (item, basis) pairs than a pair list holds
-    # (1024) -- their items walk their bases themselves
+    # up to 14 bases per MC-residual block, nearly every block coded: the fullest tiles of the catalogue (208 items, 1018 pairs) -- still
+    # inside a pair list (4096 pairs): the serial pair phase is reached only through HVQM4_AMD_PAIR_CAP (tests/test_gpu_modes.py)
     ("manybases320x240", SynthConfig(width=320, height=240, gop="IPB", seed=41, max_predi_bases=14, p_zero=0.02, p_proc1=0.0, literal_weight=0.1)),
     ("pselfref320x240", SynthConfig(width=320, height=240, gop="IPBBPBBP", seed=39, p_future_refs=True)),
 ]
+
+# One picture per launch (gop "IPB"), small and dense: together with manybases320x240 they launch each of the fourteen instantiations of
+# hvq_recon_inline_kernel with an I, a P and a B picture as the fullest (tests/test_launch_coverage.py; the items of the fullest tile of
+# the I, P and B picture behind each clip).  128 x 64 in 4:2:0 is two luma tiles and one per chroma plane, 96 x 96 three luma tiles: a
+# two-tile workgroup with one tile in every clip.
+def _shape(w, h, p_zero, bases, seed, sampling="420"):
+    return (f"shape{sampling}_{w}x{h}_z{int(round(100 * p_zero)):02d}_b{bases}_s{seed}",
+            SynthConfig(width=w, height=h, gop="IPB", seed=seed, sampling=sampling, max_predi_bases=bases, p_proc1=0.0, literal_weight=0.0, p_zero=p_zero))
+
+
+SHAPES = [
+    _shape(128, 64, 0.06, 14, 52, "444"),   # 180 121 128
+    _shape(128, 64, 0.14, 6, 51, "422"),    # 128  74  90
+    _shape(96, 96, 0.2, 6, 51),             #  98  99  64
+    _shape(96, 96, 0.3, 14, 52),            #  82  64  45
+    _shape(128, 64, 0.5, 6, 51),            #  24  40  27
+    _shape(128, 64, 0.2, 6, 52),            # 110  82  72
+    _shape(128, 64, 0.4, 6, 51),            #  36  31  40
+    _shape(128, 64, 0.0, 6, 52),            # 216 165 196
+    _shape(128, 64, 0.06, 6, 51),           # 163 117 100
+    _shape(128, 64, 0.3, 6, 51),            #  63  66  43
+    _shape(96, 96, 0.0, 6, 51),             # 219 208 137
+    _shape(128, 64, 0.3, 6, 51, "444"),     #  76  56  55
+]
+
+# what the parity suites decode on the GPU and compare with the oracle, picture by picture
+PARITY = SMALL + MEDIUM + REGRESSION + SHAPES
 
 # config C4 -- the per-GPU share at 8 GPUs: clips 0, 8, ..., 56 of the 64 (4 x 320x240 + 4 x 640x480, HVQM4 1.3
 # and 1.5 alternating, seed = clip number), one 16-picture GOP each here (bench.py plays the GOP four times)

@@ -81,6 +81,47 @@ def histogram(clip) -> Counter:
     return h
 
 
+TILE_FIRST_AT, MAX_ITEMS_AT, MAX_PAIRS_AT = 84, 108, 112          # HvqPicHeader (hvq_desc.h): u32 tile_first[4], u16 max_items, u32 max_pairs
+
+
+def fullest_tile(hdr: bytes):
+    """(max_items, max_pairs) of a blob header: what sizes the launch of hvq_recon_inline_kernel the picture rides in"""
+    return struct.unpack_from("<H", hdr, MAX_ITEMS_AT)[0], struct.unpack_from("<I", hdr, MAX_PAIRS_AT)[0]
+
+
+def launch_inputs(clip):
+    """per picture of `clip` (host parser, CPU): (picture kind "I" | "P" | "B", max_items, max_pairs, tiles of plane Y, U, V)"""
+    from hvqm4_amd._lib import lib
+    l = lib()
+    prs = l.hvq_parser_create(clip.width, clip.height, clip.samp_h, clip.samp_v, 1 if clip.version == "1.5" else 0)
+    bound = l.hvq_parser_blob_bound(prs)
+    blob = np.zeros(bound, dtype=np.uint8)
+    out = []
+    for ft, pic in zip(clip.kinds, clip.pictures):
+        n = C.c_size_t(0)
+        rc = l.hvq_parse_picture(prs, ft, pic + b"\0" * 8, len(pic), blob.ctypes.data, bound, C.byref(n))
+        assert rc == 0, rc
+        hdr = blob[:128].tobytes()
+        tf = struct.unpack_from("<4I", hdr, TILE_FIRST_AT)
+        out.append((PIC[ft],) + fullest_tile(hdr) + (tuple(tf[k + 1] - tf[k] for k in range(3)),))
+    l.hvq_parser_destroy(prs)
+    return out
+
+
+def levels(kinds):
+    """Dependency level of every picture of one stream submitted whole and flushed once, with a slot per picture (hvq_runtime.cpp,
+    enqueue_common: no slot is reused, so only the references count): an I picture has none, a P picture follows the anchor before it,
+    a B picture the two anchors before it.  One launch reconstructs one level, so the I pictures of all GOPs share level 0."""
+    out, anchors = [], []
+    for k in kinds:
+        k = PIC.get(k, k)
+        lvl = 0 if k == "I" else anchors[-1] + 1 if k == "P" else max(anchors[-2:]) + 1
+        if k != "B":
+            anchors.append(lvl)
+        out.append(lvl)
+    return out
+
+
 def required_cells():
     """every cell a legal stream can hit and the path treats differently"""
     cells = []

@@ -37,7 +37,7 @@ def main():
     out = {"generator": "tests/golden/make_checksums.py",
            "what": "per clip and picture (decode order): crc32 of Y, U, V, picture, adler32 of Y, U, V, picture (zlib) of the reference's picture",
            "clips": {}}
-    catalogue = {name: (name, cfg) for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE}
+    catalogue = {name: (name, cfg) for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE + clips.SHAPES}
     for name, entry in manifest["clips"].items():
         clip = clips.get(catalogue[name])
         assert hashlib.sha256(clip.data).hexdigest() == entry["clip_sha256"], name

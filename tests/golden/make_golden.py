@@ -5,7 +5,7 @@ Runs only in the build container (needs oracle/_ref/libh4mref.so, i.e. /root/ref
 clip of tests/clips.py it stores the expected output of the reference (Tilka/hvqm4
 h4m_audio_decode.c, compiled by oracle/Makefile):
   - small clips: the .h4m bytes (synthetic, produced by hvqm4_amd/synth.py) + SHA-256 per picture
-  - medium clips: SHA-256 of the clip bytes (guards against generator drift) + SHA-256 per picture
+  - medium and shape clips: SHA-256 of the clip bytes (guards against generator drift) + SHA-256 per picture
   - small clips: where the reference's 20 bit-buffer cursors stop after every picture (ref_cursors.json)
 The fixtures are data (inputs and expected outputs), not reference source.
 """
@@ -29,7 +29,7 @@ def main():
                 "clips": {}}
     cursors = {"generator": "tests/golden/make_golden.py", "what": "probe of ref_decode_clip: per picture, the byte offset at which "
                "each of the reference's 20 bit-buffer cursors stops (-1: empty section)", "clips": {}}
-    for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE:
+    for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE + clips.SHAPES:
         clip = clips.get((name, cfg))
         pics, probe = bridge.ref_decode(clip.data, clip.n_pictures, probe=True)
         entry = {
@@ -38,7 +38,7 @@ def main():
             "clip_sha256": hashlib.sha256(clip.data).hexdigest(),
             "picture_sha256": [hashlib.sha256(p.tobytes()).hexdigest() for p in pics],
         }
-        if clip.width * clip.height <= 128 * 96 and clip.samp == 2 and clip.samp_v == 2:
+        if clip.width * clip.height <= 128 * 96 and clip.samp == 2 and clip.samp_v == 2 and (name, cfg) not in clips.SHAPES:
             # display epilogue: RGB of every picture through the reference's own dumpRGB (h4m:901-926)
             entry["rgb_sha256"] = [hashlib.sha256(bridge.ref_rgb(p, clip.width, clip.height).tobytes()).hexdigest() for p in pics]
         if (name, cfg) in clips.SMALL:

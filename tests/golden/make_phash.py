@@ -28,7 +28,7 @@ def main():
     out = {"generator": "tests/golden/make_phash.py",
            "what": "per clip and picture (decode order): ahash, dhash, phash (16 hex digits each) and sum_y of the reference's picture, by tests/phash_ref.py",
            "clips": {}}
-    catalogue = {name: (name, cfg) for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE}
+    catalogue = {name: (name, cfg) for name, cfg in clips.SMALL + clips.MEDIUM + clips.C4_SHARE + clips.SHAPES}
     for name, entry in manifest["clips"].items():
         clip = clips.get(catalogue[name])
         assert hashlib.sha256(clip.data).hexdigest() == entry["clip_sha256"], name

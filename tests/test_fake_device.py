@@ -22,6 +22,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.test_recon_plan import L, plan  # noqa: F401 -- L is the fixture: the library with hvq_recon_inline_plan declared
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NATIVE = os.path.join(HERE, "native")
@@ -251,6 +253,36 @@ def test_the_clips_scenarios_cover_every_clip_of_the_manifest(drivers, tmp_path)
             r, out = run_driver(drivers["plain"], scenario, {}, "late", d)
             _clips_seen[scenario] = check_run(r, out, scenario)
     assert sorted(_clips_seen["clips0"] + _clips_seen["clips1"]) == sorted(CLIPS)
+
+
+def test_flush_timing_lines_say_what_the_plan_says(drivers, L, tmp_path):
+    """tests/test_gpu_shapes.py reads which instantiation a launch took off the runtime's HVQM4_AMD_FLUSH_TIMING lines.  Pinned here without
+    a GPU: the `seven` scenario flushes seven golden clips one after the other, so flush k holds one launch per dependency level of clip k
+    (coverage.levels) -- every line must match the expression that test imports and say what hvq_recon_inline_plan says for the fullest
+    tile of the level's blob headers."""
+    from tests import clips, coverage
+    from tests.test_gpu_shapes import launch_lines
+    r, out = run_driver(drivers["plain"], "seven", {"HVQM4_AMD_FLUSH_TIMING": "1"}, "eager", tmp_path)
+    check_run(r, out, "seven")
+    flushes, lines = [], []
+    for line in r.stderr.splitlines():
+        lines.append(line)
+        if line.startswith("flush_end "):
+            flushes.append(launch_lines("\n".join(lines)))
+            lines = []
+    assert len(flushes) == len(SEVEN)
+    small = dict(clips.SMALL)
+    for name, got in zip(SEVEN, flushes):
+        clip = clips.get((name, small[name]))
+        pics, lv = coverage.launch_inputs(clip), coverage.levels(clip.kinds)
+        want = []
+        for level in sorted(set(lv)):
+            mi = max(p[1] for p, l in zip(pics, lv) if l == level)
+            mp = max(p[2] for p, l in zip(pics, lv) if l == level)
+            p = plan(L, mi, mp)
+            want.append(dict(launch=len(want), level=level, queue=0, max_items=mi, max_pairs=mp, tpw=p["tpw"], items=p["items"], pairs=p["pairs"],
+                             pool=p["pool"], lds=p["lds"], workgroups=L.hvq_recon_inline_residency(p["tpw"], p["items"], p["lds"])))
+        assert got == want, name
 
 
 def test_fake_helpers_equal_the_librarys():

@@ -18,7 +18,7 @@ def gpu_ctx():
     ctx.close()
 
 
-@pytest.mark.parametrize("case", clips.SMALL + clips.MEDIUM + clips.REGRESSION, ids=lambda c: c[0])
+@pytest.mark.parametrize("case", clips.PARITY, ids=lambda c: c[0])
 def test_gpu_parsed_clip_matches_oracle(gpu_ctx, case):
     from hvqm4_amd import batch
     from oracle import bridge
@@ -26,7 +26,7 @@ def test_gpu_parsed_clip_matches_oracle(gpu_ctx, case):
     want = bridge.oracle_decode(clip.data, clip.n_pictures)
     got = batch.decode_clip(gpu_ctx, clip.data, gpu_parse=True)
     assert np.array_equal(got, want)
-    if case in clips.SMALL and bridge.have_ref():       # ... and the unmodified reference decoder itself, when it is on this box (oracle/_ref)
+    if case in clips.SMALL + clips.SHAPES and bridge.have_ref():       # ... and the unmodified reference decoder itself, when it is on this box (oracle/_ref)
         assert np.array_equal(got, bridge.ref_decode(clip.data, clip.n_pictures)[0]), "GPU-parsed pictures differ from the compiled reference"
     st = gpu_ctx.stats()
     assert st.gpu_parsed == clip.n_pictures

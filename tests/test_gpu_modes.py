@@ -1,8 +1,9 @@
 """GPU: both workgroup shapes of the reconstruction kernel on every parity clip.
 
-The runtime picks one or two tiles per workgroup per launch from the AOT payload density (hvq_runtime.cpp, flush_end); the
-test clips are dense synthetic streams, so the default run exercises mostly the one-tile kernels.  Here the parity, batch and
-GPU-parse suites run once more in a child process with each shape forced (HVQM4_AMD_TILES_PER_WG is read once per process)."""
+The runtime picks one or two tiles per workgroup per launch from the fullest tile of the launch (hvq_recon_inline_plan); left to
+itself it takes two tiles for nearly every launch of the parity clips, so the default run hardly meets the one-tile kernels.  Here the
+parity, batch and GPU-parse suites run once more in a child process with each shape forced (HVQM4_AMD_TILES_PER_WG is read once per
+process); tests/test_launch_coverage.py proves that the two runs launch each of the fourteen instantiations with every picture kind."""
 import os
 import subprocess
 import sys
@@ -29,10 +30,11 @@ def test_parity_suites_with_forced_tiles_per_workgroup(tiles):
 
 @pytest.mark.parametrize("cap", ["24", "200"])
 def test_parity_suites_with_tiles_beyond_the_pair_list(cap):
-    """A tile with more (item, basis) pairs than the picture's pair list reserves (1024 at most) gets no pair list: its items walk
-    their bases themselves (the kernel's serial pair phase).
-    No encoder-like stream reaches 1024 pairs in 256 blocks; with the list capped at 24 nearly every tile of the parity clips
-    takes that path, at 200 the two kinds of tile meet inside one workgroup."""
+    """A workgroup whose tiles have more (item, basis) pairs than the launch's pair list holds (4096 at most) gets no pair list: its
+    items walk their bases themselves (the kernel's serial pair phase).
+    No parity clip reaches 4096 pairs (two tiles of manybases320x240 have 2 x 1018 at the most), so that path is reached ONLY through
+    HVQM4_AMD_PAIR_CAP: with the list capped at 24 nearly every tile of the parity clips takes it, at 200 the two kinds of tile meet
+    inside one workgroup."""
     env = dict(os.environ, HVQM4_AMD_PAIR_CAP=cap)
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
                         "tests/test_gpu_parity.py", "tests/test_gpu_gparse.py", "-k", NOT_PARSER_ONLY],

@@ -47,7 +47,7 @@ def decode_via_descriptors(clip, truncate=None):
     return np.stack(out), flags
 
 
-@pytest.mark.parametrize("case", clips.SMALL + clips.MEDIUM[:2] + clips.REGRESSION, ids=lambda c: c[0])
+@pytest.mark.parametrize("case", clips.SMALL + clips.MEDIUM[:2] + clips.REGRESSION + clips.SHAPES, ids=lambda c: c[0])
 def test_parse_plus_descriptor_spec_matches_oracle(case):
     from oracle import bridge
     clip = clips.get(case)
@@ -187,7 +187,7 @@ def _blobs(clip, threads, mangle=None):
     return out
 
 
-@pytest.mark.parametrize("case", clips.SMALL + clips.MEDIUM[:2] + clips.REGRESSION, ids=lambda c: c[0])
+@pytest.mark.parametrize("case", clips.SMALL + clips.MEDIUM[:2] + clips.REGRESSION + clips.SHAPES, ids=lambda c: c[0])
 def test_sections_parsed_side_by_side_give_the_same_blob(case):
     """hvq_parser_set_threads: block kinds, DC values, vectors and the planes' payloads are separate bit buffers (h4m:1981-1993,
     2030-2044) decoded by a small pool -- the blob must not depend on how many threads shared the work (the SDK boundary runs 4)"""

@@ -26,9 +26,9 @@ def test_oracle_matches_golden_small(name):
     assert got == e["picture_sha256"]
 
 
-@pytest.mark.parametrize("case", clips.MEDIUM, ids=lambda c: c[0])
+@pytest.mark.parametrize("case", clips.MEDIUM + clips.SHAPES, ids=lambda c: c[0])
 def test_oracle_matches_golden_full_size(case):
-    """320x240 / 640x480 clips are regenerated from their seed; the manifest pins clip bytes and output."""
+    """320x240 / 640x480 clips and the shape clips are regenerated from their seed; the manifest pins clip bytes and output."""
     from oracle import bridge
     e = MANIFEST["clips"][case[0]]
     clip = clips.get(case)
