@@ -149,6 +149,11 @@ SYMBOLS = {
     "hvq_context_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "hvq_context_destroy": (None, [C.c_void_p]),
     "hvq_context_set_launch_queues": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_context_set_group_bytes": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "hvq_context_launch_groups": (C.c_int, [C.c_void_p]),
+    "hvq_launch_group_default_bytes": (C.c_uint64, []),
+    "hvq_launch_group_plan": (C.c_uint32, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                           C.c_uint64, C.c_uint32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint64)]),
     "hvq_stream_open": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
     "hvq_stream_close": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_stream_ring_bytes": (C.c_uint64, [C.c_int] * 5),

@@ -32,6 +32,14 @@ class Context:
         """1 or 2 launch queues for this context's batches (hvq_context_set_launch_queues); 1 when two contexts share the GPU"""
         check(lib().hvq_context_set_launch_queues(self._h, n))
 
+    def set_group_bytes(self, nbytes: int) -> None:
+        """reuse window a launch group of this context's batches may span (hvq_context_set_group_bytes); 0: batches are never split"""
+        check(lib().hvq_context_set_group_bytes(self._h, nbytes))
+
+    def launch_groups(self) -> int:
+        """launch groups of the last flushed batch (hvq_context_launch_groups), 0: nothing flushed"""
+        return check(lib().hvq_context_launch_groups(self._h))
+
     def open_stream(self, width: int, height: int, h_samp: int = 2, v_samp: int = 2, is15: bool = True,
                     nslots: int = 4) -> int:
         sid = check(lib().hvq_stream_open(self._h, width, height, h_samp, v_samp, int(is15), nslots))

@@ -122,6 +122,13 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_compose(const void *tab_d
 
 #define HVQ_EXPORT extern "C" __attribute__((visibility("default")))
 
+/* Reuse window a launch group may span (hvq_launch_group_plan, hvq_context_set_group_bytes), bytes: 512 MiB.  A window counts every
+ * P/B picture twice (written once, reading as much), so this is about 256 MiB of distinct lines, the last-level cache.  The dense
+ * benchmark batch (128 streams of 640x480, window 707.8 MB) runs as two groups, which is what the sweep found best (one group 0.917,
+ * two 0.895, three 0.955, four 0.903, six 1.044 ms per step: profiles/r10_launch_groups.txt); BASELINE config 4 (221.2 MB) and
+ * everything smaller stay one group. */
+#define HVQ_GROUP_BYTES_DEFAULT (512ull << 20)
+
 /* ---- LDS sizing of one launch of hvq_recon_inline_kernel (pure apart from the two environment caps HVQM4_AMD_PAIR_CAP and
  * HVQM4_AMD_POOL_CAP, read once per process: hvq_flush_end calls it per launch, tests/test_recon_plan.py directly) ----
  * The kernel keeps its item queue, pair list and the tile range of the pool in LDS: accumulator rows and a block column for the items of
@@ -190,6 +197,61 @@ HVQ_EXPORT void hvq_recon_inline_plan(uint32_t max_items, uint32_t max_pairs, in
     *items_cap = two ? cap2 : cap1; *pair_cap = two ? pr2 : pr1; *pool_cap = two ? po2 : po1;
     *lds_bytes = two ? lds2 : lds1;
 }
+
+/* Launch groups of a batch (build_tiles): into how many groups of streams its launches are split, and which stream goes where.  Pure;
+ * it sees what build_tiles knows at begin -- per stream its picture size and the kinds and levels of its pending pictures (pictures
+ * [first[s], first[s + 1]) of `kinds` / `levels`; HVQ_PIC_*), no blob lengths.
+ *   A stream's reuse window is the largest sum, over two consecutive levels, of the algorithmic bytes of its pictures in them (written
+ *   once, P/B pictures read as much again): what is touched between an anchor's write and its last read one level later.  The batch's
+ *   window is the sum over its streams, G = ceil(window / budget) -- at most so many that every group keeps 8 streams per launch queue
+ *   (the 8 picture slots that spread a launch over the XCDs); budget 0, or a window within it: 1.
+ *   Streams go to the groups by work (algorithmic bytes of all their pictures), heaviest first to the lightest group that is not full: a
+ *   group is full at floor(n / G) streams, n % G groups take one more, so no group falls below the minimum.
+ * group_of (nstreams entries) and window may be null.  Returns G >= 1. */
+HVQ_EXPORT uint32_t hvq_launch_group_plan(uint32_t nstreams, const uint32_t *pic_bytes, const uint32_t *first, const uint8_t *kinds,
+                                          const int32_t *levels, uint64_t budget, uint32_t queues, uint16_t *group_of, uint64_t *window)
+{
+    std::vector<uint64_t> work(nstreams, 0), per_level;
+    uint64_t win = 0;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        per_level.clear();
+        for (uint32_t i = first[s]; i < first[s + 1]; ++i) {
+            const size_t l = (size_t)std::max(levels[i], 0);
+            if (per_level.size() < l + 2) per_level.resize(l + 2, 0);
+            const uint64_t b = (uint64_t)pic_bytes[s] * (kinds[i] == HVQ_PIC_I ? 1u : 2u);
+            per_level[l] += b; work[s] += b;
+        }
+        uint64_t w = 0;
+        for (size_t l = 0; l + 1 < per_level.size(); ++l) w = std::max(w, per_level[l] + per_level[l + 1]);
+        win += w;
+    }
+    if (window) *window = win;
+    const uint32_t min_streams = 8u * std::max(queues, 1u);
+    uint64_t g64 = budget ? (win + budget - 1) / budget : 1;
+    g64 = std::min<uint64_t>(g64, nstreams / min_streams);
+    const uint32_t G = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g64, 1), 65535);
+    if (!group_of) return G;
+    std::vector<uint32_t> order(nstreams);
+    for (uint32_t s = 0; s < nstreams; ++s) order[s] = s;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return work[a] > work[b]; });
+    std::vector<uint64_t> load(G, 0);
+    std::vector<uint32_t> count(G, 0);
+    const uint32_t base = nstreams / G;
+    uint32_t extra = nstreams % G;                     /* groups that may still take one stream more than `base` */
+    for (uint32_t s : order) {
+        uint32_t g = G;
+        for (uint32_t k = 0; k < G; ++k) {
+            if (count[k] > base || (count[k] == base && !extra)) continue;
+            if (g == G || load[k] < load[g]) g = k;
+        }
+        if (count[g] == base) --extra;
+        group_of[s] = (uint16_t)g; load[g] += work[s]; ++count[g];
+    }
+    return G;
+}
+
+/* the budget a new context carries (hvq_context_set_group_bytes changes it) */
+HVQ_EXPORT uint64_t hvq_launch_group_default_bytes(void) { return HVQ_GROUP_BYTES_DEFAULT; }
 
 static thread_local std::string g_err;
 static thread_local int g_sdk_err = 0;
@@ -306,6 +368,7 @@ struct Pending {
 struct Launch {
     int level;
     int queue;                         /* launch queue (0: the main stream, 1: stream2) */
+    int group;                         /* launch group of its streams (build_tiles): a queue runs group 0's levels, then group 1's, ... */
     uint32_t first_tile, ntiles;       /* its picture slots in the launch table: first entry, count */
     uint32_t max_tiles, workgroups;    /* grid = (8, max_tiles, slots / 8) at the chosen tiles per workgroup; workgroups that do work */
     uint32_t max_wg[2], wgs[2];        /* the same for one / two tiles per workgroup (chosen at flush_end, when the queues are known) */
@@ -317,8 +380,7 @@ struct Launch {
 /* a P picture with future-referencing macroblocks, behind the launch of its level: previous content into the destination slot
  * (unless it is there already), then the raster-order walk (hvq_selfref_kernel) from the side buffer */
 struct SelfRef {
-    int level;
-    int queue;                         /* the launch queue of its picture's level launch */
+    int launch;                        /* the launch of its picture's group, level and queue (index into `launches`) */
     uint32_t job;                      /* launch slot */
     const uint8_t *old_dev;            /* device source of the previous content, nullptr: in place already */
     const void *old_host;              /* SDK path: host source */
@@ -381,6 +443,9 @@ struct HvqContext {
     std::vector<Launch> fl_launches;   /* of the batch in flight: tile ranges known at begin, LDS sizes at end */
     int max_queues = 2;                /* hvq_context_set_launch_queues */
     std::vector<uint8_t> fl_qof;       /* launch queue of every stream in the batch in flight (two queues: dealt by work, build_tiles) */
+    uint64_t group_bytes = HVQ_GROUP_BYTES_DEFAULT;    /* hvq_context_set_group_bytes: the reuse window a launch group may span, 0: never split */
+    std::vector<uint16_t> fl_gof;      /* launch group of every stream in the batch in flight (hvq_launch_group_plan) */
+    uint32_t fl_groups = 1, groups = 0;                /* G of the batch in flight; of the resident batch (0: none) */
     HvqStats stats{};
     double parse_seconds = 0;
     std::atomic<uint64_t> copy_bytes{ 0 };     /* bitstream bytes copied into the pinned arena (copy threads), and their wall time in ns */
@@ -660,6 +725,23 @@ HVQ_EXPORT int hvq_context_set_launch_queues(HvqContext *c, int n)
     if (!c || n < 1 || n > 2) return fail(HVQ_E_ARG, "launch queues: 1 or 2");
     c->max_queues = n;
     return HVQ_OK;
+}
+
+/* The reuse window (hvq_launch_group_plan) the launches of one group of streams may span, in bytes; 0: a batch is never split.  Takes
+ * effect at the next hvq_flush_begin. */
+HVQ_EXPORT int hvq_context_set_group_bytes(HvqContext *c, uint64_t bytes)
+{
+    if (!c) return fail(HVQ_E_ARG, "null context");
+    c->group_bytes = bytes;
+    return HVQ_OK;
+}
+
+/* launch groups of the resident batch (the last one flushed), 0: none */
+HVQ_EXPORT int hvq_context_launch_groups(HvqContext *c)
+{
+    if (!c) return fail(HVQ_E_ARG, "null context");
+    { int rc = flush_end(c); if (rc) return rc; }
+    return c->launches.empty() ? 0 : (int)c->groups;
 }
 
 HVQ_EXPORT void hvq_context_destroy(HvqContext *c)
@@ -1515,8 +1597,8 @@ static int device_parse_finish(HvqContext *c)
     return HVQ_OK;
 }
 
-/* The launches of the resident batch go out dependency level by dependency level, every launch on the queue build_tiles dealt its
- * streams to (one queue, or two for large uniform batches: see there).
+/* The launches of the resident batch go out launch group by launch group, inside a group dependency level by dependency level, every
+ * launch on the queue build_tiles dealt its streams to (one queue, or two for large uniform batches: see there).
  * The second launch queue forks from the main stream (everything queued there so far is done before its first launch) ... */
 static int queues_fork(HvqContext *c, bool *two)
 {
@@ -1561,7 +1643,7 @@ static int run_launches(HvqContext *c)
         hipStream_t st = L.queue ? c->qstream[L.queue] : c->stream;
         HIPCHK(hvq_launch_recon_inline(c->jobs_dev + L.first_tile, L.ntiles, L.max_tiles, L.tpw, L.items_cap, L.pair_cap, L.pool_cap, st));
         for (const SelfRef &sr : c->selfrefs) {
-            if (sr.level != L.level || sr.queue != L.queue) continue;
+            if (sr.launch != (int)(&L - c->launches.data())) continue;
             if (sr.old_host) HIPCHK(hipMemcpyAsync(sr.dst, sr.old_host, sr.pic_bytes, hipMemcpyHostToDevice, st));
             else if (sr.old_dev) HIPCHK(hipMemcpyAsync(sr.dst, sr.old_dev, sr.pic_bytes, hipMemcpyDeviceToDevice, st));
             HIPCHK(hvq_launch_selfref(c->jobs_dev + sr.job, c->selfref_dev + sr.side_off, sr.dst, st));
@@ -1570,8 +1652,12 @@ static int run_launches(HvqContext *c)
     return HVQ_OK;
 }
 
-/* launch table of the batch in flight: one launch per dependency level (and queue), one slot {job, tiles} per picture; the
- * slot count is padded to a multiple of 8 so that grid column x runs on XCD x % 8 and a picture's tiles share one L2.
+/* launch table of the batch in flight: one launch per launch group, dependency level and queue, one slot {job, tiles} per picture;
+ * the slot count of a launch is padded to a multiple of 8 so that grid column x runs on XCD x % 8 and a picture's tiles share one L2.
+ * The launches are pushed -- and later issued (run_launches) -- group by group, inside a group level by level, inside a level queue
+ * by queue: a stream belongs to one group and one queue, so its pictures stay in level order on one in-order queue, which is all
+ * their dependencies need (clips are independent).  A batch within the context's group budget is one group: level-major over all
+ * its streams, as before there were groups.  The queues are forked and joined once around all groups (flush_end, replay_passes).
  * Needs nothing from the GPU, so it is built and uploaded while the parse kernel runs. */
 static int build_tiles(HvqContext *c)
 {
@@ -1604,6 +1690,30 @@ static int build_tiles(HvqContext *c)
         /* streams to queues by WORK (tiles of their pictures in this batch), heaviest first to the lighter queue: clips of mixed sizes
          * (BASELINE config 4 alternates 320x240 and 640x480) dealt by parity put every large clip on one queue, and that chain then ran
          * alone for most of the step (1766 against 1295 us) */
+        /* Launch groups: level-major over a large batch, everything the batch touches at two levels (0.7 GB for 128 dense streams of
+         * 640x480) passes between an anchor's write and its reads, several times the 256 MiB last-level cache.  The streams of a
+         * group walk all their levels before the next group starts, so that window is the group's (hvq_launch_group_plan: the rule,
+         * in bytes; profiles/r10_launch_groups.txt: what it measured).  HVQM4_AMD_GROUP_BYTES overrides the context's budget. */
+        static const char *genv = getenv("HVQM4_AMD_GROUP_BYTES");
+        const uint64_t budget = genv ? strtoull(genv, nullptr, 10) : c->group_bytes;
+        std::vector<uint32_t> ids, pic_bytes, first;
+        std::vector<uint32_t> dense(c->streams.size(), 0);
+        for (size_t sidx = 0; sidx < seen.size(); ++sidx)
+            if (seen[sidx]) { dense[sidx] = (uint32_t)ids.size(); ids.push_back((uint32_t)sidx); pic_bytes.push_back(c->streams[sidx].pic_bytes); }
+        first.assign(ids.size() + 1, 0);
+        for (auto &p : c->fl_pending) ++first[dense[(size_t)p.stream] + 1];
+        for (size_t k = 0; k < ids.size(); ++k) first[k + 1] += first[k];
+        std::vector<uint8_t> kinds(c->fl_pending.size());
+        std::vector<int32_t> levels(c->fl_pending.size());
+        {
+            std::vector<uint32_t> at(first.begin(), first.end() - 1);
+            for (auto &p : c->fl_pending) { const uint32_t k = at[dense[(size_t)p.stream]]++; kinds[k] = (uint8_t)p.kind; levels[k] = p.level; }
+        }
+        std::vector<uint16_t> gof(ids.size(), 0);
+        c->fl_groups = hvq_launch_group_plan((uint32_t)ids.size(), pic_bytes.data(), first.data(), kinds.data(), levels.data(), budget, (uint32_t)nq,
+                                             gof.data(), nullptr);
+        c->fl_gof.assign(c->streams.size(), 0);
+        for (size_t k = 0; k < ids.size(); ++k) c->fl_gof[ids[k]] = gof[k];
         c->fl_qof.assign(c->streams.size(), 0);
         if (nq >= 2) {
             std::vector<uint64_t> work(c->streams.size(), 0);
@@ -1611,25 +1721,30 @@ static int build_tiles(HvqContext *c)
             std::vector<uint32_t> order;
             for (size_t sidx = 0; sidx < work.size(); ++sidx) if (seen[sidx]) order.push_back((uint32_t)sidx);
             std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return work[a] > work[b]; });
-            uint64_t load[4] = { 0, 0, 0, 0 };
+            std::vector<uint64_t> load((size_t)c->fl_groups * 4, 0);       /* per group: its streams to the queues as the whole batch's were */
             for (uint32_t sidx : order) {
+                uint64_t *ld = load.data() + (size_t)c->fl_gof[sidx] * 4;
                 int q = 0;
-                for (int k = 1; k < nq; ++k) if (load[k] < load[q]) q = k;
-                c->fl_qof[sidx] = (uint8_t)q; load[q] += work[sidx];
+                for (int k = 1; k < nq; ++k) if (ld[k] < ld[q]) q = k;
+                c->fl_qof[sidx] = (uint8_t)q; ld[q] += work[sidx];
             }
         }
     }
+    /* group -> level -> queue: every queue runs group 0's levels in order, then group 1's, and both walk the groups in the same order.
+     * Nothing joins the queues between groups: a group's small I level overlaps the tail of the group before it. */
+    for (int grp = 0; grp < (int)c->fl_groups; ++grp)
     for (int lvl = 0; lvl <= max_level; ++lvl)
       for (int qi = 0; qi < nq; ++qi) {
         Launch L{};
         L.queue = qi;
+        L.group = grp;
         L.level = lvl; L.first_tile = (uint32_t)tiles.size();
         /* submission order (sorting same-stream pictures into one grid column of consecutive groups was tried: +1 % dense, -3 % flat, dropped) */
         /* (walking odd levels in reverse order, so that a level reads first the anchors its predecessor wrote last, was measured in
          * round 5: dense -1.5 %, flat -3 %, profiles/r05_recon_steps.txt) */
         for (size_t i = 0; i < c->fl_pending.size(); ++i) {
             const Pending &p = c->fl_pending[i];
-            if (p.level != lvl || (nq >= 2 && c->fl_qof[(size_t)p.stream] != qi)) continue;
+            if (p.level != lvl || (nq >= 2 && c->fl_qof[(size_t)p.stream] != qi) || (int)c->fl_gof[(size_t)p.stream] != grp) continue;
             tiles.push_back(HvqTileRef{ (uint32_t)i, p.ntiles });
             L.max_wg[0] = std::max(L.max_wg[0], p.ntiles); L.wgs[0] += p.ntiles;
             L.max_wg[1] = std::max(L.max_wg[1], p.nwg); L.wgs[1] += p.nwg;
@@ -1928,7 +2043,7 @@ static int flush_end(HvqContext *c)
             j.q_offs_off = 16;
             tq_bytes += 16 + (size_t)nt * HVQ_TILE_BLOCKS * 4;
             SelfRef sr{};
-            sr.level = p.level; sr.job = (uint32_t)k;
+            sr.job = (uint32_t)k;                        /* sr.launch: below, when the launches are known */
             sr.old_host = p.host_old;
             sr.old_dev = (p.host_old || p.old_slot == p.dst) ? nullptr : s.slot_ptr(p.old_slot);     /* -1: the zero slot */
             sr.dst = s.slot_ptr(p.dst);
@@ -1965,16 +2080,24 @@ static int flush_end(HvqContext *c)
     bool twoq = false;
     int nqs = 1;
     for (auto &L : c->fl_launches) { twoq |= L.queue >= 1; nqs = std::max(nqs, L.queue + 1); }
-    for (auto &sr : c->selfrefs) sr.queue = twoq ? (int)c->fl_qof[(size_t)c->fl_pending[slots[sr.job].job].stream] : 0;
+    /* a picture's launch: the one of its stream's group and queue at its level */
+    int nlv = 1;
+    for (auto &L : c->fl_launches) nlv = std::max(nlv, L.level + 1);
+    std::vector<int> lidx((size_t)c->fl_groups * nlv * nqs, -1);
+    for (size_t l = 0; l < c->fl_launches.size(); ++l) {
+        const Launch &L = c->fl_launches[l];
+        lidx[((size_t)L.group * nlv + L.level) * nqs + L.queue] = (int)l;
+    }
+    auto launch_of = [&](const Pending &p) -> int {
+        const int q = twoq ? (int)c->fl_qof[(size_t)p.stream] : 0;
+        return p.level < nlv ? lidx[((size_t)c->fl_gof[(size_t)p.stream] * nlv + p.level) * nqs + q] : -1;
+    };
+    for (auto &sr : c->selfrefs) sr.launch = launch_of(c->fl_pending[slots[sr.job].job]);
     for (size_t i = 0; i < c->fl_pending.size(); ++i) {
         const Pending &p = c->fl_pending[i];
         if (p.dropped) continue;
-        for (size_t l = 0; l < c->fl_launches.size(); ++l) {
-            const Launch &L = c->fl_launches[l];
-            if (p.level != L.level || (twoq && (int)c->fl_qof[(size_t)p.stream] != L.queue)) continue;
-            lmi[l] = std::max(lmi[l], p.max_items); lmp[l] = std::max(lmp[l], p.max_pairs);
-            break;
-        }
+        const int l = launch_of(p);
+        if (l >= 0) { lmi[(size_t)l] = std::max(lmi[(size_t)l], p.max_items); lmp[(size_t)l] = std::max(lmp[(size_t)l], p.max_pairs); }
     }
     for (size_t li = 0; li < c->fl_launches.size(); ++li) {
         Launch &L = c->fl_launches[li];
@@ -1985,10 +2108,12 @@ static int flush_end(HvqContext *c)
         if (flush_timing())
             fprintf(stderr, "[flush] launch %zu (level %d, queue %d): fullest tile %u items, %u pairs -> %u tile(s) per workgroup, items %u, pairs %u, pool %u, %u B of LDS = %u workgroups per CU\n",
                     li, (int)L.level, (int)L.queue, mi, mp, L.tpw, L.items_cap, L.pair_cap, L.pool_cap, lds, hvq_recon_inline_residency(L.tpw, L.items_cap, lds));
+        if (flush_timing()) fprintf(stderr, "[flush] group %d of %u: launch %zu (level %d, queue %d), %u picture slots\n", L.group, c->fl_groups, li, L.level, L.queue, L.ntiles);
         L.max_tiles = L.max_wg[L.tpw - 1]; L.workgroups = L.wgs[L.tpw - 1];
         st.workgroups += L.workgroups;
     }
     c->launches = c->fl_launches;
+    c->groups = c->fl_groups;
     st.launches = (uint32_t)c->launches.size();
     st.launch_queues = (uint32_t)nqs;
     st.parse_seconds = c->parse_seconds;

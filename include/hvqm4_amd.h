@@ -48,7 +48,7 @@ typedef struct HvqStats {
     uint64_t luma_pixels;       /* sum of w*h over them */
     uint64_t algorithmic_bytes; /* 1.5 B/px written + 1.5 B/px read for P/B */
     uint64_t descriptor_bytes;  /* blob bytes uploaded (not credited in the roofline) */
-    uint32_t launches;          /* kernel launches per pass: dependency levels x launch queues */
+    uint32_t launches;          /* kernel launches per pass: launch groups x dependency levels x launch queues */
     uint32_t workgroups;        /* total workgroups per pass */
     double   parse_seconds;     /* host entropy-parse time accumulated by hvq_stream_submit */
     uint32_t flags_or;          /* OR of all blob header flags (HVQ_F_*) */
@@ -70,6 +70,18 @@ int  hvq_context_create(int device, HvqContext **out);
  * to two HIP streams, HvqStats.launch_queues) or 1.  A process that runs TWO contexts on a GPU side by side (INTEGRATION.md "Two contexts per
  * GPU") sets 1 on both: the contexts are each other's second queue, four queues get in each other's way (157 against 171 Gpixel/s). */
 int  hvq_context_set_launch_queues(HvqContext *ctx, int n);
+/* Launch groups: a batch whose reuse window -- per stream the largest sum, over two consecutive dependency levels, of the bytes its pictures
+ * write and read; summed over the streams -- exceeds `bytes` is split into G = ceil(window / bytes) groups of streams (never fewer than 8
+ * streams per launch queue in a group); every launch queue runs all levels of group 0, then of group 1, ..., so what lies between an anchor's
+ * write and its reads is one group's window, not the batch's.  0: never split.  Same pictures either way; HvqStats.launches counts G times
+ * as many.  Takes effect at the next hvq_flush_begin.  hvq_context_launch_groups: G of the last flushed batch (0: none), or an error. */
+int  hvq_context_set_group_bytes(HvqContext *ctx, uint64_t bytes);
+int  hvq_context_launch_groups(HvqContext *ctx);
+uint64_t hvq_launch_group_default_bytes(void);     /* what a new context carries */
+/* the rule itself (pure): pictures [first[s], first[s + 1]) of `kinds` (0 I, 1 P, 2 B) and `levels` are stream s's; group_of (nstreams
+ * entries) and window may be null -> G */
+uint32_t hvq_launch_group_plan(uint32_t nstreams, const uint32_t *pic_bytes, const uint32_t *first, const uint8_t *kinds, const int32_t *levels,
+                               uint64_t budget, uint32_t queues, uint16_t *group_of, uint64_t *window);
 void hvq_context_destroy(HvqContext *ctx);
 
 /* A stream = one clip.  `nslots` >= 3 picture buffers stay resident in HBM per stream (the
