@@ -88,6 +88,14 @@ class HvqRank(C.Structure):                     # an entry of hvq_rank_pictures:
     _fields_ = [("luma", HvqRankPlane), ("chroma", HvqRankPlane)]
 
 
+class HvqBilateralPlane(C.Structure):           # include/hvqm4_amd.h: a plane's radii, its spatial table [|j|][|i|] and its range table
+    _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("pad", C.c_int32 * 2), ("spatial", (C.c_uint8 * 8) * 8), ("range", C.c_uint8 * 256)]
+
+
+class HvqBilateral(C.Structure):                # an entry of hvq_bilateral_pictures: luma for Y, chroma for U and V
+    _fields_ = [("luma", HvqBilateralPlane), ("chroma", HvqBilateralPlane)]
+
+
 class HvqTablePlane(C.Structure):               # include/hvqm4_amd.h: a plane's table kind (HVQ_TBL_*) and its parameters
     _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("pad", C.c_int32)]
 
@@ -221,6 +229,10 @@ SYMBOLS = {
     "hvq_rank_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "hvq_rank_force_general": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvq_bilateral_check": (C.c_int, [C.c_void_p]),
+    "hvq_bilateral_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "hvq_bilateral_force_general": (C.c_int, [C.c_void_p, C.c_int]),
     "hvq_map_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p]),
     "hvq_table_check": (C.c_int, [C.c_void_p]),

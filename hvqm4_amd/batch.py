@@ -730,6 +730,60 @@ class Context:
             spare, cur = cur, res
         return cur
 
+    def bilateral_force_general(self, on: bool) -> bool:
+        """hvq_bilateral_force_general: every later bilateral_pictures of this context runs the planes of radius 0 through the general
+        body of the kernel instead of the copy body (False: the chosen one again) -> the setting before.  The values do not depend on
+        it: for tests that compare the two with =="""
+        return bool(check(lib().hvq_bilateral_force_general(self._h, int(bool(on)))))
+
+    def bilateral_pictures(self, sids, ordinals, bil, guide=None, src=None, out=None):
+        """hvq_bilateral_pictures: resident pictures (sids[i], ordinals[i]) through bilateral filters -- a weighted mean whose weights
+        are a spatial table times a range table of the guide's difference, exact integers with one rounding (include/hvqm4_amd.h) --
+        into uint8 pictures of their own geometry IN SLOT LAYOUT (Y | U | V), on torch's current stream, without a host synchronisation
+        and without moving a picture.  `bil`: one hvqm4_amd.bilateral.Bilateral, or a list of one per picture (equal ones share an
+        entry of the call's table; more than 64 distinct ones: ValueError).  `guide`: None (every picture guides itself) or a list of
+        one entry per picture as picture_metrics' `ref` -- None (itself), (sid, ordinal) (a resident picture of the same geometry) or
+        a uint8 CUDA tensor in slot layout.  Return forms and `out` are rank_pictures'; whatever takes src= or ref.ptr takes a row of
+        the result.  hvqm4_amd.bilateral builds the sets and gives the expected bytes (of_picture).  `src` as in picture_checksums.
+        Ordering and slot safety are export()'s."""
+        from . import bilateral as bl
+        from .metrics import references
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        table, which = Context._table_which(bil, n, bl.Bilateral, "bil", "bilateral.Bilateral", bl.MAX_SETS, "sets")
+        for b in table:
+            bl.check(b)                                                    # ValueError beyond the library's limits
+        refs = references(guide, n, lambda i: self.pic_bytes(sids[i]))
+        ptrs, out, device, where = Context._slot_frame(self, sids, ordinals, src, out)
+        if not n:
+            return out
+        a_s, a_o, stream = Context._launch_args(device, sids, ordinals)
+        from ._lib import HvqBilateral
+        a_b = (HvqBilateral * len(table))(*[b.struct() for b in table])
+        a_w = Context._which_array(which, n)
+        a_d = C.c_void_p(where.ctypes.data)                                  # void *[n]
+        check(lib().hvq_bilateral_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), Context._ref_array(refs), C.cast(a_b, C.c_void_p), len(table),
+                                           a_w, a_d, stream))
+        return out
+
+    def smooth_pictures(self, sids, ordinals, steps, guide=None, out=None):
+        """resident pictures (sids[i], ordinals[i]) through a list of bilateral steps (hvqm4_amd.bilateral.iterate, or any list of
+        bilateral.Bilateral), one bilateral_pictures a step on torch's current stream: the first from the resident pictures, every later
+        one from the result before it through src=, every step under `guide`.  The results between the steps alternate between two
+        scratch tensors of the output's form; the last lands in `out` (rank_pictures' rules; default: a new one).  No host
+        synchronisation.  -> rank_pictures' return forms.  hvqm4_amd.bilateral.of_steps gives the expected bytes."""
+        from . import bilateral as bl
+        steps = bl.as_steps(steps)
+        n = len(sids)
+        cur = spare = None
+        for k, step in enumerate(steps):
+            dst = out if k == len(steps) - 1 else spare
+            if cur is None:
+                res = self.bilateral_pictures(sids, ordinals, step, guide=guide, out=dst)
+            else:
+                res = self.bilateral_pictures(sids, [-1] * n, step, guide=guide, src=[cur[i] for i in range(n)], out=dst)
+            spare, cur = cur, res
+        return cur
+
     def map_pictures(self, sids, ordinals, tables, planes=7, src=None, out=None):
         """hvq_map_pictures: resident pictures (sids[i], ordinals[i]) through lookup tables, out = table[plane][in], nothing rounded
         (include/hvqm4_amd.h), into uint8 pictures of their own geometry IN SLOT LAYOUT (Y | U | V), on torch's current stream, without

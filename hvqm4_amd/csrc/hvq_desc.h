@@ -718,6 +718,53 @@ _Static_assert(sizeof(HvqRankJob) == 48, "HvqRankJob must be 48 bytes");
 #endif
 
 
+/* one plane of one picture of the bilateral launch (hvq_bilateral.hip, hvq_bilateral_pictures): three jobs a picture, Y, U, V.  `src`,
+ * `dst` and `guide` are planes of ny rows of nx samples, dense (pitch nx: a multiple of 4, as the addresses are); guide is 0 where the
+ * plane guides itself.  Behind the jobs of a launch lie the call's parameter sets as they stand in include/hvqm4_amd.h, luma and chroma
+ * of set 0, of set 1, ...: `ps` is the index of the plane's HvqBilateralPlane among them (HVQ_BL_PLANE_BYTES each; the kernel reads its
+ * `spatial` rows as qwords and copies its `range` bytes into LDS).  Grid row = picture, its three jobs one behind the other; a workgroup
+ * of HVQ_BL_LANES lanes takes a tile of one plane -- HVQ_BL_TW x HVQ_BL_TH targets in the general body, HVQ_BL_CTW x HVQ_BL_CTH in the
+ * copy body: tiles_x tiles side by side, `tiles` in all; the workgroups of a grid row walk the tiles of Y, then U, then V, those past
+ * them leave.  Every member is a dword or a qword (scalar loads); 64 bytes. */
+#define HVQ_BL_LANES  256u
+#define HVQ_BL_TW     64u           /* targets a tile is wide: 16 dwords, one store a lane */
+#define HVQ_BL_TH     16u           /* its rows: lane l owns dword l & 15 of row l >> 4 */
+#define HVQ_BL_CTW    256u          /* the copy body's tile: a wave moves 256 adjacent bytes of a row, a lane four rows 4 apart */
+#define HVQ_BL_CTH    16u
+#define HVQ_BL_MAX_R  7u            /* the largest radius: HVQ_BIL_MAX_RADIUS */
+#define HVQ_BL_HALO   8u            /* bytes staged left and right of a tile's 64: the radius rounded up to whole dwords */
+#define HVQ_BL_ROW_DWORDS ((HVQ_BL_TW + 2u * HVQ_BL_HALO) / 4u)   /* 20 */
+#define HVQ_BL_MAX_ROWS (HVQ_BL_TH + 2u * HVQ_BL_MAX_R)          /* 30 staged rows at the most */
+#define HVQ_BL_BUF    (HVQ_BL_MAX_ROWS * HVQ_BL_ROW_DWORDS)      /* dwords of a staged tile: the source's, and the guide's */
+#define HVQ_BL_PLANE_BYTES 336u     /* sizeof(HvqBilateralPlane): rx, ry, pad[2], spatial[8][8], range[256] */
+#define HVQ_BL_SPATIAL_AT  16u      /* ... the byte its spatial table begins at */
+#define HVQ_BL_RANGE_AT    80u      /* ... and its range table */
+#define HVQ_BL_COPY    0u
+#define HVQ_BL_GENERAL 1u
+typedef struct HvqBilateralJob {
+    uint64_t src;                      /* device address of the source plane, a multiple of 4 */
+    uint64_t dst;                      /* device address of the target plane, a multiple of 4 */
+    uint64_t guide;                    /* device address of the guide plane, a multiple of 4; 0: the source guides itself */
+    uint32_t nx, ny;                   /* samples of the plane: nx a multiple of 4 */
+    uint32_t tiles_x, tiles;
+    uint32_t body;                     /* HVQ_BL_COPY or HVQ_BL_GENERAL */
+    uint32_t ps;                       /* index of the plane's HvqBilateralPlane behind the jobs */
+    uint32_t rx, ry;                   /* the radii, 0 .. HVQ_BL_MAX_R */
+    uint32_t pad[2];
+} HvqBilateralJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqBilateralJob) == 64 && sizeof(HvqBilateralJob) % 16 == 0, "HvqBilateralJob must be 64 bytes: job tables are uploaded in 16-byte units");
+static_assert(HVQ_BL_TW * HVQ_BL_TH == HVQ_BL_LANES * 4u && HVQ_BL_TW == 64u, "a lane stores one dword of the tile");
+static_assert(HVQ_BL_CTW == 64u * 4u && HVQ_BL_CTH * 64u == HVQ_BL_LANES * 4u, "the copy body: 64 lanes side by side, four waves, four rows a lane");
+static_assert(HVQ_BL_HALO >= HVQ_BL_MAX_R + 1u && HVQ_BL_HALO % 4u == 0, "the staged row: whole dwords that hold the halo; an unaligned read takes the dword behind");
+static_assert(HVQ_BL_BUF <= 3u * HVQ_BL_LANES, "a lane stages three dwords of a tile at the most");
+static_assert(HVQ_BL_PLANE_BYTES % 16u == 0 && HVQ_BL_SPATIAL_AT % 8u == 0 && HVQ_BL_RANGE_AT % 4u == 0, "the sets lie behind the jobs in 16-byte units; rows of qwords, a table of dwords");
+#else
+_Static_assert(sizeof(HvqBilateralJob) == 64, "HvqBilateralJob must be 64 bytes");
+#endif
+
+
 /* one plane of one picture of the map launch (hvq_map.hip, hvq_map_pictures): three jobs a picture, Y, U, V.  A point operation does not
  * look at rows: `src` and `dst` are the plane's `dwords` dwords, dense.  `table` is the device address of the plane's 256 table bytes
  * (a multiple of 16: record which[i], plane p); a plane that is copied (its bit of `planes` is clear) has body HVQ_MP_COPY and table 0.

@@ -44,6 +44,7 @@
 #include "hvq_scale.h"
 #include "hvq_filter.h"
 #include "hvq_rank.h"
+#include "hvq_bilateral.h"
 #include "hvq_map.h"
 #include "hvq_label.h"
 #include "hvq_distance.h"
@@ -101,6 +102,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_scale(const void *jobs_de
 extern "C" __attribute__((weak)) hipError_t hvq_launch_filter(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_rank.hip.  Weak for the same reason: hvq_rank_pictures then refuses with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_rank(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_bilateral.hip.  Weak for the same reason: hvq_bilateral_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_bilateral(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 /* hvq_map.hip.  Weak for the same reason: hvq_map_pictures and hvq_histogram_tables then refuse with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_map(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_tables(const void *jobs_dev, int nrecords, hipStream_t stream);
@@ -474,6 +477,7 @@ struct HvqContext {
     int wp_force = 0;                  /* hvq_warp_force_direct: 0 the chosen body of hvq_warp.hip, 1 the direct one, 2 the tiled one wherever LDS holds the box */
     bool fl_force_filter = false;      /* hvq_filter_force_filter: identity planes take the filter body of hvq_filter.hip, not the copy body */
     bool rk_force_general = false;     /* hvq_rank_force_general: planes that are copied take the min/max body of hvq_rank.hip, not the copy body */
+    bool bl_force_general = false;     /* hvq_bilateral_force_general: planes of radius 0 take the general body of hvq_bilateral.hip, not the copy body */
     bool sc_force_direct = false;      /* hvq_scale_force_direct: every plane takes the direct body of hvq_scale.hip */
     /* GPU entropy parse: blobs + scratch + nests of a batch, its job and result tables, the events around its parse kernel.  Two
      * sets: hvq_flush_next queues the parse of batch k + 1 BEFORE it takes the results of batch k, so the reconstruction of batch k
@@ -2606,7 +2610,7 @@ static int export_enqueue(HvqContext *c, const void *jobs, size_t bytes, void *h
 }
 
 /* ---- The frame of the calls that write uint8 pictures in slot layout, Y | U | V ("The slot-layout frame"): scale,
- * filter, warp, compose, rank, map.  Everything here inlines into the entry point's loop: no allocation, no indirect call ---- */
+ * filter, warp, compose, rank, bilateral, map.  Everything here inlines into the entry point's loop: no allocation, no indirect call ---- */
 
 /* "%d pictures": the most one launch's grid takes; `why` is what a record call adds to the text (GRID_ROW) */
 static int count_check(int n, const char *noun, const char *why = "")
@@ -3367,6 +3371,64 @@ HVQ_EXPORT int hvq_rank_pictures(HvqContext *c, int n, const int *streams, const
         }));
     }
     return slot_enqueue(c, hvq_launch_rank, "rank", "hvq_rank.hip", jobs, n, max_tiles, hip_stream);
+}
+
+/* Bilateral filters on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):
+ * the call's parameter sets go behind the jobs in the same upload, as they stand in the header */
+static int bilateral_plane_check(const HvqBilateralPlane &p, const char *plane)
+{
+    if (p.rx < 0 || p.rx > HVQ_BIL_MAX_RADIUS || p.ry < 0 || p.ry > HVQ_BIL_MAX_RADIUS)
+        return fail(HVQ_E_ARG, "%s bilateral: radii %d, %d outside 0 .. %d", plane, p.rx, p.ry, HVQ_BIL_MAX_RADIUS);
+    if (!p.spatial[0][0] || !p.range[0]) return fail(HVQ_E_ARG, "%s bilateral: spatial[0][0] %d, range[0] %d (the centre tap has a weight: both at least 1)", plane, p.spatial[0][0], p.range[0]);
+    if (p.pad[0] || p.pad[1]) return fail(HVQ_E_ARG, "%s bilateral: pad %d, %d (0)", plane, p.pad[0], p.pad[1]);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int hvq_bilateral_check(const HvqBilateral *b)
+{
+    if (!b) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = bilateral_plane_check(b->luma, "luma"); if (rc) return rc; }
+    return bilateral_plane_check(b->chroma, "chroma");
+}
+
+HVQ_EXPORT int hvq_bilateral_force_general(HvqContext *c, int on) { return force_switch(c, &HvqContext::bl_force_general, on); }
+
+HVQ_EXPORT int hvq_bilateral_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                      const HvqMetricsRef *guide, const HvqBilateral *sets, int nsets, const int *which,
+                                      void *const *dst, void *hip_stream)
+{
+    static_assert(HVQ_BIL_MAX_RADIUS == (int)HVQ_BL_MAX_R && HVQ_BIL_MAX_SETS == (int)HVQ_BL_MAX_SETS && sizeof(HvqBilateralPlane) == HVQ_BL_PLANE_BYTES &&
+                  offsetof(HvqBilateralPlane, spatial) == HVQ_BL_SPATIAL_AT && offsetof(HvqBilateralPlane, range) == HVQ_BL_RANGE_AT &&
+                  sizeof(HvqBilateral) == 2u * HVQ_BL_PLANE_BYTES, "the header's values and layout are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !dst || !sets))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nsets < 1 || nsets > HVQ_BIL_MAX_SETS) return fail(HVQ_E_ARG, "%d sets: one call takes 1 .. %d", nsets, HVQ_BIL_MAX_SETS);
+    for (int b = 0; b < nsets; ++b) { int rc = hvq_bilateral_check(sets + b); if (rc) return rc; }
+    { int rc = chain_begin(c, n, streams, ordinals, src, guide); if (rc) return rc; }
+    const size_t job_bytes = (size_t)n * 3u * sizeof(HvqBilateralJob);
+    std::vector<uint8_t> up(job_bytes + (size_t)nsets * sizeof(HvqBilateral));
+    HvqBilateralJob *jobs = (HvqBilateralJob *)up.data();
+    memcpy(up.data() + job_bytes, sets, (size_t)nsets * sizeof(HvqBilateral));
+    uint32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr, *g = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        { int rc = picture_reference(c, i, streams[i], guide ? guide + i : nullptr, nullptr, &g); if (rc) return rc; }     /* null: the picture guides itself */
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("destination", i, dst[i]); if (rc) return rc; }
+        const int b = which ? which[i] : 0;
+        if (b < 0 || b >= nsets) return fail(HVQ_E_ARG, "picture %d: set %d of %d", i, b, nsets);
+        uint8_t *const d = (uint8_t *)dst[i];
+        max_tiles = std::max(max_tiles, (uint32_t)plane_walk(slot_shape(s), [&](int p, size_t off, uint32_t nx, uint32_t ny) {
+            const HvqBilateralPlane &bp = p ? sets[b].chroma : sets[b].luma;
+            HvqBilateralJob &j = jobs[(size_t)i * 3u + (size_t)p];
+            j = hvq_bl_job((uint64_t)(uintptr_t)(a + off), (uint64_t)(uintptr_t)(d + off), g ? (uint64_t)(uintptr_t)(g + off) : 0u, nx, ny,
+                           (uint32_t)(2 * b + (p ? 1 : 0)), (uint32_t)bp.rx, (uint32_t)bp.ry, c->bl_force_general);
+            return j.tiles;
+        }));
+    }
+    return slot_enqueue(c, hvq_launch_bilateral, "bilateral", "hvq_bilateral.hip", up, n, max_tiles, hip_stream);
 }
 
 /* Lookup tables on resident pictures in slot layout (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "The slot-layout frame"):

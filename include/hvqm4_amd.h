@@ -909,6 +909,65 @@ int     hvq_rank_pictures(HvqContext *ctx, int n, const int *streams, const int 
                           const HvqRank *ranks, int nranks, const int *which, void *const *dst, void *hip_stream);
 int     hvq_rank_force_general(HvqContext *ctx, int on);
 
+/* Resident pictures through BILATERAL FILTERS into uint8 pictures of THEIR OWN geometry in slot layout, where they lie: for `n` pictures,
+ * of any streams, sizes and samplings, in one kernel launch on the caller's HIP stream and without a host synchronisation, each plane
+ * through a weighted mean of a rectangular window whose weights depend on the samples themselves: smoothing that keeps edges.  The
+ * sigma filter ("surface blur") and the joint / cross bilateral filter, whose weights come from another picture (the guide), are special
+ * cases.  What hvq_filter_pictures cannot be: the weights are no constants and the filter is not separable.  hvqm4_amd.bilateral builds
+ * the tables.  The result composes like hvq_scale_pictures': whatever takes `src` or `ref.ptr` takes it.  The values are exact
+ * integers with one rounding, and this text is the authority for the bytes.
+ *   Planes.    Y goes through bil.luma, U and V through bil.chroma, each at its own resolution: Ny rows x Nx samples a.  The guide plane g
+ *              is the same plane of the guide picture, or a itself when the picture has no guide.
+ *   Window.    cx(v) = min(max(v, 0), Nx - 1), cy likewise (hvq_rank_pictures' clamps): the border replicates the edge sample, and a
+ *              clamped coordinate counts as often as it occurs.
+ *   Weights.   For j in [-ry, ry] and i in [-rx, rx]: q = (cy(y + j), cx(x + i)), w(j, i) = spatial[|j|][|i|] * range[ |g[q] - g[y][x]| ].
+ *              Both factors are uint8, so w <= 65025.
+ *   Value.     den = sum w, num = sum w * a[q], out = (num + den / 2) / den: floor of the quotient, one rounding, half up.  No clamp is
+ *              needed: a weighted mean of bytes is a byte.
+ *   32 bits.   With radius 7 the window has 225 taps and the largest num + den / 2 is 225 * 65025 * 255 + 7315312 = 3738124687 < 2^32:
+ *              every intermediate fits uint32.
+ *   Limits.    rx, ry each 0 .. HVQ_BIL_MAX_RADIUS, independently.  spatial[0][0] >= 1 and range[0] >= 1: the centre tap then has a
+ *              weight, so den >= 1 always.  pad is 0.  Entries of spatial outside [0, ry] x [0, rx] are not read.  A zero in spatial
+ *              switches a tap off: a disc is a table with zero corners.
+ *   Guide.     guide == NULL, or guide[i] == {-1, 0, NULL}: the picture guides itself.  Otherwise HvqMetricsRef's two non-trivial forms,
+ *              with hvq_picture_metrics' checks and texts: stream >= 0 -- a resident picture of the source's geometry, no pointer; stream
+ *              -1 with a pointer that is a multiple of 16 -- the caller's device memory in slot layout.  A guide of another geometry
+ *              refuses the call.  A guide that belongs to the batch in flight ends that batch, as a source does.
+ *   Known answers.  Radius 0 copies the plane.  A flat plane stays flat under any tables.  A range table with only range[0] != 0 copies the
+ *              plane under any radius and spatial table.  range all ones and spatial all ones is the box mean with replicated borders,
+ *              rounded half up.  {0, 1, 0} under spatial[0] = {2, 1}, ry = 0 and a flat range table gives 1 at its centre (2 / 4 rounds
+ *              up).  A two-level step of 40 | 200 under range[d] = 0 for d >= 100 is left byte for byte as it is, at radius 7 with every
+ *              other weight 255.  A flat guide makes the call a linear filter: with the spatial quadrant {4, 2; 2, 1} it is the 3 x 3
+ *              binomial of hvq_filter_pictures exactly.  A picture guided by a copy of itself equals the unguided call.  Transposing the
+ *              plane, the radii and spatial transposes the result; mirroring the plane mirrors it.
+ *   hvq_bilateral_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL record or, in either plane: a radius outside 0 ..
+ *              HVQ_BIL_MAX_RADIUS; spatial[0][0] == 0; range[0] == 0; a pad that is not 0.
+ *   The call.  Output i has the geometry of its source, in slot layout (Y | U | V tightly packed): dst[i] is a non-null DEVICE pointer,
+ *              a multiple of 16, of hvq_stream_pic_bytes bytes.  Exactly those bytes are written, each once and whatever was there
+ *              before; nothing outside them is written (no memset, no atomics).  dst[i] must not overlap any source or guide of the
+ *              call: the caller's business, not checked.  which[i] selects sets[which[i]]; which == NULL: sets[0] for all.  nsets is
+ *              1 .. HVQ_BIL_MAX_SETS; every entry of the table is checked, used or not.
+ *   Bodies.    A plane of radius 0 in both axes takes the kernel's copy body, every other the general one.  The values do not depend on
+ *              it.  hvq_bilateral_force_general(ctx, 1) makes every later call of the context run the planes of radius 0 through the
+ *              general body (0: the chosen one again) and returns the setting before: for tests that compare the two with ==.
+ *   HVQ_E_ARG for the whole call: what hvq_bilateral_check refuses; nsets outside 1 .. 64; a which[i] outside 0 .. nsets - 1; a null or
+ *              misaligned dst[i]; n above 65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no multiple
+ *              of 16; a guide with a stream and a pointer, of another geometry, of a stream below -1 or with a misaligned pointer; a NULL
+ *              context, sets or dst.  n == 0 is HVQ_OK and does nothing.  Every argument is checked before anything is enqueued: a
+ *              refused call leaves every destination untouched.  HVQ_E_NOGPU (after those checks) from a build without the bilateral
+ *              kernel.
+ *   a_i and `src` are hvq_picture_checksums'; lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain,
+ *   slot safety and ending the batch in flight only when a requested picture belongs to it are hvq_scale_pictures'. */
+#define HVQ_BIL_MAX_RADIUS 7
+#define HVQ_BIL_MAX_SETS   64
+typedef struct HvqBilateralPlane { int32_t rx, ry, pad[2]; uint8_t spatial[8][8]; uint8_t range[256]; } HvqBilateralPlane;  /* 336 bytes */
+typedef struct HvqBilateral      { HvqBilateralPlane luma, chroma; } HvqBilateral;  /* chroma serves U and V, at their own resolution */
+int     hvq_bilateral_check(const HvqBilateral *b);
+int     hvq_bilateral_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                               const HvqMetricsRef *guide, const HvqBilateral *sets, int nsets, const int *which,
+                               void *const *dst, void *hip_stream);
+int     hvq_bilateral_force_general(HvqContext *ctx, int on);
+
 /* Resident pictures through LOOKUP TABLES -- a point operation, out = table[in] -- into uint8 pictures of THEIR OWN geometry in slot
  * layout, where they lie: for `n` pictures, of any streams, sizes and samplings, in one kernel launch on the caller's HIP stream and
  * without a host synchronisation.  Equalisation, levels, gamma, inversion, posterising and binarisation are tables (hvqm4_amd.maps
