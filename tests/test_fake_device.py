@@ -261,7 +261,7 @@ def test_flush_timing_lines_say_what_the_plan_says(drivers, L, tmp_path):
     (coverage.levels) -- every line must match the expression that test imports and say what hvq_recon_inline_plan says for the fullest
     tile of the level's blob headers."""
     from tests import clips, coverage
-    from tests.test_gpu_shapes import launch_lines
+    from tests.gpu_kit import launch_lines
     r, out = run_driver(drivers["plain"], "seven", {"HVQM4_AMD_FLUSH_TIMING": "1"}, "eager", tmp_path)
     check_run(r, out, "seven")
     flushes, lines = [], []

@@ -4,71 +4,31 @@ include/hvqm4_amd.h -- and against footprints painted without any window arithme
 256 sentinel bytes before and behind it, which must stay untouched.  The shapes are those of the golden clips: 64 x 48 4:2:0, 48 x 64
 4:4:4 and 296 x 160 4:2:2, whose chroma planes are 148 wide, so that every plane crosses a seam of the kernel's 64-column tiles; the
 smallest geometry hvq_stream_open accepts; 8 x 8.  The cases run in ONE child process that imports torch first (see
-tests/test_gpu_export.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more is started on
+tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more is started on
 a GPU that has reported a fault."""
-import json
 import os
-import subprocess
 import sys
-import traceback
 import zlib
 
 import numpy as np
 import pytest
 
+from tests import gpu_child, gpu_kit
+from tests.gpu_kit import ROOT, SENTINEL, check_bytes as _check, clip as _clip, decode as _decode, geom as _geom, golden as _golden
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
-SENTINEL = 0xA5
-GUARD = 256
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
-def _clip(name):
-    return open(os.path.join(ROOT, "tests", "golden", name + ".h4m"), "rb").read()
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
-
-
-def _geom(hdr):
-    return (hdr.width, hdr.height, hdr.h_samp, hdr.v_samp)
-
-
-def _rooms(torch, nb, uniform):
-    """out for Context.bilateral_pictures with GUARD sentinel bytes before and behind every allocation -> (out, guards): one tensor
-    [n, bytes] when the geometries are one, a list otherwise"""
-    n = len(nb)
-    if uniform:
-        room = torch.full((n * nb[0] + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
-        return room[GUARD:GUARD + n * nb[0]].view(n, nb[0]), [room[:GUARD], room[GUARD + n * nb[0]:]]
-    rooms = [torch.full((b + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda") for b in nb]
-    return [r[GUARD:GUARD + b] for r, b in zip(rooms, nb)], [r[:GUARD] for r in rooms] + [r[GUARD + b:] for r, b in zip(rooms, nb)]
-
-
 def _bil(torch, ctx, sids, ords, bil, src=None, guide=None, steps=None):
     """one call (or smooth_pictures with `steps`) into guarded rooms -> (list of uint8 tensors, guards)"""
     uniform = len({ctx._geometry(s) for s in set(sids)}) <= 1
-    out, guards = _rooms(torch, [ctx.pic_bytes(s) for s in sids], uniform)
+    out, guards = gpu_kit.rooms(torch, [ctx.pic_bytes(s) for s in sids], uniform)
     got = ctx.smooth_pictures(sids, ords, steps, guide=guide, out=out) if steps is not None else ctx.bilateral_pictures(sids, ords, bil, guide, src, out)
     assert got is out
     return [out[i] for i in range(len(sids))], guards
-
-
-def _check(torch, got, guards, wants, what):
-    for g in guards:
-        assert g.numel() == GUARD and bool(g.eq(SENTINEL).all()), f"{what}: the bytes around an output were written"
-    assert len(got) == len(wants), what
-    for i, (g, w) in enumerate(zip(got, wants)):
-        g = g.cpu().numpy()
-        w = np.frombuffer(w, dtype=np.uint8) if isinstance(w, bytes) else np.asarray(w, dtype=np.uint8).reshape(-1)
-        assert g.shape == w.shape, (what, i, g.shape, w.shape)
-        if not np.array_equal(g, w):
-            bad = np.flatnonzero(g != w)
-            raise AssertionError(f"{what}: picture {i}: {bad.size} of {g.size} bytes differ, first at {bad[0]}: got {g[bad[0]]}, want {w[bad[0]]}")
 
 
 _expected = {}
@@ -93,17 +53,7 @@ def _general(torch, ctx, sids, ords, bils, src, guide, got, what):
     _check(torch, again, guards, [g.cpu().numpy() for g in got], what + ": the general body everywhere")
 
 
-class _Uploaded:
-    """pictures in the caller's memory (src=), on streams that nothing was decoded into"""
-
-    def __init__(self, torch, ctx, pics, geoms):
-        self.ctx, self.pics, self.geoms, self.by_geom = ctx, pics, list(geoms), {}
-        for g in geoms:
-            if g not in self.by_geom:
-                self.by_geom[g] = ctx.open_stream(g[0], g[1], g[2], g[3], True, 3)
-        self.sids = [self.by_geom[g] for g in geoms]
-        self.bufs = [torch.from_numpy(np.array(p, dtype=np.uint8)).cuda() for p in pics]
-
+class _Uploaded(gpu_kit.Uploaded):
     def run(self, torch, bils, what, wants=None, general=False, guides=None):
         """the pictures in ONE call, bils[i] for picture i (guides[i]: None or a picture as numpy bytes), compared with `wants`
         (default: the module's bytes)"""
@@ -118,16 +68,11 @@ class _Uploaded:
             _general(torch, self.ctx, self.sids, [-1] * n, bils, self.bufs, gbufs, got, what)
         return got
 
-    def close(self):
-        for s in self.by_geom.values():
-            self.ctx.close_stream(s)
-
 
 def case_golden(torch, ctx):
     """every golden clip's pictures under the five shared sets and the identity, and all of it again with the copy body switched off"""
     from hvqm4_amd import bilateral as B
     from tests import bilateral_cases as cases
-    from tests.test_gpu_export import _golden
     samplings = set()
     sets = [b for _l, b in cases.FIVE] + [B.identity()]
     assert sets[0] == B.bilateral(1.5, 12) and sets[1] == B.sigma_filter(2, 10) and sets[2] == B.box((3, 1)) and sets[3] == B.disc(3) and B.copies(sets[4].chroma)
@@ -417,45 +362,10 @@ def case_tools(torch, ctx):
 CASES = ["golden", "seams", "narrow", "arithmetic", "guides", "planes", "many", "sources", "refusals", "tools"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bilateral") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_bilateral import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "bilateral", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_bilateral(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

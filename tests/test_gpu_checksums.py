@@ -1,23 +1,21 @@
 """GPU: picture checksums (hvq_picture_checksums, Context.picture_checksums) against tests/golden/checksums.json (the reference's pictures
 through zlib) and against tests/checksums_ref.py on arbitrary bytes, compared with ==.  Nothing is read back except where a case says so.
-The cases run in ONE child process that imports torch first (see tests/test_gpu_export.py); each test reports its case.  The child stops
+The cases run in ONE child process that imports torch first (see tests/gpu_child.py); each test reports its case.  The child stops
 at the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a fault."""
 import json
 import os
-import subprocess
-import sys
-import traceback
 import zlib
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import ROOT, SEVEN_CLIPS as CLIPS, clip as _clip, decode as _decode
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
 SENTINEL = 0x5A5A5A5A5A5A5A5A
-CLIPS = ["ragged24x40", "gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "wide296x160", "natural128x96", "pselfref64x48_15"]
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
@@ -28,15 +26,6 @@ def _fixture():
     if "fixture" not in _cache:
         _cache["fixture"] = json.load(open(os.path.join(ROOT, "tests", "golden", "checksums.json")))["clips"]
     return _cache["fixture"]
-
-
-def _clip(name):
-    return open(os.path.join(ROOT, "tests", "golden", name + ".h4m"), "rb").read()
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
 
 
 def _same(got, wants, what):
@@ -250,45 +239,10 @@ def case_refusals(torch, ctx):
 CASES = ["goldens", "caller_memory", "consistency", "determinism", "ordering", "refusals"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("checksums") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_checksums import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "checksums", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_checksums(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

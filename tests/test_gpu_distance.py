@@ -4,23 +4,21 @@ tests/test_distance_cpu.py holds equal to tests/distance_ref.py, the plain-Pytho
 The planes and masks are tests/distance_cases.py's: the smallest planes, planes just past a column group, a row group and a mask tile,
 72 x 24 in the three samplings with each plane, rows of 8192, one background sample in a corner of 200 x 136, every metric under both
 borders, 60 mixed pictures under 64 rules.  Every output is allocated with 256 sentinel bytes before and behind it, which must stay
-untouched.  The cases run in ONE child process that imports torch first (see tests/test_gpu_export.py); each test reports its case.  The
+untouched.  The cases run in ONE child process that imports torch first (see tests/gpu_child.py); each test reports its case.  The
 child stops at the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a fault."""
 import json
 import os
-import subprocess
 import sys
-import traceback
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import GUARD, ROOT, SENTINEL, Uploaded as _Uploaded, decode as _decode, golden as _golden
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
-SENTINEL = 0xA5
-GUARD = 256
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
@@ -58,22 +56,6 @@ def _check(torch, maps, guards, wants, what):
         if not np.array_equal(got, want):
             bad = np.argwhere(got != want)
             raise AssertionError(f"{label}: {bad.shape[0]} of {got.size} distances differ, first at (y, x) = {tuple(bad[0])}: got {got[tuple(bad[0])]}, want {want[tuple(bad[0])]}")
-
-
-class _Uploaded:
-    """pictures in the caller's memory (src=), on streams that nothing was decoded into"""
-
-    def __init__(self, torch, ctx, pics, geoms):
-        self.ctx, self.pics, self.geoms, self.by_geom = ctx, pics, list(geoms), {}
-        for g in geoms:
-            if g not in self.by_geom:
-                self.by_geom[g] = ctx.open_stream(g[0], g[1], g[2], g[3], True, 3)
-        self.sids = [self.by_geom[g] for g in geoms]
-        self.bufs = [torch.from_numpy(np.array(p, dtype=np.uint8)).cuda() for p in pics]
-
-    def close(self):
-        for s in self.by_geom.values():
-            self.ctx.close_stream(s)
 
 
 def _run_cases(torch, ctx, cs):
@@ -208,7 +190,6 @@ def case_chain(torch, ctx):
     from hvqm4_amd import distance as D
     from hvqm4_amd import labels as L
     from hvqm4_amd import maps as M
-    from tests.test_gpu_export import _decode, _golden
     fixture = json.load(open(os.path.join(ROOT, "tests", "golden", "distance.json")))["clips"]
     seen = 0
     for name, data, _hdr, _n in _golden():
@@ -344,45 +325,10 @@ def case_tools(torch, ctx):
 CASES = ["small", "tiles", "far", "wide", "mixed", "mask", "morph", "chain", "refusals", "tools"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("distance") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_distance import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "distance", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_distance(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

@@ -1,20 +1,16 @@
-"""GPU: picture export into torch tensors (hvq_export_pictures, Context.export), tolerance 0 everywhere.
-
-Torch brings its own HIP runtime, and a stream handle of torch's means something to the library only when both share one runtime:
-torch must be imported before the library is loaded (hvqm4_amd.export.check_one_hip_runtime).  The main suite loads the library long
-before this file runs, so the cases run in ONE child process that imports torch first; each test reports its case."""
-import json
+"""GPU: picture export into torch tensors (hvq_export_pictures, Context.export), tolerance 0 everywhere.  The cases run in ONE child
+process that imports torch first (see tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP
+error: nothing more is started on a GPU that has reported a fault."""
 import os
-import subprocess
-import sys
-import traceback
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import decode as _decode, golden as _golden, long_clip as _long_clip, pics as _pics, self_ref_clip as _self_ref_clip
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FMTS = ("rgb", "rgbp", "yuv444p")
 CHILD_TIMEOUT = 900
 
@@ -28,28 +24,11 @@ def _alloc(torch, geom, fmt, n=None, fill=0):
     return torch.full(shape, fill, dtype=torch.uint8, device="cuda")
 
 
-def _decode(ctx, data, nslots=None):
-    """a clip through the batched path: (sid, header, number of pictures)"""
-    from hvqm4_amd.container import parse_header, video_pictures
-    hdr = parse_header(data)
-    pics = list(video_pictures(data))
-    sid = ctx.open_stream(hdr.width, hdr.height, hdr.h_samp, hdr.v_samp, hdr.is15, nslots or len(pics) + 3)
-    for ft, _d, p in pics:
-        ctx.submit(sid, ft, p)
-    ctx.flush()
-    return sid, hdr, len(pics)
-
-
 def _want(data, n, hdr, fmt):
     from oracle import bridge
     from tests.test_export_cpu import export_reference
     yuv = bridge.oracle_decode(data, n)
     return np.stack([export_reference(yuv[k], hdr.width, hdr.height, hdr.h_samp, hdr.v_samp, fmt) for k in range(n)])
-
-
-def _golden():
-    from tests.test_export_cpu import golden_clips
-    return list(golden_clips())
 
 
 def case_goldens(torch, ctx):
@@ -121,11 +100,6 @@ def case_pitched(torch, ctx):
         ctx.close_stream(sid)
 
 
-def _long_clip():
-    from hvqm4_amd.synth import SynthConfig, make_clip
-    return make_clip(SynthConfig(width=640, height=480, gop="IPBBPBBPBBPB", seed=61))
-
-
 def case_no_host_sync(torch, ctx):
     from hvqm4_amd.container import parse_header, video_pictures
     from oracle import bridge
@@ -192,7 +166,6 @@ def case_refusals(torch, ctx):
     import ctypes as C
     from hvqm4_amd._lib import HVQ_E_ARG, HVQ_E_STATE, HvqError, lib
     from hvqm4_amd.export import HvqExportDst
-    from tests.test_gpu_reject import _pics, _self_ref_clip
     g = {name: (data, hdr, n) for name, data, hdr, n in _golden()}
     data, hdr, n = g["gop64x48_15"]
     w, h = hdr.width, hdr.height
@@ -268,35 +241,10 @@ def case_one_hip_runtime(torch, ctx):
 CASES = ["goldens", "mixed_batch", "pitched", "no_host_sync", "close_after_export", "refusals", "one_hip_runtime"]
 
 
-def _child(out_path):
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    res = {}
-    ctx = batch.Context(0)
-    for name in CASES:
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception:
-            res[name] = traceback.format_exc()
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("export") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_export import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    return res
+child_results = gpu_child.results_fixture(__name__, "export", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_export(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

@@ -1,22 +1,18 @@
 """GPU: antialiased float export (hvq_export_resampled with HVQ_FILTER_TRIANGLE, Context.export_float(antialias=True)) against
 tests/export_aa_ref.py, tolerance 0: every comparison but torch_sanity is of raw bits.  The cases run in ONE child process that
-imports torch first (see tests/test_gpu_export.py); each test reports its case.  Unlike the child of tests/test_gpu_export_float.py
-this one stops at the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a fault.
+imports torch first (see tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error:
+nothing more is started on a GPU that has reported a fault.
 
 Which body of the kernel a geometry takes (tiled: LDS, one barrier; direct: nested tap loops) is the host's decision,
 hvq_resample_tile_rows; the cases assert through it that both ran, and body_agreement runs the same geometries through both."""
-import json
-import os
-import subprocess
-import sys
-import traceback
-
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import decode as _decode, golden_by_name as _golden, long_clip as _long_clip
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = ("float32", "float16", "bfloat16")
 CHILD_TIMEOUT = 420                                 # the cases take about a minute together; a hung child is ended, not waited for
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -24,16 +20,6 @@ SENTINEL = -7.5                                     # exact in all three types
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
-def _golden():
-    from tests.test_export_cpu import golden_clips
-    return {name: (data, hdr, n) for name, data, hdr, n in golden_clips()}
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
-
-
 def _norm():
     from hvqm4_amd.export import normalisation
     return normalisation(MEAN, STD, 1 / 255)
@@ -315,7 +301,6 @@ def case_chain(torch, ctx):
     from hvqm4_amd.container import parse_header, video_pictures
     from oracle import bridge
     from tests.export_float_ref import export_float_reference
-    from tests.test_gpu_export import _long_clip
     clip = _long_clip()
     hdr = parse_header(clip.data)
     pics = [(ft, bytes(p)) for ft, _d, p in video_pictures(clip.data)]
@@ -383,50 +368,10 @@ CASES = ["goldens_identity", "downscale", "body_agreement", "upscale", "mixed_ba
          "torch_sanity"]
 
 
-def _gpu_error(exc) -> bool:
-    """HVQ_E_HIP from the library, or a HIP error torch reports: the GPU may have faulted, nothing more is started on it"""
-    from hvqm4_amd._lib import HVQ_E_HIP, HvqError
-    if isinstance(exc, HvqError):
-        return exc.code == HVQ_E_HIP
-    text = str(exc)
-    return isinstance(exc, RuntimeError) and ("HIP error" in text or "hipError" in text or "CUDA error" in text)
-
-
-def _child(out_path):
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("export_aa") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_export_aa import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "export_aa", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_export_aa(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

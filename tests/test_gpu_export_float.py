@@ -1,19 +1,16 @@
 """GPU: float export (hvq_export_tensors, Context.export_float) against tests/export_float_ref.py, tolerance 0: every comparison is
-of raw bits.  The cases run in ONE child process that imports torch first (see tests/test_gpu_export.py); each test reports its case.
+of raw bits.  The cases run in ONE child process that imports torch first (see tests/gpu_child.py); each test reports its case.  The
+child stops at the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a fault.
 
 The wide geometry (1280 samples, coordinates above 2^10) is synthesised here: tests/clips.py holds nothing that wide."""
-import json
-import os
-import subprocess
-import sys
-import traceback
-
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import decode as _decode, golden_by_name as _golden, long_clip as _long_clip, pics as _pics, self_ref_clip as _self_ref_clip
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = ("float32", "float16", "bfloat16")
 CHILD_TIMEOUT = 900
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -21,16 +18,6 @@ SENTINEL = -7.5                                     # exact in all three types
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
-def _golden():
-    from tests.test_export_cpu import golden_clips
-    return {name: (data, hdr, n) for name, data, hdr, n in golden_clips()}
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
-
-
 def _norm(mean=MEAN, std=STD, scale=1 / 255):
     from hvqm4_amd.export import normalisation
     return normalisation(mean, std, scale)
@@ -198,7 +185,6 @@ def case_no_host_sync(torch, ctx):
     from hvqm4_amd.container import parse_header, video_pictures
     from oracle import bridge
     from tests.test_export_cpu import export_reference
-    from tests.test_gpu_export import _long_clip
     clip = _long_clip()
     hdr = parse_header(clip.data)
     pics = [(ft, bytes(p)) for ft, _d, p in video_pictures(clip.data)]
@@ -266,7 +252,6 @@ def case_refusals(torch, ctx):
     from hvqm4_amd.container import video_pictures
     from hvqm4_amd.export import HvqTensorDst
     from tests.export_float_ref import bits_of
-    from tests.test_gpu_reject import _pics, _self_ref_clip
     data, hdr, n = _golden()["gop64x48_15"]
     w, h = hdr.width, hdr.height
 
@@ -378,35 +363,10 @@ def case_torch_sanity(torch, ctx):
 CASES = ["goldens", "resampled", "mixed_batch", "pitched", "store_forms", "no_host_sync", "refusals", "torch_sanity"]
 
 
-def _child(out_path):
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    res = {}
-    ctx = batch.Context(0)
-    for name in CASES:
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception:
-            res[name] = traceback.format_exc()
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("export_float") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_export_float import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    return res
+child_results = gpu_child.results_fixture(__name__, "export_float", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_export_float(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

@@ -1,56 +1,29 @@
 """GPU: filtered pictures in slot layout (hvq_filter_pictures / Context.filter_pictures) against hvqm4_amd.filters.of_picture, compared
 with == (tests/test_filters_cpu.py compares that module with tests/filter_ref.py, the plain-Python restatement of include/hvqm4_amd.h).
 Every output is allocated with 256 sentinel bytes before and behind it, which must stay untouched.  The cases run in ONE child process
-that imports torch first (see tests/test_gpu_export.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP
+that imports torch first (see tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP
 error: nothing more is started on a GPU that has reported a fault."""
 import json
 import os
-import subprocess
-import sys
-import traceback
 import zlib
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import ROOT, SENTINEL, check_bytes as _check, clip as _clip, decode as _decode, geom as _geom, geometry_rooms as _rooms
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
-SENTINEL = 0xA5
-GUARD = 256
 SAMPLINGS = ((2, 2), (2, 1), (1, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
-def _clip(name):
-    return open(os.path.join(ROOT, "tests", "golden", name + ".h4m"), "rb").read()
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
-
-
-def _geom(hdr):
-    return (hdr.width, hdr.height, hdr.h_samp, hdr.v_samp)
-
-
 def _nbytes(g):
     from hvqm4_amd import scale
     return scale.nbytes(*g)
-
-
-def _rooms(torch, geoms, as_list=False):
-    """out for Context.filter_pictures with GUARD sentinel bytes before and behind every allocation -> (out, guards)"""
-    nb = [_nbytes(g) for g in geoms]
-    n = len(geoms)
-    if n and not as_list and all(g == geoms[0] for g in geoms):
-        room = torch.full((n * nb[0] + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
-        return room[GUARD:GUARD + n * nb[0]].view(n, nb[0]), [room[:GUARD], room[GUARD + n * nb[0]:]]
-    rooms = [torch.full((b + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda") for b in nb]
-    return [r[GUARD:GUARD + b] for r, b in zip(rooms, nb)], [r[:GUARD] for r in rooms] + [r[GUARD + b:] for r, b in zip(rooms, nb)]
 
 
 def _filter(torch, ctx, sids, ords, geoms, filt, src=None):
@@ -59,19 +32,6 @@ def _filter(torch, ctx, sids, ords, geoms, filt, src=None):
     got = ctx.filter_pictures(sids, ords, filt, src, out)
     assert got is out
     return [out[i] for i in range(len(geoms))], guards
-
-
-def _check(torch, got, guards, wants, what):
-    for g in guards:
-        assert g.numel() == GUARD and bool(g.eq(SENTINEL).all()), f"{what}: the bytes around an output were written"
-    assert len(got) == len(wants), what
-    for i, (g, w) in enumerate(zip(got, wants)):
-        g = g.cpu().numpy()
-        w = np.asarray(w, dtype=np.uint8).reshape(-1)
-        assert g.shape == w.shape, (what, i, g.shape, w.shape)
-        if not np.array_equal(g, w):
-            bad = np.flatnonzero(g != w)
-            raise AssertionError(f"{what}: picture {i}: {bad.size} of {g.size} bytes differ, first at {bad[0]}: got {g[bad[0]]}, want {w[bad[0]]}")
 
 
 def _contents(g, seed):
@@ -456,45 +416,10 @@ def case_bodies(torch, ctx):
 CASES = ["identity", "seams", "narrow", "orientation", "signed", "chroma", "many", "sources", "golden", "composition", "ordering", "refusals", "bodies"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("filters") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_filters import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "filters", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_filters(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

@@ -6,23 +6,21 @@ the plain-Python restatement of include/hvqm4_amd.h -- compared with ==.  The pl
 plane, 8192 x 8 for the carry across 32 chunks, the window's tile and planes past its seams, the checkerboard, all 0, all 255, random
 planes; every window of the list under every mode, k, c and invert; 60 mixed pictures under 64 rules; 300 rectangles; and the 8192 x 2064
 plane of 255 whose table wraps.  Every output is allocated with 256 sentinel bytes before and behind it, which must stay untouched.  The
-cases run in ONE child process that imports torch first (see tests/test_gpu_export.py); each test reports its case.  The child stops at
+cases run in ONE child process that imports torch first (see tests/gpu_child.py); each test reports its case.  The child stops at
 the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a fault."""
 import json
 import os
-import subprocess
 import sys
-import traceback
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import GUARD, ROOT, SENTINEL, Uploaded as _uploaded, decode as _decode, golden as _golden
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
-SENTINEL = 0xA5
-GUARD = 256
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
@@ -88,11 +86,6 @@ def _check_bytes(got, guards, wants, what):
             bad = np.flatnonzero(g != w)
             label = what[i] if isinstance(what, list) else f"{what}: picture {i}"
             raise AssertionError(f"{label}: {bad.size} of {g.size} bytes differ, first at {bad[0]}: got {g[bad[0]]}, want {w[bad[0]]}")
-
-
-def _uploaded(torch, ctx, pics, geoms):
-    from tests.test_gpu_distance import _Uploaded
-    return _Uploaded(torch, ctx, pics, geoms)
 
 
 def case_tables(torch, ctx):
@@ -207,7 +200,6 @@ def case_chain(torch, ctx):
     from hvqm4_amd import integral as I
     from hvqm4_amd import labels as L
     from hvqm4_amd import rank as R
-    from tests.test_gpu_export import _decode, _golden
     fixture = json.load(open(os.path.join(ROOT, "tests", "golden", "integral.json")))
     rule = I.adaptive(5, c=7, k=51)
     assert fixture["windows"]["adaptive_5_c7_k51"] == [rule.mode, rule.rx, rule.ry, rule.k, rule.c, rule.invert]
@@ -366,45 +358,10 @@ def case_tools(torch, ctx):
 CASES = ["tables", "windows", "mixed", "rects", "wrap", "chain", "refusals", "tools"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("integral") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_integral import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "integral", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_integral(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

@@ -1,19 +1,15 @@
 """GPU: JPEG files of resident pictures (hvq_encode_jpeg, Context.encode_jpeg) against tests/jpeg_ref.py on the oracle's pictures and on
 caller memory of chosen content, compared with == on bytes: the file is specified exactly.  The cases run in ONE child process that imports
-torch first (see tests/test_gpu_export.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more
+torch first (see tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more
 is started on a GPU that has reported a fault."""
-import json
-import os
-import subprocess
-import sys
-import traceback
-
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import decode as _decode, golden_by_name as _golden, long_clip_data as _long_clip, oracle as _oracle
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
 SENTINEL = 0x5A
 GUARD = 64                                          # bytes on either side of a destination
@@ -21,8 +17,6 @@ SIX = ["gop64x48_15", "yuv422_296x160", "yuv444_13_portrait48x64", "ragged24x40"
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
-from tests.test_gpu_metrics import _decode, _golden, _gpu_error, _long_clip, _oracle          # noqa: E402  (shared child-side helpers)
-
 _state = {}
 
 
@@ -252,44 +246,10 @@ def case_ordering(torch, ctx):
 CASES = ["goldens", "qualities", "content", "wide", "overflow", "refusals", "ordering"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("jpeg") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_jpeg import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "jpeg", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_jpeg(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

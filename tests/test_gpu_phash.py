@@ -1,20 +1,19 @@
 """GPU: perceptual hashes and nearest-hash search (hvq_picture_hashes / Context.picture_hashes, hvq_hash_nearest / Context.hash_nearest)
 against tests/golden/phash.json (tests/phash_ref.py on the reference's pictures), against tests/phash_ref.py on arbitrary bytes, and
 against hvqm4_amd.phash.nearest, compared with ==.  The cases run in ONE child process that imports torch first (see
-tests/test_gpu_export.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more is started on a
+tests/gpu_child.py); each test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more is started on a
 GPU that has reported a fault."""
 import json
 import os
-import subprocess
-import sys
-import traceback
 
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import ROOT, SEVEN_CLIPS as CLIPS, clip as _clip, decode as _decode
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
 SENTINEL = 0x5A5A5A5A5A5A5A5A
 SENTINEL32 = 0x5A5A5A5A
@@ -29,15 +28,6 @@ def _fixture():
         clips = json.load(open(os.path.join(ROOT, "tests", "golden", "phash.json")))["clips"]
         _cache["fixture"] = {nm: [[int(a, 16), int(d, 16), int(p, 16), s] for a, d, p, s in rows] for nm, rows in clips.items()}
     return _cache["fixture"]
-
-
-def _clip(name):
-    return open(os.path.join(ROOT, "tests", "golden", name + ".h4m"), "rb").read()
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
 
 
 def _same(got, wants, what):
@@ -65,7 +55,6 @@ def case_goldens(torch, ctx):
     """the seven golden clips of tests/test_gpu_checksums.py, all three samplings, in ONE call, their pictures interleaved: a plane
     narrower than the grid (24 wide: 8-byte units, a sample feeds two cells), fractional cells (296 / 32 = 9.25 and 296 / 9), n = 1 and
     n = 0.  Records == the fixture; sum_y == sum_a of plane Y from picture_metrics on the same call list.  No picture is read back"""
-    from tests.test_gpu_checksums import CLIPS
     assert len(CLIPS) == 7
     fix = _fixture()
     streams, samplings, widths = [], set(), set()
@@ -369,45 +358,10 @@ def case_end_to_end(torch, ctx):
 CASES = ["goldens", "caller_memory", "cells64", "nearest", "nearest_columns", "refusals", "ordering", "end_to_end"]
 
 
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    from tests.test_gpu_metrics import _gpu_error
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("phash") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_phash import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "phash", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_phash(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)

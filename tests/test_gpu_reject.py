@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import clips
+from tests.gpu_kit import pics as _pics, self_ref_clip as _self_ref_clip
 
 pytestmark = pytest.mark.gpu
 
@@ -20,34 +21,6 @@ def _long_run_clip(seed=5, w=64, h=48, gop="IPBBPB"):
     """a clip whose SECOND picture (the first P) carries an overflow-symbol run of 5000 symbols: over the fast parsers' cap"""
     from hvqm4_amd.synth import SynthConfig, make_clip
     return make_clip(SynthConfig(width=w, height=h, gop=gop, seed=seed, long_escape_pb=5000))
-
-
-class _Patched:
-    """a clip with one picture replaced (what the container iterator would hand out)"""
-    def __init__(self, clip, pics):
-        self.width, self.height, self.version, self.data, self.n_pictures, self.pics = clip.width, clip.height, clip.version, clip.data, clip.n_pictures, pics
-
-
-def _self_ref_clip(seed=5, w=64, h=48, gop="IPBBPB"):
-    """a clip whose SECOND picture (the first P) can never be decoded like the reference: its luma DC tree is a single leaf 0x7F
-    with dc_shift 0, outside the overflow window (-128, 127) -- every overflow read of the section spins for ever"""
-    import struct
-    from hvqm4_amd.synth import SynthConfig, make_clip
-    clip = make_clip(SynthConfig(width=w, height=h, gop=gop, seed=seed))
-    pics = _pics(clip)
-    b = bytearray(pics[1][1])
-    off = 8 + 0x44 + struct.unpack_from(">I", b, 8 + 4 * 4)[0] + 4           # section 4 = DC buffer of the luma plane
-    b[0] = 0
-    b[off:off + 2] = b"\x3f\x80"
-    pics[1] = (pics[1][0], bytes(b))
-    return _Patched(clip, pics)
-
-
-def _pics(cl):
-    from hvqm4_amd.container import video_pictures
-    if hasattr(cl, "pics"):
-        return list(cl.pics)
-    return [(ft, bytes(p)) for ft, _d, p in video_pictures(cl.data)]
 
 
 def test_host_parsed_capped_picture_is_refused_and_the_stream_resumes_at_an_I_picture(gpu_ctx):

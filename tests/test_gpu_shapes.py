@@ -1,7 +1,7 @@
 """GPU: the witness of tests/test_launch_coverage.py.  That file predicts, from blob headers and hvq_recon_inline_plan, which instantiation
 of hvq_recon_inline_kernel every picture of clips.SHAPES and manybases320x240 is launched in; here the runtime says which it launched.
 
-A child process per forced shape (HVQM4_AMD_TILES_PER_WG is read once per process; torch imported first, see tests/test_gpu_export.py)
+A child process per forced shape (HVQM4_AMD_TILES_PER_WG is read once per process; torch imported first, see tests/gpu_child.py)
 decodes the clips with HVQM4_AMD_FLUSH_TIMING=1, one picture a flush, and writes a marker line to stderr before each flush: the runtime's
 `[flush] launch` line behind it belongs to that picture.  Every picture must equal the oracle (and the compiled reference where it is
 built), and the (tiles per workgroup, items cap, picture kind) seen must be the 15 cells of the one-tile run and the 27 of the two-tile
@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 
 from tests import clips
+from tests.gpu_child import gpu_error
+from tests.gpu_kit import launch_lines
 from tests.test_launch_coverage import survey
 from tests.test_recon_plan import L  # noqa: F401 -- the fixture: it asserts that the two environment caps are unset
 
@@ -26,22 +28,7 @@ WITNESS = clips.SHAPES + [c for c in clips.MEDIUM if c[0] == "manybases320x240"]
 ONE_BATCH = clips.SHAPES + [c for c in clips.SMALL if c[0] == "realistic128x96"]
 KIND = {0x10: "I", 0x20: "P", 0x30: "B"}
 
-# the runtime's line per launch under HVQM4_AMD_FLUSH_TIMING (hvq_runtime.cpp, flush_end); tests/test_fake_device.py pins it without a GPU
-LAUNCH_LINE = re.compile(r"^\[flush\] launch (?P<launch>\d+) \(level (?P<level>\d+), queue (?P<queue>\d+)\): fullest tile (?P<max_items>\d+) items, "
-                         r"(?P<max_pairs>\d+) pairs -> (?P<tpw>\d+) tile\(s\) per workgroup, items (?P<items>\d+), pairs (?P<pairs>\d+), pool (?P<pool>\d+), "
-                         r"(?P<lds>\d+) B of LDS = (?P<workgroups>\d+) workgroups per CU$")
 MARKER_LINE = re.compile(r"^\[witness\] (?P<clip>\S+) (?P<ordinal>\d+) (?P<kind>[IPB])$")
-
-
-def launch_lines(stderr):
-    """the `[flush] launch` lines of a run as dicts of integers; a line that starts like one and does not match the expression fails"""
-    out = []
-    for line in stderr.splitlines():
-        if line.startswith("[flush] launch"):
-            m = LAUNCH_LINE.match(line)
-            assert m, f"the runtime's launch line has changed: {line!r}"
-            out.append({k: int(v) for k, v in m.groupdict().items()})
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------- child side
@@ -50,7 +37,6 @@ def _child(out_path, one_batch):
     torch.cuda.init()
     from hvqm4_amd import batch
     from hvqm4_amd.container import parse_header, video_pictures
-    from tests.test_gpu_metrics import _gpu_error
     ctx = batch.Context(0)
     got = {}
     try:
@@ -72,7 +58,7 @@ def _child(out_path, one_batch):
             ctx.close_stream(sid)
     except Exception as e:
         traceback.print_exc()
-        if _gpu_error(e):
+        if gpu_error(e):
             print("stopped: the GPU reported an error", file=sys.stderr, flush=True)
             os._exit(3)                            # no further GPU call, not even the context's teardown
         raise

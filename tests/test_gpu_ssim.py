@@ -1,19 +1,15 @@
 """GPU: windowed SSIM (hvq_picture_ssim, Context.picture_ssim) against tests/ssim_ref.py on the oracle's pictures, records and maps
-compared with == on the raw bits.  The cases run in ONE child process that imports torch first (see tests/test_gpu_export.py); each
+compared with == on the raw bits.  The cases run in ONE child process that imports torch first (see tests/gpu_child.py); each
 test reports its case.  The child stops at the first HVQ_E_HIP or HIP error: nothing more is started on a GPU that has reported a
 fault."""
-import json
-import os
-import subprocess
-import sys
-import traceback
-
 import numpy as np
 import pytest
 
+from tests import gpu_child
+from tests.gpu_kit import decode as _decode, golden_by_name as _golden, long_clip_data as _long_clip, oracle as _oracle, synth as _synth
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300                                 # the cases take seconds each; a hung child is ended, not waited for
 SENTINEL = 0x5A5A5A5A5A5A5A5A
 GUARD = 64                                          # sentinel floats behind a map
@@ -21,26 +17,6 @@ GUARD = 64                                          # sentinel floats behind a m
 
 # ------------------------------------------------------------------------------------------------------------- child side
 _cache = {}
-
-
-def _golden():
-    if "golden" not in _cache:
-        from tests.test_export_cpu import golden_clips
-        _cache["golden"] = {name: (data, hdr, n) for name, data, hdr, n in golden_clips()}
-    return _cache["golden"]
-
-
-def _oracle(name, data, n):
-    """the oracle's pictures of a clip, decoded once for all cases"""
-    if ("yuv", name) not in _cache:
-        from oracle import bridge
-        _cache["yuv", name] = bridge.oracle_decode(data, n)
-    return _cache["yuv", name]
-
-
-def _decode(ctx, data, nslots=None):
-    from tests.test_gpu_export import _decode as dec
-    return dec(ctx, data, nslots)
 
 
 def _want(a, b, hdr, key=None):
@@ -73,18 +49,6 @@ def _same(got, maps, wants, what):
             bad = np.flatnonzero(flat != wants[i][1])
             raise AssertionError(f"{what}: pair {i}: {len(bad)} of {flat.size} map elements differ, first at {bad[0]}: got {flat[bad[0]]:#x}, "
                                  f"want {wants[i][1][bad[0]]:#x}")
-
-
-def _synth(width, height, gop, seed):
-    key = ("synth", width, height, gop, seed)
-    if key not in _cache:
-        from hvqm4_amd.synth import SynthConfig, make_clip
-        _cache[key] = make_clip(SynthConfig(width=width, height=height, gop=gop, seed=seed)).data
-    return _cache[key]
-
-
-def _long_clip():
-    return _synth(640, 480, "IPBBPBBPBBPB", 61)             # the clip of tests/test_gpu_metrics.py
 
 
 def case_goldens(torch, ctx):
@@ -358,53 +322,10 @@ def case_ordering(torch, ctx):
 CASES = ["goldens", "mixed_batch", "tile_edges", "overwrite_and_determinism", "refusals", "ordering"]
 
 
-def _gpu_error(exc) -> bool:
-    """HVQ_E_HIP from the library, or a HIP error torch reports: the GPU may have faulted, nothing more is started on it"""
-    from hvqm4_amd._lib import HVQ_E_HIP, HvqError
-    if isinstance(exc, HvqError):
-        return exc.code == HVQ_E_HIP
-    text = str(exc)
-    return isinstance(exc, RuntimeError) and ("HIP error" in text or "hipError" in text or "CUDA error" in text)
-
-
-def _child(out_path):
-    import time
-    import torch                                   # FIRST: the library then binds torch's HIP runtime
-    torch.cuda.init()
-    from hvqm4_amd import batch
-    res = {}
-    ctx = batch.Context(0)
-    stopped = False
-    for name in CASES:
-        t0 = time.time()
-        try:
-            globals()["case_" + name](torch, ctx)
-            res[name] = "ok"
-        except Exception as e:
-            res[name] = traceback.format_exc()
-            stopped = _gpu_error(e)
-        print(f"{name}: {time.time() - t0:.1f} s", flush=True)
-        with open(out_path, "w") as f:             # after every case: what a crash leaves is readable
-            json.dump(res, f)
-        if stopped:
-            print(f"stopped after {name}: the GPU reported an error", flush=True)
-            os._exit(3)                            # no further GPU call, not even the context's teardown
-    ctx.close()
-
-
 # ------------------------------------------------------------------------------------------------------------ parent side
-@pytest.fixture(scope="module")
-def child_results(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("ssim") / "results.json")
-    r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_ssim import _child; "
-                        f"_child({out!r})"], cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    res = json.load(open(out)) if os.path.exists(out) else {}
-    res["_log"] = f"exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
-    print(res["_log"])
-    return res
+child_results = gpu_child.results_fixture(__name__, "ssim", CHILD_TIMEOUT)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_ssim(case, child_results):
-    got = child_results.get(case)
-    assert got == "ok", got or f"the case did not run: {child_results['_log']}"
+    gpu_child.report(case, child_results)
