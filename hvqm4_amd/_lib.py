@@ -108,6 +108,10 @@ class HvqLabelRule(C.Structure):               # include/hvqm4_amd.h: the foregr
     _fields_ = [("plane", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("connectivity", C.c_int32)]
 
 
+class HvqCornerRule(C.Structure):              # include/hvqm4_amd.h: the plane, the measure (HVQ_CRN_*), the window radius, k, nms, margin, threshold
+    _fields_ = [(n, C.c_int32) for n in ("plane", "mode", "radius", "k", "nms", "margin")] + [("pad", C.c_int32 * 2), ("threshold", C.c_int64)]
+
+
 class HvqSelect(C.Structure):                   # an entry of hvq_select_components: inclusive ranges of area, box width and box height
     _fields_ = [(n, C.c_uint32) for n in ("area_min", "area_max", "w_min", "w_max", "h_min", "h_max", "invert", "pad")]
 
@@ -243,6 +247,11 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int, C.c_void_p]),
     "hvq_select_components": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "hvq_corner_check": (C.c_int, [C.c_void_p]),
+    "hvq_corner_rows_bytes": (C.c_int64, [C.c_int] * 5),
+    "hvq_corner_response_bytes": (C.c_int64, [C.c_int] * 5),
+    "hvq_corner_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "hvq_distance_check": (C.c_int, [C.c_void_p]),
     "hvq_distance_bytes": (C.c_int64, [C.c_int] * 5),
     "hvq_distance_pictures": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -924,6 +924,71 @@ class Context:
         check(lib().hvq_label_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_l, a_c, cap, stream))
         return labels, comps
 
+    def corner_pictures(self, sids, ordinals, rules=None, which=None, cap=1024, src=None, mask=None, points=None, rows=None, response=None):
+        """hvq_corner_pictures: the corners of one plane of the resident pictures (sids[i], ordinals[i]) -- the measure, the suppression
+        and the order of the list are include/hvqm4_amd.h's --, on torch's current stream, without a host synchronisation and without
+        moving a picture.  `rules`: one hvqm4_amd.corners.Rule (default corners.harris(): Y, radius 1, k 10, nms 3, threshold 1), a list
+        of one per picture (equal ones share an entry; more than 64 distinct ones: ValueError), or a list of distinct rules together
+        with `which`, one index per picture.  -> (mask, points, rows): lists of n CUDA tensors, mask[i] uint8 [pic_bytes] IN SLOT LAYOUT
+        (255 at the corners of the rule's plane; it goes wherever `src=` goes), points[i] int64 [cap + 1, 4] (row 0: K, stored, status,
+        0; row j: x, y, R, index, in raster order; rows beyond `stored` keep what they held), rows[i] int32 [Ny + 1] (the corners above
+        each row).  `response`: True, or a list of int64 [Ny, Nx] tensors: every R of the plane, returned as a fourth list.  `mask` /
+        `points` / `rows`, if given: such lists, contiguous, 16-byte aligned; `cap` is then the points' room.  hvqm4_amd.corners gives
+        the expected values (of_picture, response_of_plane) and reads the list (records, strongest, grid).  `src` as in
+        picture_checksums.  Ordering and slot safety are export()'s."""
+        import torch
+        from . import corners as cr
+        n = Context._pictures(self._geom, sids, ordinals, limit=True)
+        if which is not None:
+            table = [rules] if isinstance(rules, cr.Rule) else list(rules or ())
+            if not table or len(table) > cr.MAX_RULES:
+                raise ValueError(f"{len(table)} rules: one call takes 1 .. {cr.MAX_RULES}")
+            which = [int(k) for k in which]
+            if len(which) != n or any(not 0 <= k < len(table) for k in which):
+                raise ValueError(f"which: {n} indices into the {len(table)} rules")
+        else:
+            table, which = Context._table_which(cr.Rule() if rules is None else rules, n, cr.Rule, "rules", "corners.Rule", cr.MAX_RULES, "rules")
+        for r in table:
+            cr.check(r)
+        if isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap <= cr.MAX_CAP:
+            raise ValueError(f"cap {cap!r} outside 0 .. {cr.MAX_CAP}")
+        from .checksums import sources
+        ptrs = sources(src, ordinals, lambda i: self.pic_bytes(sids[i]))
+        shapes = [cr.plane_shape(self._geometry(sids[i]), table[which[i] if which else 0].plane) for i in range(n)]
+
+        def taken(given, name, shape, dtype):
+            if given is None:
+                return [torch.empty(shape(i), dtype=dtype, device="cuda") for i in range(n)]
+
+            def one(i, t):
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape(i)) or not t.is_contiguous():
+                    raise ValueError(f"{name}[{i}] must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape(i))}")
+                if t.data_ptr() & 15:
+                    raise ValueError(f"{name}[{i}]: pointer {t.data_ptr():#x} must be a multiple of 16")
+            try:
+                return Context._out_list(given, n, one)
+            except ValueError as e:
+                raise ValueError(str(e).replace("out", name)) from None
+        mask = taken(mask, "mask", lambda i: (self.pic_bytes(sids[i]),), torch.uint8)
+        points = taken(points, "points", lambda i: (cap + 1, 4), torch.int64)
+        rows = taken(rows, "rows", lambda i: (shapes[i][0] + 1,), torch.int32)
+        asked = response is not None and response is not False
+        if asked:
+            response = taken(None if response is True else response, "response", lambda i: shapes[i], torch.int64)
+        if not n:
+            return (mask, points, rows, response) if asked else (mask, points, rows)
+        a_s, a_o, stream = Context._launch_args(mask[0].device, sids, ordinals)
+        from ._lib import HvqCornerRule
+        a_r = (HvqCornerRule * len(table))(*[r.struct() for r in table])
+        a_w = Context._which_array(which, n)
+        a_m = Context._ptr_array([t.data_ptr() for t in mask])
+        a_p = Context._ptr_array([t.data_ptr() for t in points])
+        a_y = Context._ptr_array([t.data_ptr() for t in rows])
+        a_q = Context._ptr_array([t.data_ptr() for t in response]) if asked else None
+        check(lib().hvq_corner_pictures(self._h, n, a_s, a_o, Context._ptr_array(ptrs), C.cast(a_r, C.c_void_p), len(table), a_w, a_m, a_p, a_y, a_q, cap,
+                                        stream))
+        return (mask, points, rows, response) if asked else (mask, points, rows)
+
     def select_components(self, sids, labels, comps, select, which=None, out=None):
         """hvq_select_components: label maps and record tables of the Y planes (label_pictures' results under a rule with plane 0) back
         into uint8 pictures IN SLOT LAYOUT of the geometries of sids[i]: Y 255 where the sample's component has a record and its

@@ -957,5 +957,60 @@ static_assert(HVQ_WN_TX * HVQ_WN_TY == HVQ_WN_LANES * 4u && HVQ_WN_TX % 4u == 0u
 _Static_assert(sizeof(HvqIntegralJob) == 48 && sizeof(HvqWindowJob) == 80 && sizeof(HvqRectHead) == 32 && sizeof(HvqRectTables) == 16, "job tables are uploaded in 16-byte units");
 #endif
 
+/* one picture of the four corner launches (hvq_corner.hip, hvq_corner_pictures): the plane of the picture's rule, the same plane of the
+ * mask picture, the two planes of the mask that are only filled, and the lists.  Grid row = picture in every launch.  A tile is
+ * HVQ_CR_TX x HVQ_CR_TY targets; a workgroup of HVQ_CR_LANES lanes stages its bytes with a halo of nms + radius + 1 rows and
+ * HVQ_CR_HX columns (whole dwords), a lane stores one dword of the mask.  The workgroups of a grid row of launch 1 walk the tx ty tiles
+ * of the analysed plane, then the fill tiles (HVQ_CR_FILL dwords each) of the two other planes; those past them leave.  In LDS
+ * (hvq_corner.h says what lies where): the staged bytes and the packed gradients, over which the responses are written later, and the
+ * three horizontal sums.  Every member is a dword or a qword; 128 bytes. */
+#define HVQ_CR_LANES   256u
+#define HVQ_CR_TX      64u
+#define HVQ_CR_TY      16u
+#define HVQ_CR_MAX_R   3u            /* HVQ_CRN_MAX_RADIUS */
+#define HVQ_CR_MAX_NMS 7u            /* HVQ_CRN_MAX_NMS */
+#define HVQ_CR_HX      12u           /* bytes staged left and right of a tile's 64: nms + radius + 1 <= 11 rounded up to whole dwords */
+#define HVQ_CR_SD      ((HVQ_CR_TX + 2u * HVQ_CR_HX) / 4u)                              /* 22 dwords a staged row */
+#define HVQ_CR_SROWS   (HVQ_CR_TY + 2u * (HVQ_CR_MAX_NMS + HVQ_CR_MAX_R + 1u))         /* 38 staged rows at the most */
+#define HVQ_CR_GROWS   (HVQ_CR_TY + 2u * (HVQ_CR_MAX_NMS + HVQ_CR_MAX_R))              /* 36 rows of gradients */
+#define HVQ_CR_GS      85u           /* dwords a row of gradients: 64 + 2 (7 + 3) = 84 and one more, an odd pitch for the lanes that walk rows */
+#define HVQ_CR_HS      79u           /* dwords a row of horizontal sums and qwords a row of responses: 64 + 2 7 = 78 and one more */
+#define HVQ_CR_RROWS   (HVQ_CR_TY + 2u * HVQ_CR_MAX_NMS)                               /* 30 rows of responses */
+#define HVQ_CR_S_AT    0u
+#define HVQ_CR_G_AT    (HVQ_CR_SROWS * HVQ_CR_SD)                                        /* 836 */
+#define HVQ_CR_R_AT    0u            /* the responses lie over the staged bytes and the gradients, which are dead by then */
+#define HVQ_CR_H_AT    (2u * HVQ_CR_RROWS * HVQ_CR_HS)                                   /* 4740 */
+#define HVQ_CR_HPLANE  (HVQ_CR_GROWS * HVQ_CR_HS)                                        /* 2844 dwords each of the sums of gx gx, gx gy, gy gy */
+#define HVQ_CR_LDS     (HVQ_CR_H_AT + 3u * HVQ_CR_HPLANE)                                /* 13272 dwords: 53088 bytes, three workgroups a CU */
+#define HVQ_CR_HSEG    13u           /* columns a lane of the horizontal pass slides along: 36 rows x 6 segments <= 256 lanes */
+#define HVQ_CR_VSEG    10u           /* rows a lane of the vertical pass slides down: 78 columns x 3 segments <= 256 lanes */
+#define HVQ_CR_FILL    (HVQ_CR_LANES * 4u)   /* dwords of a fill tile: sixteen bytes a lane */
+typedef struct HvqCornerJob {
+    uint64_t src;                      /* device address of the analysed plane, a multiple of 4 */
+    uint64_t mask;                     /* device address of the same plane of the mask picture, a multiple of 4 */
+    uint64_t points;                   /* device address of int64 [cap + 1][4], a multiple of 16 */
+    uint64_t rows;                     /* device address of uint32 [ny + 1], a multiple of 16 */
+    uint64_t response;                 /* device address of int64 [ny][nx], a multiple of 16; 0: none */
+    uint64_t fill[2];                  /* device addresses of the two other planes of the mask picture, multiples of 4 */
+    int64_t threshold;
+    uint32_t nx, ny;                   /* the plane; nx is a multiple of 4 */
+    uint32_t tx, ty;                   /* tiles across and down */
+    uint32_t mode, radius, k, nms, margin;
+    uint32_t cap;                      /* rows the list has room for */
+    uint32_t fill_dwords[2], fill_value[2], fill_tiles[2];
+} HvqCornerJob;
+
+#if defined(__cplusplus)
+static_assert(sizeof(HvqCornerJob) == 128, "job tables are uploaded in 16-byte units");
+static_assert(HVQ_CR_TX * HVQ_CR_TY == HVQ_CR_LANES * 4u && HVQ_CR_TX == 64u, "a lane stores one dword of the tile");
+static_assert(HVQ_CR_HX >= HVQ_CR_MAX_NMS + HVQ_CR_MAX_R + 1u && HVQ_CR_HX % 4u == 0u, "the staged row: whole dwords that hold the halo");
+static_assert(HVQ_CR_GS > HVQ_CR_TX + 2u * (HVQ_CR_MAX_NMS + HVQ_CR_MAX_R) && HVQ_CR_HS > HVQ_CR_TX + 2u * HVQ_CR_MAX_NMS, "the pitches hold the widest rows");
+static_assert(HVQ_CR_G_AT + HVQ_CR_GROWS * HVQ_CR_GS <= HVQ_CR_H_AT && HVQ_CR_R_AT % 2u == 0u, "the responses cover the staged bytes and the gradients, as qwords");
+static_assert(HVQ_CR_GROWS * ((HVQ_CR_TX + 2u * HVQ_CR_MAX_NMS + HVQ_CR_HSEG - 1u) / HVQ_CR_HSEG) <= HVQ_CR_LANES, "a lane a segment of the horizontal pass");
+static_assert((HVQ_CR_TX + 2u * HVQ_CR_MAX_NMS) * ((HVQ_CR_RROWS + HVQ_CR_VSEG - 1u) / HVQ_CR_VSEG) <= HVQ_CR_LANES, "a lane a segment of the vertical pass");
+#else
+_Static_assert(sizeof(HvqCornerJob) == 128, "job tables are uploaded in 16-byte units");
+#endif
+
 
 #endif

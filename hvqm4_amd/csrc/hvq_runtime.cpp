@@ -47,6 +47,7 @@
 #include "hvq_bilateral.h"
 #include "hvq_map.h"
 #include "hvq_label.h"
+#include "hvq_corner.h"
 #include "hvq_distance.h"
 #include "hvq_integral.h"
 #include "hvq_warp.h"
@@ -111,6 +112,8 @@ extern "C" __attribute__((weak)) hipError_t hvq_launch_tables(const void *jobs_d
 extern "C" __attribute__((weak)) hipError_t hvq_launch_label(const void *jobs_dev, int npics, uint32_t max_tiles, uint32_t max_seams, uint32_t max_chunks,
                                                              hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_select(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
+/* hvq_corner.hip.  Weak for the same reason: hvq_corner_pictures then refuses with HVQ_E_NOGPU */
+extern "C" __attribute__((weak)) hipError_t hvq_launch_corner(const void *jobs_dev, int npics, uint32_t max_tiles, uint32_t max_rows, hipStream_t stream);
 /* hvq_distance.hip.  Weak for the same reason: hvq_distance_pictures and hvq_distance_mask then refuse with HVQ_E_NOGPU */
 extern "C" __attribute__((weak)) hipError_t hvq_launch_distance(const void *jobs_dev, int npics, uint32_t max_colgroups, uint32_t max_rowgroups, hipStream_t stream);
 extern "C" __attribute__((weak)) hipError_t hvq_launch_distance_mask(const void *jobs_dev, int npics, uint32_t max_tiles, hipStream_t stream);
@@ -3559,6 +3562,92 @@ HVQ_EXPORT int hvq_select_components(HvqContext *c, int n, const int *streams, c
     }
     HIPCHK(hipSetDevice(c->device));
     return slot_enqueue(c, hvq_launch_select, "select", "hvq_label.hip", jobs, n, max_tiles, hip_stream);
+}
+
+/* Corners of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Corners").  The four launches of a call go
+ * behind ONE job table; there is no memory besides the outputs. */
+HVQ_EXPORT int hvq_corner_check(const HvqCornerRule *r)
+{
+    if (!r) return fail(HVQ_E_ARG, "bad arguments");
+    if (r->plane < 0 || r->plane > 2) return fail(HVQ_E_ARG, "corner rule: plane %d (0 Y, 1 U, 2 V)", r->plane);
+    if (r->mode != HVQ_CRN_HARRIS && r->mode != HVQ_CRN_MIN_EIGEN) return fail(HVQ_E_ARG, "corner rule: mode %d (0 Harris, 1 min-eigenvalue)", r->mode);
+    if (r->radius < 1 || r->radius > HVQ_CRN_MAX_RADIUS) return fail(HVQ_E_ARG, "corner rule: radius %d outside 1 .. %d", r->radius, HVQ_CRN_MAX_RADIUS);
+    if (r->k < 0 || r->k > 64 || (r->mode == HVQ_CRN_MIN_EIGEN && r->k)) return fail(HVQ_E_ARG, "corner rule: k %d (0 .. 64 under Harris, 0 under min-eigenvalue)", r->k);
+    if (r->nms < 0 || r->nms > HVQ_CRN_MAX_NMS) return fail(HVQ_E_ARG, "corner rule: nms %d outside 0 .. %d", r->nms, HVQ_CRN_MAX_NMS);
+    if (r->margin < 0 || r->margin > 255) return fail(HVQ_E_ARG, "corner rule: margin %d outside 0 .. 255", r->margin);
+    if (r->threshold < 1) return fail(HVQ_E_ARG, "corner rule: threshold %lld (at least 1)", (long long)r->threshold);
+    if (r->pad[0] || r->pad[1]) return fail(HVQ_E_ARG, "corner rule: pad %d, %d (0)", r->pad[0], r->pad[1]);
+    return HVQ_OK;
+}
+
+static int corner_plane(int width, int height, int h_samp, int v_samp, int plane, int64_t *nx, int64_t *ny)
+{
+    { int rc = geometry_supported(width, height, h_samp, v_samp); if (rc) return rc; }
+    if (plane < 0 || plane > 2) return fail(HVQ_E_ARG, "plane %d (0 Y, 1 U, 2 V)", plane);
+    const SlotShape s = slot_shape(width, height, h_samp, v_samp);
+    *nx = s.w >> (plane ? s.xs : 0); *ny = s.h >> (plane ? s.ys : 0);
+    return HVQ_OK;
+}
+
+HVQ_EXPORT int64_t hvq_corner_rows_bytes(int width, int height, int h_samp, int v_samp, int plane)
+{
+    int64_t nx = 0, ny = 0;
+    { int rc = corner_plane(width, height, h_samp, v_samp, plane, &nx, &ny); if (rc) return rc; }
+    return 4 * (ny + 1);
+}
+
+HVQ_EXPORT int64_t hvq_corner_response_bytes(int width, int height, int h_samp, int v_samp, int plane)
+{
+    int64_t nx = 0, ny = 0;
+    { int rc = corner_plane(width, height, h_samp, v_samp, plane, &nx, &ny); if (rc) return rc; }
+    return 8 * nx * ny;
+}
+
+HVQ_EXPORT int hvq_corner_pictures(HvqContext *c, int n, const int *streams, const int *ordinals, const void *const *src,
+                                   const HvqCornerRule *rules, int nrules, const int *which, uint8_t *const *mask, int64_t *const *points,
+                                   uint32_t *const *rows, int64_t *const *response, int cap, void *hip_stream)
+{
+    static_assert(HVQ_CRN_HARRIS == (int)HVQ_CR_HARRIS && HVQ_CRN_MIN_EIGEN == (int)HVQ_CR_MIN_EIGEN && HVQ_CRN_MAX_RADIUS == (int)HVQ_CR_MAX_R &&
+                  HVQ_CRN_MAX_NMS == (int)HVQ_CR_MAX_NMS && sizeof(HvqCornerRule) == 40 && offsetof(HvqCornerRule, threshold) == 32,
+                  "the header's values and layout are the kernel's");
+    if (!c || n < 0 || (n && (!streams || !ordinals || !mask || !points || !rows || !rules))) return fail(HVQ_E_ARG, "bad arguments");
+    { int rc = count_check(n, "pictures"); if (rc) return rc; }
+    if (!n) return HVQ_OK;
+    if (nrules < 1 || nrules > HVQ_CRN_MAX_RULES) return fail(HVQ_E_ARG, "%d rules: one call takes 1 .. %d", nrules, HVQ_CRN_MAX_RULES);
+    for (int r = 0; r < nrules; ++r) { int rc = hvq_corner_check(rules + r); if (rc) return rc; }
+    if (cap < 0 || cap > HVQ_CRN_MAX_CAP) return fail(HVQ_E_ARG, "cap %d outside 0 .. %d", cap, HVQ_CRN_MAX_CAP);
+    { int rc = chain_begin(c, n, streams, ordinals, src, nullptr); if (rc) return rc; }
+    std::vector<HvqCornerJob> jobs((size_t)n);
+    uint32_t max_tiles = 0, max_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t *a = nullptr;
+        { int rc = picture_source(c, i, streams, ordinals, src, &a); if (rc) return rc; }
+        const Stream &s = c->streams[(size_t)streams[i]];
+        { int rc = slot_pointer_check("mask", i, mask[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("point list", i, points[i]); if (rc) return rc; }
+        { int rc = slot_pointer_check("row index", i, rows[i]); if (rc) return rc; }
+        int64_t *const resp = response ? response[i] : nullptr;
+        if ((uintptr_t)resp & 15u) return fail(HVQ_E_ARG, "response map %d: the pointer must be a multiple of 16", i);
+        const int r = which ? which[i] : 0;
+        if (r < 0 || r >= nrules) return fail(HVQ_E_ARG, "picture %d: rule %d of %d", i, r, nrules);
+        const HvqCornerRule &rule = rules[r];
+        uint64_t off[3] = { 0, 0, 0 }, from = 0;
+        uint32_t dw[3] = { 0, 0, 0 }, px = 0, py = 0;
+        plane_walk(slot_shape(s), [&](int p, size_t o, uint32_t nx, uint32_t ny) {
+            off[p] = o; dw[p] = (nx >> 2) * ny;
+            if (p == rule.plane) { from = o; px = nx; py = ny; }
+            return 0;
+        });
+        HvqCornerJob &j = jobs[(size_t)i];
+        j = hvq_cr_job((uint64_t)(uintptr_t)(a + from), (uint64_t)(uintptr_t)mask[i], off, dw, (uint32_t)rule.plane, (uint64_t)(uintptr_t)points[i],
+                       (uint64_t)(uintptr_t)rows[i], (uint64_t)(uintptr_t)resp, px, py, (uint32_t)rule.mode, (uint32_t)rule.radius, (uint32_t)rule.k,
+                       (uint32_t)rule.nms, (uint32_t)rule.margin, rule.threshold, (uint32_t)cap);
+        max_tiles = std::max(max_tiles, hvq_cr_tiles(j));
+        max_rows = std::max(max_rows, j.ny);
+    }
+    { int rc = kernel_check(hvq_launch_corner, "corner", "hvq_corner.hip", true); if (rc) return rc; }
+    return export_enqueue(c, jobs.data(), jobs.size() * sizeof(HvqCornerJob), hip_stream,
+                          [=](const void *t, hipStream_t st) { return hvq_launch_corner(t, n, max_tiles, max_rows, st); });
 }
 
 /* Exact distance transforms of resident pictures (include/hvqm4_amd.h: the specification; DESIGN.md 4.5, "Distances").  The two launches

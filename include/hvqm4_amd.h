@@ -1112,6 +1112,79 @@ typedef struct HvqSelect { uint32_t area_min, area_max, w_min, w_max, h_min, h_m
 int     hvq_select_components(HvqContext *ctx, int n, const int *streams, const uint32_t *const *labels, const uint64_t *const *comps,
                               int cap, const HvqSelect *sel, int nsel, const int *which, void *const *dst, void *hip_stream);
 
+/* CORNERS of resident pictures, where they lie: the trackable points of ONE plane of each of `n` pictures, of any streams, sizes and
+ * samplings -- Harris' measure or the smaller eigenvalue of the structure tensor (Shi-Tomasi) --, as a mask picture, a row index and an
+ * ordered list, on the caller's HIP stream and without a host synchronisation.  It is the step between a filter and motion: gradients
+ * give edges, this gives the points a map can be fitted through.  This text is the authority for the values.  All values are exact
+ * integers; nothing is rounded except the one floor square root.
+ *   Samples.   Picture i goes through rules[which[i]] (which == NULL: rules[0] for all).  a*(y, x) = a[clamp(y)][clamp(x)] of plane
+ *              rule.plane (0 Y, 1 U, 2 V; Nx x Ny samples at the plane's own resolution): borders are replicated, as in
+ *              hvq_filter_pictures.
+ *   Gradients. The 3 x 3 Sobel pair at any integer position, inside the plane or not:
+ *              gx(y, x) = a*(y-1, x+1) + 2 a*(y, x+1) + a*(y+1, x+1) - a*(y-1, x-1) - 2 a*(y, x-1) - a*(y+1, x-1), gy its transpose
+ *              (rows y+1 minus rows y-1).  |g| <= 4 * 255 = 1020.
+ *   Sums.      Over the (2r + 1)^2 positions around (y, x), r = rule.radius in 1 .. HVQ_CRN_MAX_RADIUS, positions outside the plane
+ *              included (their gradients read a*): A = sum gx^2, B = sum gx gy, C = sum gy^2, T = A + C.
+ *              A, C <= 49 * 1020^2 = 50 979 600 < 2^26, |B| < 2^26 likewise, T < 2^27.
+ *   Response.  R, int64.  HVQ_CRN_HARRIS: R = 256 (A C - B^2) - k T^2 with k in 1/256ths, 0 <= k <= 64 (k = 10 is the usual 0.04).
+ *              A C >= B^2 (Cauchy-Schwarz), so 0 <= 256 (A C - B^2) < 2^8 * 2^52 = 2^60 and 0 <= k T^2 <= 2^6 * 2^54 = 2^60: |R| < 2^61.
+ *              HVQ_CRN_MIN_EIGEN: R = T - isqrt((A - C)^2 + 4 B^2), isqrt the floor square root; the radicand is below 2^52 + 2^54 < 2^55
+ *              and at most T^2, so 0 <= R < 2^27: R is twice the smaller eigenvalue, rounded up.  k must be 0 in this mode.
+ *   Corners.   A sample p = (x, y) is a corner when margin <= x < Nx - margin and margin <= y < Ny - margin (0 <= margin <= 255),
+ *              R(p) >= threshold (threshold >= 1), and no sample q != p OF THE PLANE with |qx - px| <= nms and |qy - py| <= nms beats
+ *              it.  q beats p when R(q) > R(p), or R(q) == R(p) and q's raster index y Nx + x is the smaller.  Samples in the margin
+ *              still suppress.  nms = 0 keeps every sample over the threshold.  The order is total: the result does not depend on the
+ *              order of evaluation.
+ *   mask[i]    a DEVICE pointer, a non-null multiple of 16: a uint8 picture in slot layout of the geometry of streams[i],
+ *              hvq_stream_pic_bytes bytes, every byte written once.  The analysed plane holds 255 at corners and 0 elsewhere; of the
+ *              planes that were not analysed Y is filled with 0, U and V with 128.  It goes wherever `src` goes.
+ *   rows[i]    a DEVICE pointer, a non-null multiple of 16: uint32 [Ny + 1], hvq_corner_rows_bytes bytes.  rows[y] is the number of
+ *              corners in the rows above y, rows[Ny] = K: a row index into the list.  While the work runs it holds working values.
+ *   points[i]  a DEVICE pointer, a non-null multiple of 16: int64 [cap + 1][4], cap in 0 .. HVQ_CRN_MAX_CAP.  Row 0 is {K, stored =
+ *              min(K, cap), status = 0, 0}.  Row j, 1 <= j <= stored, is {x, y, R, y Nx + x}, in ascending raster order.  Rows beyond
+ *              `stored` are not touched.
+ *   response   NULL, or an array of n entries, each NULL or a DEVICE pointer, a multiple of 16: int64 [Ny][Nx],
+ *              hvq_corner_response_bytes bytes, every R of the plane.
+ *   Known answers (both modes, r = 1, 2, 3).  A flat plane: K = 0 under every rule.  One straight vertical 0 | 255 edge: R <= 0 (Harris)
+ *              or R = 0 (min-eigenvalue) everywhere, K = 0.  A 0 / 255 checkerboard of single samples: R = 0 at every sample further
+ *              than r + 1 from the border (both Sobel columns have the same parity there); with nms = 1 and threshold = 1 its corners
+ *              are exactly the four corners of the plane.  Stripes of period 4 (0, 0, 255, 255 along x): every |gx| = 1020, gy = 0;
+ *              under Harris with k = 64 and r = 3 the most negative R is -64 (49 * 1020^2)^2 = -166 330 855 434 240 000, which needs 58
+ *              bits; under min-eigenvalue R = 0 everywhere.  A 32 x 24 plane that is 255 for y >= 10, x >= 13 and 0 elsewhere, under
+ *              Harris with r = 1, k = 10, nms = 3, threshold = 1: exactly one corner, (x, y) = (13, 10) with R = 2 192 466 340 080 000;
+ *              with r = 2 it is (14, 11), with r = 3 (15, 12).
+ *   hvq_corner_check (host only): HVQ_OK, or HVQ_E_ARG for a NULL rule, a plane outside 0 .. 2, an unknown mode, a radius outside
+ *              1 .. HVQ_CRN_MAX_RADIUS, k outside 0 .. 64 or k != 0 under HVQ_CRN_MIN_EIGEN, nms outside 0 .. HVQ_CRN_MAX_NMS, a margin
+ *              outside 0 .. 255, threshold < 1, a pad that is not 0.
+ *   hvq_corner_rows_bytes, hvq_corner_response_bytes (host only): 4 (Ny + 1) and 8 Nx Ny of that plane of such a picture;
+ *              HVQ_E_GEOMETRY, or HVQ_E_ARG for the plane.
+ *   The call.  Four launches behind one job table, and no memory besides the outputs: a workgroup stages a 64 x 16 tile with a halo of
+ *              nms + r + 1, takes the gradients once per position, slides the three sums along the rows and down the columns, leaves
+ *              the responses of the tile and its nms halo in LDS and suppresses from there; a wave a row counts the mask's corners;
+ *              one workgroup a picture scans the counts into rows and writes row 0 of points; a wave a row places its corners.
+ *   HVQ_E_ARG for the whole call: what hvq_corner_check refuses, in any entry, used or not; nrules outside 1 .. HVQ_CRN_MAX_RULES; a
+ *              which[i] outside 0 .. nrules - 1; cap outside 0 .. HVQ_CRN_MAX_CAP; a null or misaligned mask[i], points[i] or rows[i]; a
+ *              misaligned response[i]; n above 65535; a bad stream or ordinal; a src[i] with an ordinal other than -1 or that is no
+ *              multiple of 16; a NULL context, rules, mask, points or rows.  n == 0 is HVQ_OK and does nothing.  Every argument is
+ *              checked before anything is enqueued: a refused call leaves every output untouched.  HVQ_E_NOGPU (after those checks)
+ *              from a build without the corner kernels.
+ *   a_i and `src`, lookup, the HVQ_E_STATE cases, ordering on `hip_stream`, membership of the export chain, slot safety and ending the
+ *   batch in flight only when a requested picture belongs to it are hvq_label_pictures'. */
+#define HVQ_CRN_MAX_RULES   64
+#define HVQ_CRN_MAX_CAP     (1 << 20)
+#define HVQ_CRN_MAX_RADIUS  3      /* structure window (2r+1)^2, r in 1..3 */
+#define HVQ_CRN_MAX_NMS     7
+#define HVQ_CRN_HARRIS      0
+#define HVQ_CRN_MIN_EIGEN   1
+typedef struct HvqCornerRule { int32_t plane, mode, radius, k, nms, margin, pad[2]; int64_t threshold; } HvqCornerRule;  /* 40 bytes */
+int     hvq_corner_check(const HvqCornerRule *r);
+int64_t hvq_corner_rows_bytes(int width, int height, int h_samp, int v_samp, int plane);      /* 4 (Ny + 1) */
+int64_t hvq_corner_response_bytes(int width, int height, int h_samp, int v_samp, int plane);  /* 8 Nx Ny */
+int     hvq_corner_pictures(HvqContext *ctx, int n, const int *streams, const int *ordinals, const void *const *src,
+                            const HvqCornerRule *rules, int nrules, const int *which,
+                            uint8_t *const *mask, int64_t *const *points, uint32_t *const *rows, int64_t *const *response,
+                            int cap, void *hip_stream);
+
 /* EXACT DISTANCE TRANSFORMS of resident pictures, where they lie: for ONE plane of each of `n` pictures, of any streams, sizes and
  * samplings, how far every foreground sample is from the background, on the caller's HIP stream and without a host synchronisation.
  * It is the step behind a mask that labelling is not: erosion and dilation by a disc of any radius, the thickness of an object, seeds
